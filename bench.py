@@ -30,7 +30,10 @@ the GEMMs on the bf16 matrix cores through an exact three-term split of every fp
 (six products per 16 k, dropped terms below 2^-26 |a b|; per-layer error vs fp64 within the
 fp32 dot-product bound, tests/test_gpu_f32_net.py::test_gemm_layers_are_fp32_class);
 ``--dtype bf16`` is the opt-in bf16-operand mode.  Run: ``python bench.py [--gpus N --steps K --warmup W]`` (N>1
-under torch.distributed.run, one process per GPU).
+under torch.distributed.run, one process per GPU).  A plain run does only what the headline
+figure needs (set-up, warm-up, the K timed steps, the result line); ``--full`` adds the
+measurements that take steps of their own (``host_launch_ms_per_step``), and
+``--dump-outputs DIR`` writes what the last timed step computed as ``DIR/<name>.npy``.
 """
 from __future__ import annotations
 
@@ -92,6 +95,14 @@ def parse():
                     help="run the actor graph after the learner step on the same stream (default: the actor "
                          "graph runs on its own HIP stream, concurrent with the learner step)")
     ap.add_argument("--seed", type=int, default=1122)
+    ap.add_argument("--full", action="store_true",
+                    help="also take the measurements beside the headline figure that need runs of their own "
+                         "(host_launch_ms_per_step: 20 extra untimed steps, each enqueued into an idle GPU); "
+                         "a plain run sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last timed step left (parameters, gradient, loss, "
+                         "sampled indices / weights / new priorities, the actor's Q values) as DIR/<name>.npy "
+                         "(float32 / float64); --algo apex, 1 GPU or rank 0")
     ap.add_argument("--profile-steps", type=int, default=0, help="extra untimed steps after timing (for rocprof)")
     ap.add_argument("--no-reserve", dest="reserve", action="store_false",
                     help="do not take the actor stream from the pool before the process group")
@@ -147,6 +158,8 @@ def parse():
                     help="central topology: actors run free (default: paced at --actor-steps packets per learner "
                          "step per actor through the credit window)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.algo != "apex" or args.actor_only):
+        ap.error("--dump-outputs covers the Ape-X DQN engines (--algo apex, not --actor-only)")
     if args.actor_steps < 1:
         ap.error("--actor-steps must be >= 1 (the overlapped engine stages one actor step per learner step)")
     return args
@@ -166,6 +179,30 @@ def _host_launch_cost(eng, device, n: int = 20) -> float:
         lat.append(time.perf_counter() - t1)
     torch.cuda.synchronize(device)
     return statistics.median(lat)
+
+
+def dump_outputs(out_dir: str, learner, actor_q) -> dict:
+    """``--dump-outputs``: the arrays the last timed step left with its caller, one .npy each
+    (float32 as computed; integer arrays as float64, exact below 2^53).  All of them together
+    are ~7 MB at the default shapes (two parameter-sized vectors dominate)."""
+    arrays = {
+        "params": learner.flat,                # the network after the step's optimizer update
+        "grad": learner.flat_grad,             # the step's (pre-clip) gradient
+        "loss": learner.loss,
+        "norms": learner.norms,                # grad L2, (unused), clip coefficient, lr
+        "batch_idx": learner.idx.double(),     # the step's PER draw ...
+        "is_weights": learner.w,               # ... its importance weights ...
+        "new_priorities": learner.prio,        # ... and the priorities written back
+        "actor_q": actor_q,                    # the actor step's Q values, [envs, actions]
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float32 if a.dtype not in (np.float32, np.float64) else a.dtype, copy=False)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
 
 
 class Watchdog:
@@ -346,7 +383,9 @@ def main():
         dist.barrier()
     torch.cuda.synchronize(device)
     dt = time.perf_counter() - t0
-    host_launch = _host_launch_cost(eng, device)  # extra untimed steps after the timed region
+    dumped = dump_outputs(args.dump_outputs, eng.learner, eng.actor.q) if args.dump_outputs and rank == 0 else None
+    # --full: extra untimed steps after the timed region
+    host_launch = _host_launch_cost(eng, device) if args.full else None
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -422,7 +461,8 @@ def main():
             # wall time of the enqueue loop: includes waiting on a full launch queue (back-pressure)
             "host_enqueue_ms_per_step": round(1000.0 * t_host / args.steps, 4),
             # one train_step's host cost with the GPU idle (no back-pressure), median of 20
-            "host_launch_ms_per_step": round(1000.0 * host_launch, 4),
+            "host_launch_ms_per_step": round(1000.0 * host_launch, 4) if args.full else None,
+            "dumped_outputs": dumped,
             "last_loss": round(stats["loss"], 6),
             "last_grad_norm_l2": round(stats["grad_norm_l2"], 6),
         }
@@ -666,6 +706,9 @@ def central(args, rank, world, device, wd, pre=None, emulate: int = 0):
     dt = time.perf_counter() - t0
     packets = sum(eng.applied.values()) - a0
     wd.kick()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng.learner, eng.actor.q if getattr(eng, "actor", None) is not None
+                     else torch.zeros(0, args.actions))
     links = eng.close()
     wd.off()
     st = eng.learner.stats()

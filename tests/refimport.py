@@ -4,7 +4,9 @@ The reference needs ``gym`` (absent here) and relies on ``np.array(x, copy=False
 (an error on NumPy 2).  We register a stub ``gym`` module whose ``spaces`` are this
 framework's Box/Discrete and import the reference files under private names with a
 NumPy shim applied only inside them.  Nothing from the reference is copied into the
-framework; tests skip when /root/reference is absent.
+framework.  The suite itself never imports the reference: ``scripts/make_golden.py`` does,
+to record the results the tests compare with (``tests/golden/``); it names the reference
+checkout through ``configure(path)`` or ``APEX_REFERENCE_DIR``.
 """
 from __future__ import annotations
 
@@ -15,11 +17,16 @@ import types
 
 import numpy as np
 
-REF = "/root/reference"
+REF = os.environ.get("APEX_REFERENCE_DIR", "")
+
+
+def configure(path: str) -> None:
+    global REF
+    REF = os.path.abspath(path)
 
 
 def available() -> bool:
-    return os.path.isdir(REF) and os.path.exists(os.path.join(REF, "memory.py"))
+    return bool(REF) and os.path.isdir(REF) and os.path.exists(os.path.join(REF, "memory.py"))
 
 
 def _stub_gym():

@@ -15,9 +15,11 @@ from apex_amd.envs import make
 from apex_amd.model import AQL
 from apex_amd.trainers.aql import aql_update
 
-from . import refimport
+from . import goldens
 
-pytestmark = pytest.mark.skipif(not refimport.available(), reason="reference not mounted")
+AQL_DIS_ENVS = ["CartPole-v0", "BipedalWalker-v3"]
+AQL_DIS_STEPS, AQL_DIS_LR, AQL_DIS_B = 3, 1e-3, 32
+BATCH_FIELDS = ("s", "a", "r", "s2", "d", "a_mu", "w")
 
 
 def _batch(env, model, B, seed):
@@ -83,39 +85,69 @@ def _grads(m):
     return {n: (None if p.grad is None else p.grad.detach().clone()) for n, p in m.named_parameters()}
 
 
-@pytest.mark.parametrize("env_id", ["CartPole-v0", "BipedalWalker-v3"])
-def test_aql_dis_step_matches_reference(env_id):
-    ref_model = refimport.load("model")
-    ref_utils = refimport.load("utils")
+def record_reference_steps(ref_model, ref_utils, env_id):
+    """The reference side of the test below, on the reference's own ``model.AQL`` and
+    ``utils`` modules: one dict of arrays per step (scripts/make_golden.py stores them as
+    tests/golden/aql_dis_<env>_step<k>.npz; step 0 also holds the initial state_dict)."""
     env = make(env_id)
+    shape = AQL(env, propose_sample=1, uniform_sample=50, device="cpu")  # (the batch's dimensions)
     torch.manual_seed(3)
     theirs = ref_model.AQL(env, propose_sample=1, uniform_sample=50, device="cpu")
     theirs_t = ref_model.AQL(env, propose_sample=1, uniform_sample=50, device="cpu")
     theirs_t.load_state_dict(theirs.state_dict())
+    for m in (theirs, theirs_t):
+        m.q.train()
+    opt_q_r = torch.optim.Adam(theirs.q.parameters(), AQL_DIS_LR)
+    opt_p_r = torch.optim.Adam(theirs.proposal.parameters(), AQL_DIS_LR)
+    steps = []
+    for step in range(AQL_DIS_STEPS):
+        rec = {}
+        if step == 0:
+            goldens.put_state(rec, "init", theirs.state_dict())
+        batch = _batch(env, shape, AQL_DIS_B, seed=100 + step)
+        for n, t in zip(BATCH_FIELDS, batch):
+            rec["batch/" + n] = t.numpy().copy()
+        torch.manual_seed(50 + step)  # reset_noise draws from the torch RNG: same stream for both
+        lq_r, lp_r, pr_r = _ref_td_step(ref_utils, theirs, theirs_t, opt_q_r, opt_p_r, batch, AQL_DIS_B, 1, 0.99, 0.8)
+        rec["loss_q"] = lq_r.detach().numpy().copy()
+        rec["loss_p"] = lp_r.detach().numpy().copy()
+        rec["prios"] = np.asarray(pr_r).copy()
+        goldens.put_state(rec, "grads", _grads(theirs))
+        goldens.put_state(rec, "model", theirs.state_dict())
+        goldens.put_state(rec, "target", theirs_t.state_dict())
+        steps.append(rec)
+    return steps
+
+
+@pytest.mark.parametrize("env_id", AQL_DIS_ENVS)
+def test_aql_dis_step_matches_reference(env_id):
+    env = make(env_id)
+    g0 = goldens.load(f"aql_dis_{env_id}_step0")
+    init = goldens.get_state(g0, "init")   # the reference model's own initial state_dict
     ours = AQL(env, propose_sample=1, uniform_sample=50, device="cpu")
     ours_t = AQL(env, propose_sample=1, uniform_sample=50, device="cpu")
-    ours.load_state_dict(theirs.state_dict())
-    ours_t.load_state_dict(theirs_t.state_dict())
-    assert list(ours.state_dict()) == list(theirs.state_dict())
-    for m in (theirs, theirs_t, ours, ours_t):
+    assert list(ours.state_dict()) == list(init)
+    ours.load_state_dict(init)
+    ours_t.load_state_dict(init)
+    for m in (ours, ours_t):
         m.q.train()
-    lr, B = 1e-3, 32
-    opt_q_r = torch.optim.Adam(theirs.q.parameters(), lr)
-    opt_p_r = torch.optim.Adam(theirs.proposal.parameters(), lr)
+    lr, B = AQL_DIS_LR, AQL_DIS_B
     opt_q_o = torch.optim.Adam(ours.q.parameters(), lr)
     opt_p_o = torch.optim.Adam(ours.proposal.parameters(), lr)
-    for step in range(3):
-        batch = _batch(env, ours, B, seed=100 + step)
-        torch.manual_seed(50 + step)  # reset_noise draws from the torch RNG: same stream for both
-        lq_r, lp_r, pr_r = _ref_td_step(ref_utils, theirs, theirs_t, opt_q_r, opt_p_r, batch, B, 1, 0.99, 0.8)
-        g_r = _grads(theirs)
+    for step in range(AQL_DIS_STEPS):
+        g = g0 if step == 0 else goldens.load(f"aql_dis_{env_id}_step{step}")
+        batch = tuple(torch.from_numpy(g["batch/" + n]) for n in BATCH_FIELDS)
+        for x, y in zip(batch, _batch(env, ours, B, seed=100 + step)):
+            assert torch.equal(x, y)   # the recorded batch is the seeded one
+        lq_r, lp_r, pr_r = torch.from_numpy(g["loss_q"]), torch.from_numpy(g["loss_p"]), g["prios"]
+        g_r = goldens.get_state(g, "grads")
         buf = _FixedBuffer(batch)
-        torch.manual_seed(50 + step)
+        torch.manual_seed(50 + step)  # reset_noise draws from the torch RNG: the stream the recording used
         lq_o, lp_o = aql_update(ours, ours_t, buf, opt_q_o, opt_p_o, B, 0.4, 0.99, 1, 0.8, "cpu",
                                 copy_proposal_to_target=True, reset_noise=True)
         g_o = _grads(ours)
-        torch.testing.assert_close(lq_o, lq_r, rtol=1e-6, atol=1e-7)
-        torch.testing.assert_close(lp_o, lp_r, rtol=1e-6, atol=1e-7)
+        torch.testing.assert_close(lq_o.detach(), lq_r, rtol=1e-6, atol=1e-7)
+        torch.testing.assert_close(lp_o.detach(), lp_r, rtol=1e-6, atol=1e-7)
         np.testing.assert_allclose(buf.prios, pr_r, rtol=1e-6, atol=1e-7)
         assert g_o.keys() == g_r.keys()
         for n in g_r:
@@ -124,8 +156,9 @@ def test_aql_dis_step_matches_reference(env_id):
                 torch.testing.assert_close(g_o[n], g_r[n], rtol=1e-5, atol=1e-7, msg=n)
         # Adam's first steps move a parameter by ~lr * g / (|g| + eps): for a gradient near 0 an
         # ulp-level gradient difference becomes a visible (but < 1 % of lr) parameter difference
-        for m_o, m_r in ((ours, theirs), (ours_t, theirs_t)):
-            for (n, a), b in zip(m_o.state_dict().items(), m_r.state_dict().values()):
+        for m_o, sd_r in ((ours, goldens.get_state(g, "model")), (ours_t, goldens.get_state(g, "target"))):
+            assert list(m_o.state_dict()) == list(sd_r)
+            for (n, a), b in zip(m_o.state_dict().items(), sd_r.values()):
                 torch.testing.assert_close(a, b, rtol=1e-5, atol=1e-2 * lr, msg=n)
 
 

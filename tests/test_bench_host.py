@@ -75,3 +75,41 @@ def test_actor_capacity_interpolates_measured_points():
     for e, fps in b.ACTOR_GPU_CAPACITY_FPS.items():
         assert b.actor_gpu_capacity(e) == pytest.approx(fps)
     assert b.ACTOR_GPU_CAPACITY_FPS[256] < b.actor_gpu_capacity(384) < b.ACTOR_GPU_CAPACITY_FPS[512]
+
+
+def test_plain_run_is_default_and_full_is_opt_in():
+    b = _bench()
+    old = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"]
+        a = b.parse()
+        assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, "")
+        sys.argv = ["bench.py", "--full", "--dump-outputs", "out"]
+        a = b.parse()
+        assert a.full and a.dump_outputs == "out"
+        sys.argv = ["bench.py", "--algo", "aql", "--dump-outputs", "out"]
+        with pytest.raises(SystemExit):
+            b.parse()
+    finally:
+        sys.argv = old
+
+
+def test_dump_outputs_writes_float_npy_per_array(tmp_path):
+    import types
+
+    import numpy as np
+    import torch
+
+    lr = types.SimpleNamespace(flat=torch.arange(6, dtype=torch.float32), flat_grad=torch.ones(6),
+                               loss=torch.tensor([0.5]), norms=torch.zeros(4),
+                               idx=torch.tensor([3, 2 ** 30, 7], dtype=torch.int32), w=torch.rand(3),
+                               prio=torch.rand(3))
+    shapes = _bench().dump_outputs(str(tmp_path / "d"), lr, torch.zeros(2, 18))
+    assert shapes["actor_q"] == [2, 18] and shapes["params"] == [6]
+    total = 0
+    for name in shapes:
+        a = np.load(tmp_path / "d" / (name + ".npy"))
+        assert a.dtype in (np.float32, np.float64) and list(a.shape) == shapes[name]
+        total += a.nbytes
+    assert total < 64 * 2 ** 20
+    assert np.load(tmp_path / "d" / "batch_idx.npy").tolist() == [3.0, float(2 ** 30), 7.0]

@@ -3,14 +3,13 @@ forward against the reference model classes, losses vs reference utils."""
 import random
 
 import numpy as np
-import pytest
 import torch
 
 from apex_amd.envs import make
 from apex_amd.model import AQL, DuelingDQN, NoisyLinear
 from apex_amd.models.dqn import env_spec
 
-from . import refimport
+from . import goldens
 
 ATARI_KEYS = [("features.0.weight", (32, 4, 8, 8)), ("features.0.bias", (32,)), ("features.2.weight", (64, 32, 4, 4)),
               ("features.2.bias", (64,)), ("features.4.weight", (64, 64, 3, 3)), ("features.4.bias", (64,)),
@@ -56,52 +55,82 @@ def test_aql_param_counts_and_keys():
     assert a_mu.shape == (1, 51, 4) and q.shape == (1, 51)
 
 
-@pytest.mark.skipif(not refimport.available(), reason="reference not mounted")
-def test_dueling_forward_matches_reference_model():
-    ref = refimport.load("model")
+def _dueling_forward_case():
+    """Weights and input of the dueling differential test, from NumPy's legacy generator (the
+    3.5 MB of Atari-sized weights are regenerated, not stored: that stream never changes)."""
     env = env_spec((4, 84, 84), 18)
-    theirs = ref.DuelingDQN(env)
     ours = DuelingDQN(env)
-    ours.load_state_dict(theirs.state_dict())  # their checkpoint loads into ours
-    theirs.load_state_dict(ours.state_dict())  # and vice versa
-    x = torch.randint(0, 256, (3, 4, 84, 84)).float()
-    torch.testing.assert_close(ours(x), theirs(x))
-    random.seed(0)
-    a1 = ours.act(x[0], 0.3)
-    random.seed(0)
-    a2 = theirs.act(x[0], 0.3)
-    assert a1[0] == a2[0]
-    np.testing.assert_allclose(a1[1], a2[1])
+    rng = np.random.RandomState(11)
+    with torch.no_grad():
+        for p in ours.parameters():
+            fan_in = p[0].numel() if p.dim() > 1 else p.numel()
+            p.copy_(torch.from_numpy((rng.standard_normal(tuple(p.shape)) / np.sqrt(fan_in)).astype(np.float32)))
+    x = torch.from_numpy(rng.randint(0, 256, (3, 4, 84, 84)).astype(np.float32))
+    return env, ours, x
 
 
-@pytest.mark.skipif(not refimport.available(), reason="reference not mounted")
+def _dueling_outputs(model, x):
+    """In float64 on both sides: the recorded outputs are compared on other machines, whose
+    fp32 convolutions sum in another order (8e-5 on |q| ~ 100 between two CPUs); in fp64 that
+    difference is ~1e-13, far inside assert_close's fp64 tolerance of 1e-7."""
+    model, x = model.double(), x.double()
+    random.seed(0)
+    a = model.act(x[0], 0.3)
+    return {"q": model(x).detach().numpy(), "act_action": np.int64(a[0]), "act_q": np.asarray(a[1])}
+
+
+def test_dueling_forward_matches_reference_model():
+    """The reference's DuelingDQN with this model's state_dict loaded (strict), same input
+    (recorded: tests/golden/models_dueling.npz, with the reference's own state_dict layout)."""
+    g = goldens.load("models_dueling")
+    env, ours, x = _dueling_forward_case()
+    # their checkpoint loads into ours: same keys, order, shapes and dtypes (and ours loaded into
+    # theirs when the outputs below were recorded)
+    sd = {k: v.clone() for k, v in ours.state_dict().items()}
+    assert list(sd) == g["ref_keys"].tolist()
+    assert [list(v.shape) for v in sd.values()] == [s[s >= 0].tolist() for s in g["ref_shapes"]]
+    assert [str(v.dtype) for v in sd.values()] == g["ref_dtypes"].tolist()
+    ours.load_state_dict({k: torch.zeros(tuple(s[s >= 0].tolist()), dtype=getattr(torch, d.split(".")[1]))
+                          for k, s, d in zip(g["ref_keys"].tolist(), g["ref_shapes"], g["ref_dtypes"].tolist())})
+    ours.load_state_dict(sd)
+    o = _dueling_outputs(ours, x)
+    assert o["q"].dtype == g["q"].dtype == np.float64
+    torch.testing.assert_close(torch.from_numpy(o["q"]), torch.from_numpy(g["q"]))
+    assert o["act_action"] == g["act_action"]
+    np.testing.assert_allclose(o["act_q"], g["act_q"])
+
+
+AQL_FORWARD_ENVS = ("CartPole-v0", "BipedalWalker-v3")
+
+
+def _aql_act(model, s):
+    torch.manual_seed(7)
+    np.random.seed(7)
+    random.seed(7)
+    r = model.act(s, 0.0)
+    return {"action": np.asarray(r[0]), "a_mu": np.asarray(r[1]), "q": r[2].detach().numpy()}
+
+
 def test_aql_forward_matches_reference_model():
-    ref = refimport.load("model")
-    for env_id in ("CartPole-v0", "BipedalWalker-v3"):
+    """The reference's AQL (propose 2 + uniform 5) acting on the same state with the same RNG
+    streams; its freshly initialised state_dict is the recorded checkpoint loaded here
+    (tests/golden/models_aql_<env>.npz)."""
+    for env_id in AQL_FORWARD_ENVS:
+        g = goldens.load("models_aql_" + env_id)
         env = make(env_id)
-        torch.manual_seed(0)
-        theirs = ref.AQL(env, propose_sample=2, uniform_sample=5, device="cpu")
         ours = AQL(env, propose_sample=2, uniform_sample=5, device="cpu")
-        ours.load_state_dict(theirs.state_dict())
-        s = env.reset()
-        torch.manual_seed(7)
-        np.random.seed(7)
-        random.seed(7)
-        r1 = theirs.act(s, 0.0)
-        torch.manual_seed(7)
-        np.random.seed(7)
-        random.seed(7)
-        r2 = ours.act(s, 0.0)
-        assert int(r1[0]) == int(r2[0])
-        np.testing.assert_allclose(r1[1], r2[1])
-        torch.testing.assert_close(r1[2], r2[2])
+        ours.load_state_dict(goldens.get_state(g, "state"))
+        r2 = _aql_act(ours, g["s"])
+        assert int(g["action"]) == int(r2["action"])
+        # proposals are fp32 network outputs (+ seeded noise) recorded on another machine: the
+        # fp32 tolerance of the Q comparison below, not NumPy's 1e-7 (one fp32 ulp)
+        np.testing.assert_allclose(g["a_mu"], r2["a_mu"], rtol=1.3e-6, atol=1e-5)
+        torch.testing.assert_close(torch.from_numpy(g["q"]), torch.from_numpy(r2["q"]))
 
 
-@pytest.mark.skipif(not refimport.available(), reason="reference not mounted")
-def test_compute_loss_matches_reference_utils():
-    ref_utils = refimport.load("utils")
-    from apex_amd import utils
-
+def _loss_case():
+    """Models and batch of the loss differential test; the initial weights are recorded in
+    tests/golden/models_loss.npz so both sides start from the same checkpoint."""
     env = make("CartPole-v0")
     torch.manual_seed(0)
     model, tgt = DuelingDQN(env), DuelingDQN(env)
@@ -109,19 +138,38 @@ def test_compute_loss_matches_reference_utils():
     g = torch.Generator().manual_seed(1)
     batch = (torch.randn(B, 4, generator=g), torch.randint(0, 2, (B,), generator=g), torch.randn(B, generator=g),
              torch.randn(B, 4, generator=g), (torch.rand(B, generator=g) < 0.2).float(), torch.rand(B, generator=g))
-    l1, p1 = utils.compute_loss(model, tgt, batch, 3, 0.99)
-    l2, p2 = ref_utils.compute_loss(model, tgt, batch, 3, 0.99)
-    torch.testing.assert_close(l1, l2)
-    np.testing.assert_allclose(p1, p2, rtol=1e-6)
-    opt1 = torch.optim.RMSprop(model.parameters(), 1e-3, alpha=0.95, eps=1.5e-7, centered=True)
-    model2 = DuelingDQN(env)
-    model2.load_state_dict(model.state_dict())
-    opt2 = torch.optim.RMSprop(model2.parameters(), 1e-3, alpha=0.95, eps=1.5e-7, centered=True)
-    n1 = utils.update_parameters(l1, model, opt1, 40)
-    l2b, _ = ref_utils.compute_loss(model2, tgt, batch, 3, 0.99)
-    n2 = ref_utils.update_parameters(l2b, model2, opt2, 40)
-    torch.testing.assert_close(torch.as_tensor(n1), torch.as_tensor(n2))
-    for a, b in zip(model.parameters(), model2.parameters()):
+    # float64 on both sides (see _dueling_outputs): recorded results, compared on other machines
+    batch = tuple(t.double() if t.is_floating_point() else t for t in batch)
+    return env, model.double(), tgt.double(), batch
+
+
+def _loss_and_update(u, model, tgt, batch):
+    """compute_loss + update_parameters of either implementation's utils module ``u``."""
+    opt = torch.optim.RMSprop(model.parameters(), 1e-3, alpha=0.95, eps=1.5e-7, centered=True)
+    loss, prios = u.compute_loss(model, tgt, batch, 3, 0.99)
+    out = {"loss": loss.detach().numpy().copy(), "prios": np.asarray(prios).copy()}
+    out["grad_norm"] = np.asarray(torch.as_tensor(u.update_parameters(loss, model, opt, 40)).detach().numpy())
+    goldens.put_state(out, "after", model.state_dict())
+    return out
+
+
+def test_compute_loss_matches_reference_utils():
+    """The reference's utils.compute_loss / update_parameters on the same models and batch
+    (recorded: tests/golden/models_loss.npz)."""
+    from apex_amd import utils
+
+    g = goldens.load("models_loss")
+    env, model, tgt, batch = _loss_case()
+    model.load_state_dict(goldens.get_state(g, "model"))
+    tgt.load_state_dict(goldens.get_state(g, "target"))
+    assert all(p.dtype == torch.float64 for p in model.parameters())
+    o = _loss_and_update(utils, model, tgt, batch)
+    torch.testing.assert_close(torch.from_numpy(o["loss"]), torch.from_numpy(g["loss"]))
+    np.testing.assert_allclose(o["prios"], g["prios"], rtol=1e-6)
+    torch.testing.assert_close(torch.from_numpy(o["grad_norm"]), torch.from_numpy(g["grad_norm"]))
+    after = goldens.get_state(g, "after")
+    assert list(after) == list(model.state_dict())
+    for a, b in zip(model.state_dict().values(), after.values()):
         torch.testing.assert_close(a, b)
 
 

@@ -4,7 +4,7 @@ import pytest
 
 from apex_amd.replay.nstep import BatchStorage
 
-from . import refimport
+from . import goldens
 
 
 def _drive(bs, rewards, dones, A=3, seed=0):
@@ -41,30 +41,48 @@ def test_textbook_mode():
     assert pr.shape == (5,) and (pr > 0).all()
 
 
-@pytest.mark.skipif(not refimport.available(), reason="reference not mounted")
-def test_reference_mode_matches_reference_batchstorage():
-    ref = refimport.load("memory")
+def _drive_reference_mode(bs, raises_on_lone_done):
+    """400 scripted steps into either implementation's BatchStorage(3, 0.99): every batch it
+    emits (priorities + the five lists) and the steps at which a done arrives on an empty
+    window (Q4: the reference raises IndexError there, this framework emits nothing)."""
     rng = np.random.RandomState(3)
     T, A = 400, 6
     rewards = rng.randn(T)
     dones = rng.rand(T) < 0.06
     dones[0] = False
-    ours, theirs = BatchStorage(3, 0.99), ref.BatchStorage(3, 0.99)
     qs = rng.randn(T, A).astype(np.float32)
+    out, k, lone = {}, 0, []
     for t in range(T):
         args = (rng.randn(2).astype(np.float32), float(rewards[t]), int(t % A), bool(dones[t]), qs[t])
-        if dones[t] and len(theirs.state_deque) == 0:
-            # the reference raises IndexError here (Q4); ours emits nothing
-            with pytest.raises(IndexError):
-                theirs.add(*args)
-            ours.add(*args)
+        if dones[t] and len(bs.state_deque) == 0:
+            lone.append(t)
+            if raises_on_lone_done:
+                with pytest.raises(IndexError):
+                    bs.add(*args)
+            else:
+                bs.add(*args)
             continue
-        ours.add(*args)
-        theirs.add(*args)
-        if len(theirs) >= 50:
-            (b1, p1), (b2, p2) = ours.make_batch(), theirs.make_batch()
-            np.testing.assert_allclose(p1, p2, rtol=1e-12)
-            for x, y in zip(b1, b2):
-                np.testing.assert_array_equal(np.asarray(x), np.asarray(y))
-            ours.reset()
-            theirs.reset()
+        bs.add(*args)
+        if len(bs) >= 50:
+            b, p = bs.make_batch()
+            out[f"prios{k}"] = np.asarray(p)
+            for j, x in enumerate(b):
+                out[f"batch{k}_{j}"] = np.asarray(x)
+            k += 1
+            bs.reset()
+    out["n_batches"] = np.int64(k)
+    out["lone_done_steps"] = np.asarray(lone, dtype=np.int64)
+    return out
+
+
+def test_reference_mode_matches_reference_batchstorage():
+    """Against the reference's BatchStorage(3, 0.99) (recorded: tests/golden/nstep_reference_mode.npz)."""
+    theirs = goldens.load("nstep_reference_mode")
+    ours = _drive_reference_mode(BatchStorage(3, 0.99), raises_on_lone_done=False)
+    n = int(theirs["n_batches"])
+    assert int(ours["n_batches"]) == n and n >= 1
+    np.testing.assert_array_equal(ours["lone_done_steps"], theirs["lone_done_steps"])
+    for k in range(n):
+        np.testing.assert_allclose(ours[f"prios{k}"], theirs[f"prios{k}"], rtol=1e-12)
+        for j in range(5):
+            np.testing.assert_array_equal(ours[f"batch{k}_{j}"], theirs[f"batch{k}_{j}"])

@@ -10,7 +10,7 @@ from apex_amd.memory import (CustomPrioritizedReplayBuffer, CustomPrioritizedRep
                              PrioritizedReplayBuffer, ReplayBuffer)
 from apex_amd.replay.segment_tree import MinSegmentTree, SegmentTree, SumSegmentTree
 
-from . import refimport
+from . import goldens
 
 
 def test_capacity_must_be_pow2():
@@ -68,53 +68,67 @@ def test_uniform_replay_roundtrip():
     assert o.shape == (10, 2) and set(a.tolist()) <= {2, 3, 4}
 
 
-@pytest.mark.skipif(not refimport.available(), reason="reference not mounted")
-@pytest.mark.parametrize("exact", [False])
-def test_per_matches_reference_exactly(exact):
-    ref = refimport.load("memory")
-    ours = PrioritizedReplayBuffer(100, 0.6, exact_mass=exact)
-    theirs = ref.PrioritizedReplayBuffer(100, 0.6)
+def _drive_per(buf):
+    """The scripted add / sample / update sequence of the PER differential test, on either
+    implementation's buffer: every sampled tuple and the final tree totals."""
     rng = np.random.RandomState(0)
+    out, k = {}, 0
     for i in range(150):
         tr = (rng.randn(3).astype(np.float32), i % 4, float(rng.randn()), rng.randn(3).astype(np.float32), i % 9 == 0)
-        ours.add(*tr)
-        theirs.add(*tr)
+        buf.add(*tr)
         if i > 40 and i % 10 == 0:
             random.seed(i)
-            so = ours.sample(16, 0.4)
-            random.seed(i)
-            st_ = theirs.sample(16, 0.4)
-            assert list(so[-1]) == list(st_[-1])
-            np.testing.assert_allclose(so[-2], st_[-2], rtol=0, atol=0)
-            for x, y in zip(so[:5], st_[:5]):
-                np.testing.assert_array_equal(np.asarray(x), np.asarray(y))
+            smp = buf.sample(16, 0.4)
+            for j, x in enumerate(smp):
+                out[f"sample{k}_{j}"] = np.asarray(x)
+            k += 1
             pr = rng.uniform(0.1, 5, 16)
-            ours.update_priorities(so[-1], pr)
-            theirs.update_priorities(st_[-1], pr)
-    assert ours._max_priority == theirs._max_priority
-    assert ours._it_sum.sum() == theirs._it_sum.sum()
-    assert ours._it_min.min() == theirs._it_min.min()
+            buf.update_priorities(smp[-1], pr)
+    out["n_samples"] = np.int64(k)
+    out["max_priority"] = np.float64(buf._max_priority)
+    out["it_sum"] = np.float64(buf._it_sum.sum())
+    out["it_min"] = np.float64(buf._it_min.min())
+    return out
 
 
-@pytest.mark.skipif(not refimport.available(), reason="reference not mounted")
-def test_custom_per_matches_reference():
-    ref = refimport.load("memory")
-    ours = CustomPrioritizedReplayBuffer(64, 0.6)
-    theirs = ref.CustomPrioritizedReplayBuffer(64, 0.6)
+@pytest.mark.parametrize("exact", [False])
+def test_per_matches_reference_exactly(exact):
+    """Against the reference's PrioritizedReplayBuffer(100, 0.6) driven through the same
+    sequence (recorded: tests/golden/replay_per.npz)."""
+    theirs = goldens.load("replay_per")
+    ours = _drive_per(PrioritizedReplayBuffer(100, 0.6, exact_mass=exact))
+    assert int(ours["n_samples"]) == int(theirs["n_samples"]) == 10
+    for k in range(10):
+        assert list(ours[f"sample{k}_6"]) == list(theirs[f"sample{k}_6"])
+        np.testing.assert_allclose(ours[f"sample{k}_5"], theirs[f"sample{k}_5"], rtol=0, atol=0)
+        for j in range(5):
+            np.testing.assert_array_equal(ours[f"sample{k}_{j}"], theirs[f"sample{k}_{j}"])
+    assert ours["max_priority"] == theirs["max_priority"]
+    assert ours["it_sum"] == theirs["it_sum"]
+    assert ours["it_min"] == theirs["it_min"]
+
+
+def _drive_custom_per(buf):
     rng = np.random.RandomState(1)
     for i in range(100):
         tr = (rng.randint(0, 255, (4, 2, 2)).astype(np.uint8), i % 6, float(rng.randn()),
               rng.randint(0, 255, (4, 2, 2)).astype(np.uint8), np.float32(i % 7 == 0), float(rng.uniform(0.01, 3)))
-        ours.add(*tr)
-        theirs.add(*tr)
+        buf.add(*tr)
     random.seed(5)
-    a = ours.sample(32, 0.4)
-    random.seed(5)
-    b = theirs.sample(32, 0.4)
+    return buf.sample(32, 0.4)
+
+
+def test_custom_per_matches_reference():
+    """Against the reference's CustomPrioritizedReplayBuffer(64, 0.6) (recorded:
+    tests/golden/replay_custom_per.npz)."""
+    b = goldens.load("replay_custom_per")
+    a = _drive_custom_per(CustomPrioritizedReplayBuffer(64, 0.6))
     assert isinstance(a[0], list) and isinstance(a[3], list)
-    assert a[-1] == b[-1]
-    np.testing.assert_array_equal(a[-2], b[-2])
-    for x, y in zip(a[0], b[0]):
+    assert bool(b["obs_is_list"]) and bool(b["next_obs_is_list"])
+    assert a[-1] == b["idxes"].tolist()
+    np.testing.assert_array_equal(a[-2], b["weights"])
+    assert len(a[0]) == len(b["obs"])
+    for x, y in zip(a[0], b["obs"]):
         np.testing.assert_array_equal(x, y)
 
 

@@ -85,23 +85,37 @@ def test_checkpoint_reference_format_and_sidecar(tmp_path):
     assert torch.equal(opt2.state_dict()["state"][0]["square_avg"], opt.state_dict()["state"][0]["square_avg"])
 
 
-def test_checkpoint_loads_into_reference_model(tmp_path):
-    from tests import refimport
-
-    if not refimport.available():
-        pytest.skip("reference not present")
+def _checkpoint_case():
     from apex_amd import envs
     from apex_amd.models.dqn import DuelingDQN
+
+    env = envs.make("CartPole-v0")
+    torch.manual_seed(21)
+    mine = DuelingDQN(env)
+    x = torch.rand(5, 4, generator=torch.Generator().manual_seed(22))
+    return env, mine, x
+
+
+def test_checkpoint_loads_into_reference_model(tmp_path):
+    """The reference's DuelingDQN loaded the checkpoint ``save_model`` wrote for these seeded
+    weights (strict load_state_dict) and its forward was recorded, with the checkpoint's
+    tensors (tests/golden/trainers_checkpoint.npz): the file written here must hold exactly
+    those tensors under those keys, and this model's forward must match the recorded one."""
+    from tests import goldens
+
     from apex_amd.utils.checkpoint import save_model
 
-    ref = refimport.load("model")
-    env = envs.make("CartPole-v0")
-    mine = DuelingDQN(env)
+    g = goldens.load("trainers_checkpoint")
+    env, mine, x = _checkpoint_case()
+    mine.load_state_dict(goldens.get_state(g, "checkpoint"))  # the recorded weights, whatever the init stream
     path = save_model(mine, str(tmp_path / "model0.pth"))
-    theirs = ref.DuelingDQN(env)
-    theirs.load_state_dict(torch.load(path, map_location="cpu", weights_only=True))
-    x = torch.rand(5, 4)
-    torch.testing.assert_close(theirs(x), mine(x))
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    loaded = goldens.get_state(g, "checkpoint")   # what the reference model loaded
+    assert list(sd) == list(loaded)
+    for k in sd:
+        assert sd[k].dtype == loaded[k].dtype and torch.equal(sd[k], loaded[k]), k
+    # forwards in float64: the recorded one comes from another machine (fp32 summation order)
+    torch.testing.assert_close(torch.from_numpy(g["ref_forward"]), mine.double()(x.double()))
 
 
 # ------------------------------------------------------------------ shared params
