@@ -187,6 +187,7 @@ __global__ void vec_env_step_k(float* state, const int* __restrict__ actions, ui
     const float r = p.clip_rewards ? (r_raw > 0.f ? 1.f : (r_raw < 0.f ? -1.f : 0.f)) : r_raw;
     st[S_EPRET] += r;
     st[S_EPLEN] += 1.f;
+    // S_EPLEN counts agent steps since the last agent-level done: with episode_life, per life
     const bool time_up = p.max_episode_steps > 0 && st[S_EPLEN] >= (float)p.max_episode_steps;
     const bool agent_done = game_over || time_up || (p.episode_life && life_lost);
     reward[e] = r;
@@ -335,12 +336,30 @@ __device__ __forceinline__ void nstep_one(const NStepParams& p, const NStepState
       st.win_r[e * n + pos] = rt;
       for (int a = 0; a < A; ++a) st.win_q[((size_t)e * n + pos) * A + a] = qt[a];
     }
+    // The drain queue is a ring of n rows (dmeta = head, count).  Every step adds one (s,a)
+    // and emits at most one row, and emits nothing only while count == 0 and len < n, so
+    // len + count <= n always holds: the n entries hold a flushed window behind the rows an
+    // earlier episode still has pending (appended, not overwritten), and nothing is dropped.
     int* dmeta = st.drain_meta + e * 2;
+    int dhead = dmeta[0], dcnt = dmeta[1];
+    if (!emitted && dcnt > 0) {  // the oldest pending row goes first
+      for (int c = 0; c < 4; ++c) {
+        tt.s_ids[row * 4 + c] = st.drain_ids[(e * n + dhead) * 4 + c];
+        tt.s2_ids[row * 4 + c] = st.drain_s2[e * 4 + c];
+      }
+      tt.action[row] = st.drain_a[e * n + dhead];
+      tt.reward[row] = st.drain_r[e * n + dhead];
+      tt.done[row] = 1.f;
+      prio = st.drain_q[e * n + dhead];
+      emitted = true;
+      dhead = (dhead + 1) % n;
+      --dcnt;
+    }
     if (dt) {
       // flush the window as terminal transitions: one now (if the slot is free), the
-      // rest through the drain queue, one per following step.  A pending older drain is
-      // dropped (only possible for episodes shorter than n-1 steps).
-      int dl = 0;
+      // rest appended to the drain queue, one emitted per following step.  drain_s2 stays
+      // one row per env: every drained row has done = 1, so its next state is never
+      // bootstrapped from and rows of an older episode may take the newer one's.
       for (int j = 0; j < len; ++j) {
         float R = 0.f, g = 1.f;
         for (int i = j; i < len; ++i) { R += g * st.win_r[e * n + (start + i) % n]; g *= p.gamma; }
@@ -351,33 +370,21 @@ __device__ __forceinline__ void nstep_one(const NStepParams& p, const NStepState
           write_trans(st.win_ids + (e * n + k) * 4, a0, R, 1.f);
           prio = pr;
           emitted = true;
-        } else {
+        } else if (dcnt < n) {  // always true (see above); keeps the ring in bounds regardless
+          const int dl = (dhead + dcnt) % n;
           for (int c = 0; c < 4; ++c) st.drain_ids[(e * n + dl) * 4 + c] = st.win_ids[(e * n + k) * 4 + c];
           st.drain_a[e * n + dl] = a0;
           st.drain_r[e * n + dl] = R;
           st.drain_q[e * n + dl] = pr;
-          ++dl;
+          ++dcnt;
         }
       }
       for (int c = 0; c < 4; ++c) st.drain_s2[e * 4 + c] = hist[c];
-      dmeta[0] = 0;
-      dmeta[1] = dl;
       len = 0;
       start = 0;
-    } else if (!emitted && dmeta[1] > 0) {
-      const int k = dmeta[0];
-      for (int c = 0; c < 4; ++c) {
-        tt.s_ids[row * 4 + c] = st.drain_ids[(e * n + k) * 4 + c];
-        tt.s2_ids[row * 4 + c] = st.drain_s2[e * 4 + c];
-      }
-      tt.action[row] = st.drain_a[e * n + k];
-      tt.reward[row] = st.drain_r[e * n + k];
-      tt.done[row] = 1.f;
-      prio = st.drain_q[e * n + k];
-      emitted = true;
-      dmeta[0] = k + 1;
-      dmeta[1] -= 1;
     }
+    dmeta[0] = dhead;
+    dmeta[1] = dcnt;
     qstart = start;
     qlen = len;
   }
