@@ -49,6 +49,7 @@ HIP_SOURCES = [
     "loss_heads_kernels.hip",
     "f32_kernels.hip",
     "ipc_kernels.hip",
+    "vector_kernels.hip",
     "comm.cpp",
     "ipc.cpp",
 ]

@@ -914,4 +914,78 @@ PYBIND11_MODULE(_apex_hip, m) {
     aql_select(P<const float>(q), P<const float>(a_mu), B, T, adim, P<const float>(eps), seed,
                P<const int64_t>(counter), P<int>(act_idx), P<float>(env_act), S(s));
   });
+
+  // ---- vector-observation Ape-X (vector_kernels.hip)
+  py::class_<VecNet>(m, "VecNet");
+  // d: the ten parameter pointers by state_dict key + obs + A
+  m.def("make_vec_net", [](py::dict d) {
+    auto g = [&](const char* k) { return P<const float>(d[k].cast<uint64_t>()); };
+    VecNet n{};
+    n.w0 = g("features.0.weight"); n.b0 = g("features.0.bias");
+    n.wa1 = g("advantage.0.weight"); n.ba1 = g("advantage.0.bias");
+    n.wa2 = g("advantage.2.weight"); n.ba2 = g("advantage.2.bias");
+    n.wv1 = g("value.0.weight"); n.bv1 = g("value.0.bias");
+    n.wv2 = g("value.2.weight"); n.bv2 = g("value.2.bias");
+    n.obs = d["obs"].cast<int>(); n.A = d["A"].cast<int>();
+    return n;
+  });
+  py::class_<VecEnv>(m, "VecEnv");
+  m.def("make_vec_env", [](int kind, int E, int obs, int F, int max_steps, uint64_t state, uint64_t ring,
+                           uint64_t seed) {
+    return VecEnv{kind, E, obs, F, max_steps, P<float>(state), P<float>(ring), seed};
+  }, py::arg("kind"), py::arg("E"), py::arg("obs"), py::arg("F"), py::arg("max_steps"), py::arg("state"),
+     py::arg("ring"), py::arg("seed"));
+  m.def("vec_env_state_layout", []() {
+    py::dict d;
+    d["EPRET"] = vecs::EPRET; d["EPLEN"] = vecs::EPLEN; d["LAST"] = vecs::LAST; d["STRIDE"] = vecs::STRIDE;
+    return d;
+  });
+  m.def("vec_classic_reset", [](const VecEnv& V, uint64_t step, uint64_t new_frame, uint64_t hist, uint64_t ep_log,
+                                uint64_t s) {
+    vec_classic_reset(V, P<const int64_t>(step), P<int>(new_frame), P<int>(hist), P<float>(ep_log), S(s));
+  });
+  m.def("vec_classic_step", [](const VecEnv& V, uint64_t actions, uint64_t step, uint64_t reward, uint64_t done,
+                               uint64_t new_frame, uint64_t ep_log, uint64_t s) {
+    vec_classic_step(V, P<const int>(actions), P<const int64_t>(step), P<float>(reward), P<float>(done),
+                     P<int>(new_frame), P<float>(ep_log), S(s));
+  });
+  py::class_<VecAct>(m, "VecAct");
+  m.def("make_vec_act", [](const VecNet& net, uint64_t ring, uint64_t hist, int E, uint64_t eps, uint64_t seed,
+                           uint64_t counter, uint64_t q, uint64_t actions) {
+    return VecAct{net, P<const float>(ring), P<const int>(hist), E, P<const float>(eps), seed,
+                  P<const int64_t>(counter), P<float>(q), P<int>(actions)};
+  });
+  m.def("vec_act", [](const VecAct& a, uint64_t s) { vec_act(a, S(s)); });
+  py::class_<VecLearn>(m, "VecLearn");
+  m.def("make_vec_learn", [](const VecNet& on, const VecNet& tg, py::dict d) {
+    auto g = [&](const char* k) { return d[k].cast<uint64_t>(); };
+    auto opt = [&](const char* k) { return d.contains(k) ? d[k].cast<uint64_t>() : (uint64_t)0; };
+    VecLearn p{};
+    p.on = on; p.tg = tg;
+    p.ring = P<const float>(g("ring"));
+    p.s_ids = P<const int>(g("s_ids")); p.s2_ids = P<const int>(g("s2_ids")); p.act = P<const int>(g("action"));
+    p.rew = P<const float>(g("reward")); p.done = P<const float>(g("done"));
+    p.idx = P<const int>(g("idx")); p.w = P<const float>(g("w"));
+    p.B = d["B"].cast<int>(); p.gamma_n = d["gamma_n"].cast<float>();
+    p.q_s = P<float>(g("q_s")); p.q_s2 = P<float>(g("q_s2")); p.qt_s2 = P<float>(g("qt_s2"));
+    p.vec = P<float>(g("vec")); p.delta = P<float>(g("delta")); p.lw = P<float>(g("lw"));
+    p.step = P<const int64_t>(opt("step")); p.beta_out = P<float>(opt("beta_out"));
+    p.beta0 = d.contains("beta0") ? d["beta0"].cast<double>() : 0.4;
+    p.beta_horizon = d.contains("beta_horizon") ? d["beta_horizon"].cast<double>() : 1000.0;
+    return p;
+  });
+  m.def("vec_learn", [](const VecLearn& p, uint64_t s) { vec_learn(p, S(s)); });
+  m.def("vec_layout", []() {
+    py::dict d;
+    d["X"] = vecv::X; d["F"] = vecv::F; d["DF"] = vecv::DF; d["H"] = vecv::H; d["DH"] = vecv::DH;
+    d["DA"] = vecv::DA; d["STRIDE"] = vecv::STRIDE;
+    return d;
+  });
+  py::class_<VecGrad>(m, "VecGrad");
+  m.def("make_vec_grad", [](uint64_t vec, int B, int obs, int A, int64_t n, uint64_t grad, uint64_t part) {
+    return VecGrad{P<const float>(vec), B, obs, A, n, P<float>(grad), P<double>(part)};
+  });
+  m.def("vec_param_count", &vec_param_count);
+  m.def("vec_grad_blocks", &vec_grad_blocks);
+  m.def("vec_grad", [](const VecGrad& g, uint64_t s) { vec_grad(g, S(s)); });
 }

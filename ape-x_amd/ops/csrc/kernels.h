@@ -650,6 +650,84 @@ void aql_act_tail(const AqlTail& a, hipStream_t s);
 // rows 0..E-1 of the staging tables ``src`` -> ring slots (dst.filled + e) % dst.C (slot list in dst.slots)
 void aql_apply_staged(const AqlInsert& src, const AqlInsert& dst, int E, int obs, int TA, hipStream_t s);
 
+// ---- vector_kernels.hip (vector-observation Ape-X: classic-control envs, MLP dueling DQN)
+constexpr int kVecHidden = 128, kVecMaxObs = 8, kVecMaxA = 7;
+// the ten tensors of DuelingDQN.parameters() (MLP form), reference layouts
+struct VecNet {
+  const float *w0, *b0;      // features.0   [128][obs], [128]
+  const float *wa1, *ba1;    // advantage.0  [128][128], [128]
+  const float *wa2, *ba2;    // advantage.2  [A][128], [A]
+  const float *wv1, *bv1;    // value.0      [128][128], [128]
+  const float *wv2, *bv2;    // value.2      [1][128], [1]
+  int obs, A;
+};
+// per-env state row (floats): the physical state, the episode's running return / length and
+// the last step's own next observation (what the ring row holds unless the episode ended)
+namespace vecs {
+constexpr int EPRET = 4, EPLEN = 5, LAST = 8, STRIDE = 16;
+}
+struct VecEnv {
+  int kind;          // 0 CartPole, 1 MountainCar
+  int E, obs, F;     // envs, observation floats, frame-ring rows (of 4 * obs bytes)
+  int max_steps;     // registered TimeLimit (ends the episode with done = 1)
+  float* state;      // [E][vecs::STRIDE]
+  float* ring;       // the replay's frame ring viewed as [F][obs] fp32
+  uint64_t seed;
+};
+// frame-ring convention of vec_env_step_k: the step at counter t writes env e's new observation
+// to row ((t + 1) E + e) mod F, a reset at counter t to (t E + e) mod F; after an episode end the
+// row holds the reset observation
+void vec_classic_reset(const VecEnv& V, const int64_t* step_counter, int* new_frame, int* hist, float* ep_log,
+                       hipStream_t s);
+void vec_classic_step(const VecEnv& V, const int* actions, const int64_t* step_counter, float* reward, float* done,
+                      int* new_frame, float* ep_log, hipStream_t s);
+// Q[E][A] of the observations at ring row hist[e][3] + select_actions_k's epsilon-greedy draw
+struct VecAct {
+  VecNet net;
+  const float* ring;
+  const int* hist;         // [E][4]
+  int E;
+  const float* eps;        // [E]
+  uint64_t seed;
+  const int64_t* counter;  // the shard's step counter
+  float* q;                // [E][A]
+  int* actions;            // [E]
+};
+void vec_act(const VecAct& a, hipStream_t s);
+// Per-sample backward vectors written by vec_learn and contracted over the batch by vec_grad
+// (offsets in floats): input, features, their gradient, both hidden layers, their gradient,
+// dL/dA[0..A) with dL/dV at DA + 7.
+namespace vecv {
+constexpr int X = 0, F = 8, DF = 136, H = 264, DH = 520, DA = 776, STRIDE = 784;
+}
+struct VecLearn {
+  VecNet on, tg;
+  const float* ring;
+  const int *s_ids, *s2_ids, *act;   // replay tables, read through idx (observation = frame id [3])
+  const float *rew, *done;
+  const int* idx;                    // [B] sampled slots
+  const float* w;                    // [B] IS weights
+  int B;
+  float gamma_n;
+  float *q_s, *q_s2, *qt_s2;         // [B][A] Q(s), Q(s'), Q_target(s')
+  float* vec;                        // [B][vecv::STRIDE]
+  float *delta, *lw;                 // [B] |y - Q(s,a)|, w * Huber
+  const int64_t* step;               // learner step counter (read)
+  float* beta_out;                   // optional: beta_by_frame(step + 1, beta0, horizon) for the next draw
+  double beta0, beta_horizon;
+};
+void vec_learn(const VecLearn& p, hipStream_t s);
+struct VecGrad {
+  const float* vec;
+  int B, obs, A;
+  int64_t n;       // vec_param_count(obs, A)
+  float* grad;     // flat gradient, DuelingDQN.parameters() order
+  double* part;    // [vec_grad_blocks(n)] fp64 sum(g^2) partials (rmsprop_step's norm input)
+};
+int64_t vec_param_count(int obs, int A);
+int vec_grad_blocks(int64_t n);
+void vec_grad(const VecGrad& g, hipStream_t s);
+
 // ---- central-replay experience transport over HIP IPC (ipc_kernels.hip, parallel/ipc.py)
 struct IpcIngest {
   int kind;                         // 0: Ape-X DQN packets (frames + rows into per-link regions)

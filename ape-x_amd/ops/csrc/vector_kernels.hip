@@ -1,0 +1,500 @@
+// Vector-observation Ape-X kernels for gfx950: classic-control envs that write their
+// observations into the HBM frame ring, the acting forward of the MLP dueling net with the
+// epsilon-greedy draw, and the learner's fused forward x3 / loss / backward (reference
+// ApeX.py, DQN.py with model.py's MLP DuelingDQN: features.0 = Linear(obs, 128), two
+// 128-hidden heads).
+//
+// A vector observation is a "frame" of 4 * obs bytes in the replay's frame ring, so the n-step
+// batcher, the PER tree, the priority mix, the grad norm and the optimizer are the existing
+// kernels, unchanged.  Everything is fp32 FMA: the net is ~34k MAC per sample, the work is
+// latency-bound, and the design goal is few launches and no host sync.
+//
+//   vec_classic_reset / vec_classic_step  one thread per env (CartPole, MountainCar dynamics of
+//                                         envs/classic.py in fp32)
+//   vec_act      one workgroup per 8 envs: both heads' 128x128 weights staged (transposed) in LDS,
+//                Q[E, A], then select_actions_k's draw in the same launch
+//   vec_learn    one workgroup per 4 sampled rows: target net on (s, s'), online net on (s, s'),
+//                double-DQN n-step Huber loss, backward to per-sample vectors (aql_learn_bwd's
+//                shape); block 0 also writes the next step's PER beta
+//   vec_grad     batch contraction of the per-sample vectors into the flat gradient, one element
+//                per thread, summed in batch order (no atomics: deterministic) + one fp64
+//                sum-of-squares partial per workgroup in grad_sumsq's format
+#include "common.h"
+#include "kernels.h"
+
+namespace apex {
+
+namespace {
+
+constexpr int kH = kVecHidden;          // 128
+constexpr int kRows = 8;                // rows per forward pass of a workgroup
+constexpr int kWPitch = kH + 1;         // transposed weight image [k][j], padded: conflict-free both ways
+constexpr int kWHead = kH * kWPitch;    // floats per head image
+constexpr int kThreads = 256;
+
+// ------------------------------------------------------------------ envs
+__device__ __forceinline__ void classic_reset_obs(const VecEnv& V, int e, uint64_t ctr, float* st) {
+  float u[4];
+  uniform4(V.seed, (uint64_t)e, ctr, u);
+  if (V.kind == 0) {  // CartPole: U(-0.05, 0.05)^4
+#pragma unroll
+    for (int k = 0; k < 4; ++k) st[k] = -0.05f + 0.1f * u[k];
+  } else {            // MountainCar: position U(-0.6, -0.4), velocity 0
+    st[0] = -0.6f + 0.2f * u[0];
+    st[1] = 0.f;
+    st[2] = 0.f;
+    st[3] = 0.f;
+  }
+}
+
+__global__ void vec_classic_reset_k(VecEnv V, const int64_t* step_counter, int* new_frame, int* hist,
+                                    float* ep_log) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= V.E) return;
+  const int64_t step = step_counter ? step_counter[0] : 0;
+  const int slot = (int)(((int64_t)step * V.E + e) % V.F);
+  float* gst = V.state + (size_t)e * vecs::STRIDE;
+  float st[4];
+  classic_reset_obs(V, e, (uint64_t)step * 16 + 1, st);
+  for (int k = 0; k < vecs::STRIDE; ++k) gst[k] = k < 4 ? st[k] : 0.f;
+  for (int k = 0; k < V.obs; ++k) V.ring[(size_t)slot * V.obs + k] = st[k];
+  new_frame[e] = slot;
+  if (hist) for (int c = 0; c < 4; ++c) hist[e * 4 + c] = slot;
+  if (ep_log) for (int c = 0; c < 4; ++c) ep_log[e * 4 + c] = 0.f;
+}
+
+__global__ void vec_classic_step_k(VecEnv V, const int* __restrict__ actions, const int64_t* step_counter,
+                                   float* reward, float* done, int* new_frame, float* ep_log) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= V.E) return;
+  const int64_t step = step_counter ? step_counter[0] : 0;
+  const int slot = (int)(((int64_t)(step + 1) * V.E + e) % V.F);
+  float* gst = V.state + (size_t)e * vecs::STRIDE;
+  const int a = actions[e];
+  float nv[4] = {0.f, 0.f, 0.f, 0.f};
+  float r;
+  bool term;
+  if (V.kind == 0) {  // CartPole (Barto et al. 1983; envs/classic.py CartPoleEnv, as aql_env_step)
+    const float x = gst[0], xd = gst[1], th = gst[2], thd = gst[3];
+    const float force = (a == 1) ? 10.f : -10.f;
+    const float ct = cosf(th), sn = sinf(th);
+    const float tmp = (force + 0.05f * thd * thd * sn) / 1.1f;
+    const float tha = (9.8f * sn - ct * tmp) / (0.5f * (4.f / 3.f - 0.1f * ct * ct / 1.1f));
+    const float xa = tmp - 0.05f * tha * ct / 1.1f;
+    nv[0] = x + 0.02f * xd;
+    nv[1] = xd + 0.02f * xa;
+    nv[2] = th + 0.02f * thd;
+    nv[3] = thd + 0.02f * tha;
+    r = 1.f;
+    term = nv[0] < -2.4f || nv[0] > 2.4f || nv[2] < -0.20943951f || nv[2] > 0.20943951f;
+  } else {            // MountainCar (Moore 1990; envs/classic.py MountainCarEnv)
+    float pos = gst[0], v = gst[1];
+    v += (float)(a - 1) * 0.001f + cosf(3.f * pos) * (-0.0025f);
+    v = fminf(fmaxf(v, -0.07f), 0.07f);
+    pos += v;
+    pos = fminf(fmaxf(pos, -1.2f), 0.6f);
+    if (pos == -1.2f && v < 0.f) v = 0.f;  // inelastic left wall
+    nv[0] = pos;
+    nv[1] = v;
+    r = -1.f;
+    term = pos >= 0.5f;
+  }
+  const float ep_ret = gst[vecs::EPRET] + r;
+  const float ep_len = gst[vecs::EPLEN] + 1.f;
+  const bool time_up = V.max_steps > 0 && ep_len >= (float)V.max_steps;  // TimeLimit ends with done = 1
+  const bool d = term || time_up;
+  reward[e] = r;
+  done[e] = d ? 1.f : 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) gst[vecs::LAST + k] = nv[k];  // the step's own s' (before a reset)
+  if (d) {
+    if (ep_log) {
+      ep_log[e * 4 + 0] = ep_ret;
+      ep_log[e * 4 + 1] = ep_len;
+      ep_log[e * 4 + 2] += 1.f;
+    }
+    classic_reset_obs(V, e, (uint64_t)step * 16 + 7, nv);
+    gst[vecs::EPRET] = 0.f;
+    gst[vecs::EPLEN] = 0.f;
+  } else {
+    gst[vecs::EPRET] = ep_ret;
+    gst[vecs::EPLEN] = ep_len;
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) gst[k] = nv[k];
+  for (int k = 0; k < V.obs; ++k) V.ring[(size_t)slot * V.obs + k] = nv[k];
+  new_frame[e] = slot;
+}
+
+// ------------------------------------------------------------------ MLP dueling forward
+// LDS of a forward workgroup: both heads' first layers, transposed ([k][j], pitch 129), and the
+// activations of kRows rows.
+struct alignas(16) FwdLds {
+  float W[2 * kWHead];          // advantage.0 | value.0
+  float x[kRows * kVecMaxObs];
+  float f[kRows * kH];          // relu(features.0)
+  float h[kRows * 2 * kH];      // relu(advantage.0) | relu(value.0)
+  float q[kRows * 8];
+};
+
+// 128 elements per thread in rounds of 32 loads issued before their LDS stores: the copy pays the
+// global latency 4 times, not once per element (8 loads in flight: 16 rounds, 2/3 of the kernel)
+__device__ __forceinline__ void stage_heads(const VecNet& n, float* W) {
+  constexpr int kPer = 2 * kH * kH / kThreads, kInFlight = 32;
+  static_assert(kPer % kInFlight == 0 && (kH * kH) % (kThreads * kInFlight) == 0, "a round stays within one head");
+#pragma unroll
+  for (int c0 = 0; c0 < kPer; c0 += kInFlight) {
+    const int head = (c0 * kThreads) >> 14;  // compile-time per round
+    const float* src = head ? n.wv1 : n.wa1;
+    float v[kInFlight];
+#pragma unroll
+    for (int u = 0; u < kInFlight; ++u) v[u] = src[((c0 + u) * kThreads + threadIdx.x) & (kH * kH - 1)];
+#pragma unroll
+    for (int u = 0; u < kInFlight; ++u) {
+      const int li = ((c0 + u) * kThreads + threadIdx.x) & (kH * kH - 1);
+      W[head * kWHead + (li & (kH - 1)) * kWPitch + (li >> 7)] = v[u];
+    }
+  }
+}
+
+// Q of the kRows rows in L.x (weights of `n` already staged in L.W) -> L.f, L.h, L.q.
+// Begins and ends with a workgroup barrier.
+__device__ void vec_forward(const VecNet& n, FwdLds& L) {
+  const int t = threadIdx.x, j = t & (kH - 1), head = t >> 7;
+  __syncthreads();
+  {  // features.0: thread = (unit j, 4 rows)
+    const int r0 = head * 4;
+    float w[kVecMaxObs];
+#pragma unroll
+    for (int k = 0; k < kVecMaxObs; ++k) w[k] = k < n.obs ? n.w0[j * n.obs + k] : 0.f;
+    const float b = n.b0[j];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float acc = b;
+#pragma unroll
+      for (int k = 0; k < kVecMaxObs; ++k) acc = fmaf(w[k], L.x[(r0 + r) * kVecMaxObs + k], acc);
+      L.f[(r0 + r) * kH + j] = fmaxf(acc, 0.f);
+    }
+  }
+  __syncthreads();
+  {  // advantage.0 / value.0: thread = (head, unit j), all rows
+    float acc[kRows];
+    const float b = (head ? n.bv1 : n.ba1)[j];
+#pragma unroll
+    for (int r = 0; r < kRows; ++r) acc[r] = b;
+    const float* Wh = L.W + head * kWHead + j;
+    for (int k = 0; k < kH; k += 4) {
+      const float w0 = Wh[(k + 0) * kWPitch], w1 = Wh[(k + 1) * kWPitch], w2 = Wh[(k + 2) * kWPitch],
+                  w3 = Wh[(k + 3) * kWPitch];
+#pragma unroll
+      for (int r = 0; r < kRows; ++r) {
+        const float4 fv = *reinterpret_cast<const float4*>(&L.f[r * kH + k]);
+        acc[r] = fmaf(w0, fv.x, acc[r]);
+        acc[r] = fmaf(w1, fv.y, acc[r]);
+        acc[r] = fmaf(w2, fv.z, acc[r]);
+        acc[r] = fmaf(w3, fv.w, acc[r]);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < kRows; ++r) L.h[r * 2 * kH + t] = fmaxf(acc[r], 0.f);
+  }
+  __syncthreads();
+  {  // advantage.2 / value.2 and the dueling combine: a wave per row pair
+    const int lane = t & 63, wave = t >> 6;
+    for (int r = wave; r < kRows; r += 4) {
+      const float* hr = L.h + r * 2 * kH;
+      float advsum = 0.f, val = 0.f;
+      for (int o = 0; o <= n.A; ++o) {
+        const float* wo = o < n.A ? n.wa2 + o * kH : n.wv2;
+        const float* hb = o < n.A ? hr : hr + kH;
+        float p = fmaf(wo[lane], hb[lane], wo[lane + 64] * hb[lane + 64]);
+        p = wave_sum(p);
+        if (o < n.A) {
+          p += n.ba2[o];
+          advsum += p;
+          if (lane == 0) L.q[r * 8 + o] = p;
+        } else {
+          val = p + n.bv2[0];
+        }
+      }
+      if (lane == 0) {
+        const float mean = advsum / (float)n.A;
+        for (int o = 0; o < n.A; ++o) L.q[r * 8 + o] = val + L.q[r * 8 + o] - mean;
+      }
+    }
+  }
+  __syncthreads();
+}
+
+// ------------------------------------------------------------------ acting
+__global__ __launch_bounds__(kThreads) void vec_act_k(VecAct a) {
+  __shared__ FwdLds L;
+  const int t = threadIdx.x;
+  const int e0 = blockIdx.x * kRows;
+  if (t < kRows * kVecMaxObs) {
+    const int r = t / kVecMaxObs, k = t % kVecMaxObs;
+    const int e = min(e0 + r, a.E - 1);  // rows past E repeat the last env (never written)
+    L.x[t] = k < a.net.obs ? a.ring[(size_t)a.hist[e * 4 + 3] * a.net.obs + k] : 0.f;
+  }
+  stage_heads(a.net, L.W);
+  vec_forward(a.net, L);
+  const int e = e0 + t;
+  if (t < kRows && e < a.E) {
+    const int A = a.net.A;
+    const float* row = L.q + t * 8;
+    // select_actions_k's draw: first argmax; explore iff !(u0 > eps); min(int(u1 A), A - 1)
+    int best = 0;
+    float bv = row[0];
+    for (int k = 1; k < A; ++k)
+      if (row[k] > bv) { bv = row[k]; best = k; }
+    for (int k = 0; k < A; ++k) a.q[(size_t)e * A + k] = row[k];
+    float u[4];
+    uniform4(a.seed, (uint64_t)e, a.counter ? (uint64_t)a.counter[0] : 0ull, u);
+    if (!(u[0] > a.eps[e])) {
+      const int r = (int)(u[1] * (float)A);
+      best = r < A ? r : A - 1;
+    }
+    a.actions[e] = best;
+  }
+}
+
+// ------------------------------------------------------------------ learner
+constexpr int kSamples = kRows / 2;  // sampled rows per workgroup: rows 0..3 = s, 4..7 = s'
+
+__global__ __launch_bounds__(kThreads) void vec_learn_k(VecLearn p) {
+  __shared__ FwdLds L;
+  __shared__ float qt[kRows * 8];
+  __shared__ __align__(16) float dh[kSamples * 2 * kH];
+  __shared__ float dfp[2 * kSamples * kH];
+  __shared__ float sg[kSamples];
+  __shared__ int sa[kSamples];
+  const int t = threadIdx.x, j = t & (kH - 1), head = t >> 7;
+  const int b0 = blockIdx.x * kSamples;
+  const int obs = p.on.obs, A = p.on.A;
+  if (blockIdx.x == 0 && t == 0 && p.beta_out) {
+    // PER beta of the NEXT step (this step's draw has run): beta_by_frame(step + 1)
+    const double st = (double)(p.step ? p.step[0] : 0) + 1.0;
+    p.beta_out[0] = (float)fmin(1.0, p.beta0 + st * (1.0 - p.beta0) / p.beta_horizon);
+  }
+  if (t < kRows * kVecMaxObs) {
+    const int r = t / kVecMaxObs, k = t % kVecMaxObs;
+    const int b = min(b0 + (r & (kSamples - 1)), p.B - 1);
+    const int row = p.idx[b];
+    const int id = (r < kSamples ? p.s_ids : p.s2_ids)[row * 4 + 3];
+    L.x[t] = k < obs ? p.ring[(size_t)id * obs + k] : 0.f;
+  }
+  // target net first, so the online heads stay in LDS for the backward
+  stage_heads(p.tg, L.W);
+  vec_forward(p.tg, L);
+  if (t < kRows * 8) qt[t] = L.q[t];
+  __syncthreads();
+  stage_heads(p.on, L.W);
+  vec_forward(p.on, L);
+  if (t < kSamples) {
+    const int b = b0 + t;
+    float g = 0.f;
+    int a = 0;
+    if (b < p.B) {
+      const int row = p.idx[b];
+      a = min(max(p.act[row], 0), A - 1);
+      const float* q2 = L.q + (kSamples + t) * 8;
+      int astar = 0;
+      float best = q2[0];
+      for (int k = 1; k < A; ++k)
+        if (q2[k] > best) { best = q2[k]; astar = k; }
+      // the arithmetic of dqn_loss_k
+      const float y = p.rew[row] + p.gamma_n * qt[(kSamples + t) * 8 + astar] * (1.f - p.done[row]);
+      const float qa = L.q[t * 8 + a];
+      const float delta = fabsf(y - qa);
+      const float hub = delta < 1.f ? 0.5f * delta * delta : delta - 0.5f;
+      p.delta[b] = delta;
+      p.lw[b] = p.w[b] * hub;
+      g = p.w[b] / (float)p.B * fminf(fmaxf(qa - y, -1.f), 1.f);
+      for (int k = 0; k < A; ++k) {
+        p.q_s[(size_t)b * A + k] = L.q[t * 8 + k];
+        p.q_s2[(size_t)b * A + k] = q2[k];
+        p.qt_s2[(size_t)b * A + k] = qt[(kSamples + t) * 8 + k];
+      }
+      // Q = V + A_a - mean(A): dV = g, dA_k = g (1[k == a] - 1/A)
+      float* v = p.vec + (size_t)b * vecv::STRIDE;
+      for (int k = 0; k < 8; ++k) v[vecv::DA + k] = k < A ? g * ((k == a ? 1.f : 0.f) - 1.f / (float)A) : 0.f;
+      v[vecv::DA + 7] = g;
+    }
+    sg[t] = g;
+    sa[t] = a;
+  }
+  __syncthreads();
+  {  // d(hidden pre-activation): thread = (head, unit j)
+    float wa[kVecMaxA];
+#pragma unroll
+    for (int k = 0; k < kVecMaxA; ++k) wa[k] = (head == 0 && k < A) ? p.on.wa2[k * kH + j] : 0.f;
+    const float wv = p.on.wv2[j];
+    const float invA = 1.f / (float)A;
+#pragma unroll
+    for (int r = 0; r < kSamples; ++r) {
+      const float g = sg[r];
+      float s;
+      if (head == 0) {
+        s = 0.f;
+#pragma unroll
+        for (int k = 0; k < kVecMaxA; ++k) s = fmaf(g * ((k == sa[r] ? 1.f : 0.f) - invA), wa[k], s);
+      } else {
+        s = g * wv;
+      }
+      const float hv = L.h[r * 2 * kH + t];
+      s = hv > 0.f ? s : 0.f;
+      dh[r * 2 * kH + t] = s;
+      if (b0 + r < p.B) {
+        float* v = p.vec + (size_t)(b0 + r) * vecv::STRIDE;
+        v[vecv::H + t] = hv;
+        v[vecv::DH + t] = s;
+      }
+    }
+  }
+  __syncthreads();
+  {  // d(features) = W_adv1^T dh_adv + W_val1^T dh_val: thread = (head, input k), partial per head
+    float acc[kSamples] = {0.f, 0.f, 0.f, 0.f};
+    const float* Wk = L.W + head * kWHead + j * kWPitch;  // row k = j of the transposed image
+    for (int u = 0; u < kH; u += 4) {
+      const float w0 = Wk[u], w1 = Wk[u + 1], w2 = Wk[u + 2], w3 = Wk[u + 3];
+#pragma unroll
+      for (int r = 0; r < kSamples; ++r) {
+        const float4 d = *reinterpret_cast<const float4*>(&dh[r * 2 * kH + head * kH + u]);
+        acc[r] = fmaf(w0, d.x, acc[r]);
+        acc[r] = fmaf(w1, d.y, acc[r]);
+        acc[r] = fmaf(w2, d.z, acc[r]);
+        acc[r] = fmaf(w3, d.w, acc[r]);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < kSamples; ++r) dfp[(head * kSamples + r) * kH + j] = acc[r];
+  }
+  __syncthreads();
+  for (int i = t; i < kSamples * kH; i += kThreads) {
+    const int r = i >> 7, k = i & (kH - 1);
+    if (b0 + r >= p.B) continue;
+    const float fv = L.f[r * kH + k];
+    float* v = p.vec + (size_t)(b0 + r) * vecv::STRIDE;
+    v[vecv::F + k] = fv;
+    v[vecv::DF + k] = fv > 0.f ? dfp[r * kH + k] + dfp[(kSamples + r) * kH + k] : 0.f;
+    if (k < kVecMaxObs) v[vecv::X + k] = L.x[r * kVecMaxObs + k];
+  }
+}
+
+// ------------------------------------------------------------------ batch contraction
+// grad[i] = sum_b G[b][row] * X[b][col] for the tensor that owns flat element i (the ten
+// tensors of DuelingDQN.parameters() in order), b ascending; + one fp64 sum-of-squares
+// partial per workgroup.
+__global__ __launch_bounds__(kThreads) void vec_grad_k(VecGrad g) {
+  __shared__ double red[kThreads / 64];
+  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  const int obs = g.obs, A = g.A;
+  float v = 0.f;
+  if (i < g.n) {
+    // (offset, columns, output-gradient vector, input vector) of the owning tensor
+    int64_t off = 0;
+    int cols, goff, xoff;
+    const int64_t o1 = (int64_t)kH * obs, o2 = o1 + kH, o3 = o2 + kH * kH, o4 = o3 + kH, o5 = o4 + (int64_t)A * kH,
+                  o6 = o5 + A, o7 = o6 + kH * kH, o8 = o7 + kH, o9 = o8 + kH;
+    if (i < o1)      { off = 0;  cols = obs; goff = vecv::DF;      xoff = vecv::X; }
+    else if (i < o2) { off = o1; cols = 1;   goff = vecv::DF;      xoff = -1; }
+    else if (i < o3) { off = o2; cols = kH;  goff = vecv::DH;      xoff = vecv::F; }
+    else if (i < o4) { off = o3; cols = 1;   goff = vecv::DH;      xoff = -1; }
+    else if (i < o5) { off = o4; cols = kH;  goff = vecv::DA;      xoff = vecv::H; }
+    else if (i < o6) { off = o5; cols = 1;   goff = vecv::DA;      xoff = -1; }
+    else if (i < o7) { off = o6; cols = kH;  goff = vecv::DH + kH; xoff = vecv::F; }
+    else if (i < o8) { off = o7; cols = 1;   goff = vecv::DH + kH; xoff = -1; }
+    else if (i < o9) { off = o8; cols = kH;  goff = vecv::DA + 7;  xoff = vecv::H + kH; }
+    else             { off = o9; cols = 1;   goff = vecv::DA + 7;  xoff = -1; }
+    const int local = (int)(i - off);
+    const int row = local / cols, col = local - row * cols;
+    // 8 samples' loads in flight per round, summed in batch order (x = 1 for a bias)
+    const float* pg = g.vec + goff + row;
+    const float* px = xoff >= 0 ? g.vec + xoff + col : nullptr;
+    int b = 0;
+    for (; b + 8 <= g.B; b += 8) {
+      float gv[8], xv[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        gv[u] = pg[(size_t)(b + u) * vecv::STRIDE];
+        xv[u] = px ? px[(size_t)(b + u) * vecv::STRIDE] : 1.f;
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v = fmaf(gv[u], xv[u], v);
+    }
+    for (; b < g.B; ++b) v = fmaf(pg[(size_t)b * vecv::STRIDE], px ? px[(size_t)b * vecv::STRIDE] : 1.f, v);
+    g.grad[i] = v;
+  }
+  double sq = wave_sum((double)v * (double)v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
+  __syncthreads();
+  if (threadIdx.x == 0) g.part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+void check_net(const VecNet& n, const char* who) {
+  if (n.obs < 1 || n.obs > kVecMaxObs || n.A < 1 || n.A > kVecMaxA)
+    throw std::invalid_argument(std::string(who) + ": obs in [1, 8] and actions in [1, 7]");
+  if (!n.w0 || !n.b0 || !n.wa1 || !n.ba1 || !n.wa2 || !n.ba2 || !n.wv1 || !n.bv1 || !n.wv2 || !n.bv2)
+    throw std::invalid_argument(std::string(who) + ": missing parameter tensor");
+}
+
+void check_env(const VecEnv& V) {
+  if (V.kind < 0 || V.kind > 1) throw std::invalid_argument("vec classic env: kind 0 (CartPole) / 1 (MountainCar)");
+  if (V.obs != (V.kind == 0 ? 4 : 2)) throw std::invalid_argument("vec classic env: obs must be 4 (CartPole) / 2");
+  if (V.E < 1 || V.F < 2 * V.E) throw std::invalid_argument("vec classic env: ring must hold >= 2 E rows");
+  if (!V.state || !V.ring) throw std::invalid_argument("vec classic env: state / ring missing");
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------ launchers
+void vec_classic_reset(const VecEnv& V, const int64_t* step_counter, int* new_frame, int* hist, float* ep_log,
+                       hipStream_t s) {
+  check_env(V);
+  vec_classic_reset_k<<<(V.E + 63) / 64, 64, 0, s>>>(V, step_counter, new_frame, hist, ep_log);
+  LAUNCH_CHECK();
+}
+
+void vec_classic_step(const VecEnv& V, const int* actions, const int64_t* step_counter, float* reward, float* done,
+                      int* new_frame, float* ep_log, hipStream_t s) {
+  check_env(V);
+  vec_classic_step_k<<<(V.E + 63) / 64, 64, 0, s>>>(V, actions, step_counter, reward, done, new_frame, ep_log);
+  LAUNCH_CHECK();
+}
+
+void vec_act(const VecAct& a, hipStream_t s) {
+  check_net(a.net, "vec_act");
+  if (a.E < 1 || !a.ring || !a.hist || !a.eps || !a.q || !a.actions)
+    throw std::invalid_argument("vec_act: E >= 1 with ring, hist, eps, q and actions");
+  vec_act_k<<<(a.E + kRows - 1) / kRows, kThreads, 0, s>>>(a);
+  LAUNCH_CHECK();
+}
+
+void vec_learn(const VecLearn& p, hipStream_t s) {
+  check_net(p.on, "vec_learn (online)");
+  check_net(p.tg, "vec_learn (target)");
+  if (p.on.obs != p.tg.obs || p.on.A != p.tg.A) throw std::invalid_argument("vec_learn: nets differ in shape");
+  if (p.B < 1 || p.B > 1024) throw std::invalid_argument("vec_learn: batch must be in [1, 1024]");
+  if (!p.ring || !p.s_ids || !p.s2_ids || !p.act || !p.rew || !p.done || !p.idx || !p.w || !p.q_s || !p.q_s2 ||
+      !p.qt_s2 || !p.vec || !p.delta || !p.lw)
+    throw std::invalid_argument("vec_learn: missing buffer");
+  if (p.beta_out && !(p.beta_horizon > 0.0)) throw std::invalid_argument("vec_learn: beta horizon must be > 0");
+  vec_learn_k<<<(p.B + kSamples - 1) / kSamples, kThreads, 0, s>>>(p);
+  LAUNCH_CHECK();
+}
+
+int64_t vec_param_count(int obs, int A) {
+  return (int64_t)kH * obs + kH + 2 * ((int64_t)kH * kH + kH) + (int64_t)A * kH + A + kH + 1;
+}
+
+int vec_grad_blocks(int64_t n) { return (int)((n + kThreads - 1) / kThreads); }
+
+void vec_grad(const VecGrad& g, hipStream_t s) {
+  if (g.obs < 1 || g.obs > kVecMaxObs || g.A < 1 || g.A > kVecMaxA || g.n != vec_param_count(g.obs, g.A))
+    throw std::invalid_argument("vec_grad: n must be the MLP dueling net's parameter count");
+  if (g.B < 1 || !g.vec || !g.grad || !g.part) throw std::invalid_argument("vec_grad: missing buffer");
+  vec_grad_k<<<vec_grad_blocks(g.n), kThreads, 0, s>>>(g);
+  LAUNCH_CHECK();
+}
+
+}  // namespace apex

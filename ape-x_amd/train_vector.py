@@ -1,0 +1,121 @@
+"""GPU Ape-X training CLI for vector-observation envs:
+``python -m apex_amd.train_vector --env CartPole-v0 --envs 256 --max-step N --save-dir D``.
+
+The MI355X counterpart of the reference's single-node ``ApeX.py`` (MountainCar-v0) and
+``DQN.py`` (CartPole) trainers: one :class:`~apex_amd.engine.vector.VectorApexEngine` keeps
+E vectorised GPU envs, the HBM prioritized replay and the fused MLP dueling-DQN learner on
+one GPU.  One *step* = one learner SGD step + ``--actor-steps`` steps of all E envs.
+
+Reference cadences and artefacts kept: learning starts once the replay holds more than one
+batch, weights are published to the actors every 32 learner steps, the target network is
+synced every 2500, and ``model{t}.pth`` (the reference ``state_dict``) is written every
+``--save-interval`` (5000) steps and at the last one.  One JSON line is printed per
+``--log-interval`` steps (loss, grad norms, SGD and env steps per second, the actors' mean
+episode return) and, every ``--eval-interval`` steps, the greedy return of
+``--eval-episodes`` evaluation episodes.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import time
+
+import torch
+
+from .engine.vector import VECTOR_ENVS, VectorApexEngine, VectorEngineConfig
+
+
+def parser() -> argparse.ArgumentParser:
+    d = VectorEngineConfig()
+    p = argparse.ArgumentParser(description="Ape-X DQN on vector-observation envs (GPU-resident engine)")
+    p.add_argument("--env", default=d.env_id, choices=sorted(VECTOR_ENVS))
+    p.add_argument("--envs", type=int, default=d.n_envs, help="GPU envs (the reference's actor processes)")
+    p.add_argument("--max-step", type=int, default=100_000, help="learner SGD steps")
+    p.add_argument("--batch-size", type=int, default=d.batch_size)
+    p.add_argument("--n-step", type=int, default=d.n_step)
+    p.add_argument("--gamma", type=float, default=d.gamma)
+    p.add_argument("--lr", type=float, default=d.lr)
+    p.add_argument("--capacity", type=int, default=d.replay_capacity)
+    p.add_argument("--actor-steps", type=int, default=d.actor_steps_per_learner_step,
+                   help="steps of all envs per learner step")
+    p.add_argument("--nstep-mode", default=d.nstep_mode, choices=["reference", "textbook"])
+    p.add_argument("--target-update-interval", type=int, default=d.target_update_interval)
+    p.add_argument("--publish-interval", type=int, default=d.publish_param_interval)
+    p.add_argument("--save-interval", type=int, default=5000)
+    p.add_argument("--save-dir", default=".")
+    p.add_argument("--log-interval", type=int, default=1000, help="steps between metric reads (host syncs)")
+    p.add_argument("--eval-interval", type=int, default=0, help="steps between greedy evaluations (0 = off)")
+    p.add_argument("--eval-episodes", type=int, default=10)
+    p.add_argument("--json-log", default=None, help="append one JSON record per log interval to this file")
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--device", default="cuda:0")
+    p.add_argument("--no-graphs", action="store_true")
+    return p
+
+
+def model_path(save_dir: str, t: int) -> str:
+    return os.path.join(save_dir, f"model{t}.pth")
+
+
+def config_from_args(a) -> VectorEngineConfig:
+    return VectorEngineConfig(env_id=a.env, n_envs=a.envs, batch_size=a.batch_size, n_step=a.n_step, gamma=a.gamma,
+                              lr=a.lr, replay_capacity=a.capacity, actor_steps_per_learner_step=a.actor_steps,
+                              nstep_mode=a.nstep_mode, target_update_interval=a.target_update_interval,
+                              publish_param_interval=a.publish_interval, seed=a.seed).validate()
+
+
+def train(a) -> dict:
+    cfg = config_from_args(a)
+    if not torch.cuda.is_available():
+        raise RuntimeError("train_vector needs a GPU (the host-side trainer is apex_amd.trainers.apex_single)")
+    eng = VectorApexEngine(cfg, a.device)
+    eng.fill()
+    if not a.no_graphs:
+        eng.capture()
+    jl = open(a.json_log, "a") if a.json_log else None
+    last = {}
+    t_win, s_win, a_win = time.perf_counter(), eng.learn_steps, eng.actor_steps
+    ep_seen = torch.zeros(cfg.n_envs, device=eng.device)
+    try:
+        while eng.learn_steps < a.max_step:
+            eng.train_step()
+            t = eng.learn_steps
+            final = t >= a.max_step
+            if t % a.save_interval == 0 or final:
+                eng.save(model_path(a.save_dir, t))
+            ev = a.eval_interval > 0 and (t % a.eval_interval == 0 or final)
+            if not (t % a.log_interval == 0 or final or ev):
+                continue
+            torch.cuda.synchronize(eng.device)
+            dt = max(time.perf_counter() - t_win, 1e-9)
+            st = eng.learner.stats()
+            ret, _, cnt = eng.shard.episode_stats()
+            fresh = cnt > ep_seen  # envs that finished an episode in this window
+            ep_seen = cnt.clone()
+            last = {"step": t, "loss": st["loss"], "grad_norm": st["grad_norm"], "grad_norm_l2": st["grad_norm_l2"],
+                    "lr": st["lr"], "sgd_steps_per_s": round((t - s_win) / dt, 1),
+                    "env_steps_per_s": round((eng.actor_steps - a_win) * cfg.n_envs / dt, 1),
+                    "episodes": int(cnt.sum().item()),
+                    "actor_mean_return": float(ret[fresh].mean().item()) if bool(fresh.any()) else None}
+            if ev:
+                g = eng.evaluate(a.eval_episodes)
+                last["greedy_mean_return"] = sum(g) / len(g)
+            print(json.dumps(last), flush=True)
+            if jl:
+                jl.write(json.dumps(last) + "\n")
+                jl.flush()
+            t_win, s_win, a_win = time.perf_counter(), eng.learn_steps, eng.actor_steps
+    finally:
+        if jl:
+            jl.close()
+    return last
+
+
+def main(argv=None) -> int:
+    train(parser().parse_args(argv))
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -14,7 +14,9 @@ SURVEY Q7).  ``collect_once=True`` reproduces that behaviour.
 
 The on-GPU, many-env version of this loop is :class:`apex_amd.engine.apex.ApexEngine`
 (vectorised GPU actors + HBM replay + fused HIP learner); this trainer keeps the
-reference's host-side structure for non-image / gym-style envs.
+reference's host-side structure for non-image / gym-style envs.  ``--engine gpu`` runs the
+same configuration on :class:`apex_amd.engine.vector.VectorApexEngine` instead (GPU envs,
+HBM replay, HIP learner for CartPole / MountainCar; ``apex_amd.train_vector``).
 """
 from __future__ import annotations
 
@@ -163,7 +165,14 @@ def main(argv=None):
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--save-dir", default=".")
     p.add_argument("--collect-once", action="store_true", help="reference behaviour: collect once, train offline")
+    p.add_argument("--engine", choices=["host", "gpu"], default="host",
+                   help="gpu: the GPU-resident engine (apex_amd.train_vector) instead of CPU actor processes")
     a = p.parse_args(argv)
+    if a.engine == "gpu":
+        from .. import train_vector
+
+        return train_vector.main(["--env", a.env, "--max-step", str(int(a.max_step)), "--batch-size",
+                                  str(a.batch_size), "--seed", str(a.seed), "--save-dir", a.save_dir])
     t = train_DQN(a.env, seed=a.seed, n_workers=a.n_workers, max_step=a.max_step, batch_size=a.batch_size,
                   save_dir=a.save_dir, collect_once=a.collect_once)
     print(t.train())
