@@ -21,12 +21,20 @@ Launch budget (kernel launches per step, all on the caller's stream, no host syn
   loss mean, step counter + 1; it walks <= 64 dirty paths inside its leaves launch, a larger
   batch adds one launch per tree level of more than 64 nodes).  ``fused_norm=False`` takes the
   norm from a separate ``grad_sumsq`` launch instead (6 launches).
+* greedy evaluation: ``evaluate()`` is the stepwise yardstick (``vec_act`` ->
+  ``vec_classic_step`` -> ``frame_hist_step`` + three torch ops per env step, a host sync every 50
+  steps).  ``rollout_evaluate()`` is 1 launch + 1 read-back: ``vec_rollout`` plays every
+  episode from reset to its first done inside one kernel, heads staged once, and returns the
+  same floats bit for bit.  :class:`VectorEvaluator` is the non-blocking form, 2 launches per
+  evaluation (``copy_f32`` snapshot on the training stream, ``vec_rollout`` on a side stream) +
+  three async copies to pinned memory; eager, between graph replays.
 
 Serial actor-then-learner on one stream; overlap and multi-GPU topologies are the Atari
 engine's and are not offered here.
 """
 from __future__ import annotations
 
+import collections
 import copy
 from dataclasses import dataclass
 
@@ -386,6 +394,7 @@ class VectorApexEngine:
         self.actor_steps = 0
         self._g_actor = self._g_learn = None
         self._eval = None
+        self._rollout = None
 
     # ------------------------------------------------------------------ phases
     def publish_params(self) -> None:
@@ -505,3 +514,116 @@ class VectorApexEngine:
             if (t + 1) % 50 == 0 and bool(got.all()):
                 break
         return first.tolist()
+
+    def _eval_seed(self, seed: int | None) -> int:
+        sd = (self.cfg.seed * 7919 + 0xE7A1 + self.learn_steps) if seed is None else int(seed)
+        return sd & 0xFFFFFFFFFFFF
+
+    def rollout_evaluate(self, episodes: int = 10, seed: int | None = None,
+                         max_episode_steps: int | None = None) -> list[float]:
+        """``evaluate()`` in one launch: ``vec_rollout`` plays the ``episodes`` greedy episodes
+        from reset to their first done inside one kernel on the current stream, then one
+        read-back.  Same contract, same default seed and, for the same seed, the same returns
+        bit for bit.  The online weights are read in place (the caller's stream order protects
+        them, as in ``evaluate()``)."""
+        n = int(episodes)
+        limit = int(self.limit if max_episode_steps is None else max_episode_steps)
+        if self._rollout is None or self._rollout.n != n:
+            self._rollout = VecRolloutBuffers(self.hip, self.learner.net, self.kind, self.obs_dim, n, self.device)
+        ro = self._rollout
+        ro.launch(self._eval_seed(seed), limit)
+        return ro.returns.tolist()
+
+
+class VecRolloutBuffers:
+    """Device outputs of ``vec_rollout`` for ``n`` episodes of one net + the launch."""
+
+    def __init__(self, hip, net, kind: int, obs_dim: int, n: int, device):
+        self.hip, self.net, self.kind, self.obs_dim, self.n = hip, net, int(kind), int(obs_dim), int(n)
+        self.returns = torch.zeros(self.n, dtype=torch.float32, device=device)
+        self.lengths = torch.zeros(self.n, dtype=torch.int32, device=device)
+        self.ended = torch.zeros(self.n, dtype=torch.int32, device=device)
+
+    def launch(self, seed: int, max_steps: int, trace: dict | None = None) -> None:
+        """One ``vec_rollout`` launch on the current stream.  ``trace``: the tensors
+        ``obs`` f32 [n, T, obs_dim], ``q`` f32 [n, T, A] and ``act`` i32 [n, T]."""
+        d = dict(kind=self.kind, N=self.n, obs=self.obs_dim, max_steps=int(max_steps), seed=int(seed),
+                 returns=self.returns.data_ptr(), lengths=self.lengths.data_ptr(), ended=self.ended.data_ptr())
+        if trace is not None:
+            d.update(trace_obs=trace["obs"].data_ptr(), trace_q=trace["q"].data_ptr(),
+                     trace_act=trace["act"].data_ptr(), trace_T=int(trace["obs"].shape[1]))
+        self.hip.vec_rollout(self.hip.make_vec_rollout(self.net, d), torch.cuda.current_stream().cuda_stream)
+
+
+class VectorEvaluator:
+    """Greedy evaluation beside training: ``launch()`` snapshots the online weights on the
+    training stream and plays the episodes with ``vec_rollout`` on a side stream; training goes
+    on in place and ``poll()`` / ``wait()`` hand the result over once it has landed in pinned
+    host memory.  While a launch is in flight a further ``launch()`` does nothing (its
+    snapshot buffer may still be read by the running kernel): evaluations conflate, as the
+    reference's evaluator process does.  All launches are eager, issued between graph replays;
+    no captured graph gains a branch."""
+
+    def __init__(self, engine: VectorApexEngine, episodes: int = 10, max_episode_steps: int | None = None):
+        self.engine = engine
+        self.hip, self.device = engine.hip, engine.device
+        self.n = int(episodes)
+        self.limit = int(engine.limit if max_episode_steps is None else max_episode_steps)
+        self.model = copy.deepcopy(engine.learner.model)   # the snapshot
+        self.model._flat = None
+        self.flat = self.model.flatten_parameters()
+        for p in self.model.parameters():
+            p.requires_grad_(False)
+        self.stream = torch.cuda.Stream(device=self.device)
+        self.ro = VecRolloutBuffers(self.hip, vec_net(self.hip, self.model), engine.kind, engine.obs_dim, self.n,
+                                    self.device)
+        self.host = {"returns": torch.zeros(self.n, dtype=torch.float32).pin_memory(),
+                     "lengths": torch.zeros(self.n, dtype=torch.int32).pin_memory(),
+                     "ended": torch.zeros(self.n, dtype=torch.int32).pin_memory()}
+        self.snapshot_taken = torch.cuda.Event()
+        self.results_landed = torch.cuda.Event()
+        self._pending = False   # a launch whose result is still on its way to the host
+        self._tag = None
+        self._done = collections.deque()   # landed results not yet handed over
+
+    def launch(self, seed: int | None = None, tag=None) -> bool:
+        """Start one evaluation of the online weights as they are at this point of the current
+        stream.  ``False`` (and nothing done) while the previous one has not landed."""
+        if self._pending:
+            if not self.results_landed.query():
+                return False
+            self._harvest()  # the pinned buffers are about to be reused
+        eng = self.engine
+        sd = eng._eval_seed(seed)
+        eng.learner.copy_params_to(self.flat)
+        self.snapshot_taken.record()
+        with torch.cuda.stream(self.stream):
+            self.stream.wait_event(self.snapshot_taken)
+            self.ro.launch(sd, self.limit)
+            for k, h in self.host.items():
+                h.copy_(getattr(self.ro, k), non_blocking=True)
+            self.results_landed.record()
+        self._pending, self._tag = True, tag
+        return True
+
+    def _harvest(self) -> None:
+        self._pending = False
+        self._done.append({"tag": self._tag, "returns": self.host["returns"].tolist(),
+                           "lengths": self.host["lengths"].tolist(), "ended": self.host["ended"].tolist()})
+
+    def poll(self) -> dict | None:
+        """The oldest finished evaluation not yet handed over (each exactly once), or ``None``."""
+        if self._pending and self.results_landed.query():
+            self._harvest()
+        return self._done.popleft() if self._done else None
+
+    def wait(self) -> dict | None:
+        """As ``poll()``, but blocks until the launch in flight has landed: on the results event
+        only, never on the device.  ``None`` if nothing was launched."""
+        if self._done:
+            return self._done.popleft()
+        if not self._pending:
+            return None
+        self.results_landed.synchronize()
+        self._harvest()
+        return self._done.popleft()

@@ -956,6 +956,21 @@ PYBIND11_MODULE(_apex_hip, m) {
                   P<const int64_t>(counter), P<float>(q), P<int>(actions)};
   });
   m.def("vec_act", [](const VecAct& a, uint64_t s) { vec_act(a, S(s)); });
+  py::class_<VecRollout>(m, "VecRollout");
+  // d: kind, N, obs, max_steps, seed, returns, lengths, ended [+ trace_obs, trace_q, trace_act, trace_T]
+  m.def("make_vec_rollout", [](const VecNet& net, py::dict d) {
+    auto opt = [&](const char* k) { return d.contains(k) ? d[k].cast<uint64_t>() : (uint64_t)0; };
+    VecRollout r{};
+    r.net = net;
+    r.kind = d["kind"].cast<int>(); r.N = d["N"].cast<int>(); r.obs = d["obs"].cast<int>();
+    r.max_steps = d["max_steps"].cast<int>(); r.seed = d["seed"].cast<uint64_t>();
+    r.returns = P<float>(opt("returns")); r.lengths = P<int>(opt("lengths")); r.ended = P<int>(opt("ended"));
+    r.trace_obs = P<float>(opt("trace_obs")); r.trace_q = P<float>(opt("trace_q"));
+    r.trace_act = P<int>(opt("trace_act"));
+    r.trace_T = d.contains("trace_T") ? d["trace_T"].cast<int>() : 0;
+    return r;
+  });
+  m.def("vec_rollout", [](const VecRollout& r, uint64_t s) { vec_rollout(r, S(s)); });
   py::class_<VecLearn>(m, "VecLearn");
   m.def("make_vec_learn", [](const VecNet& on, const VecNet& tg, py::dict d) {
     auto g = [&](const char* k) { return d[k].cast<uint64_t>(); };

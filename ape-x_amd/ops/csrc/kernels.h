@@ -694,6 +694,26 @@ struct VecAct {
   int* actions;            // [E]
 };
 void vec_act(const VecAct& a, hipStream_t s);
+// N greedy episodes from reset to their first done in one launch (one workgroup per 8 episodes,
+// the heads staged once): episode e starts at the reset draw of vec_classic_reset at step
+// counter 0 and takes the first argmax of Q each step (vec_forward's and vec_classic_step's
+// arithmetic).  The trace (all three pointers or none) records the first trace_T steps of every
+// episode; rows past an episode's end are never written.
+struct VecRollout {
+  VecNet net;
+  int kind;            // 0 CartPole, 1 MountainCar
+  int N, obs;          // episodes, observation floats
+  int max_steps;       // TimeLimit: the episode ends once its length reaches it
+  uint64_t seed;       // the env seed (VecEnv::seed)
+  float* returns;      // [N] sum of rewards
+  int* lengths;        // [N] steps taken
+  int* ended;          // [N] 1 terminal, 2 time limit
+  float* trace_obs;    // optional [N][trace_T][obs]: the observation acted on
+  float* trace_q;      // optional [N][trace_T][A]
+  int* trace_act;      // optional [N][trace_T]
+  int trace_T;
+};
+void vec_rollout(const VecRollout& r, hipStream_t s);
 // Per-sample backward vectors written by vec_learn and contracted over the batch by vec_grad
 // (offsets in floats): input, features, their gradient, both hidden layers, their gradient,
 // dL/dA[0..A) with dL/dV at DA + 7.

@@ -13,6 +13,8 @@
 //                                         envs/classic.py in fp32)
 //   vec_act      one workgroup per 8 envs: both heads' 128x128 weights staged (transposed) in LDS,
 //                Q[E, A], then select_actions_k's draw in the same launch
+//   vec_rollout  one workgroup per 8 greedy episodes, reset to first done in one launch: heads staged
+//                once, then forward / first argmax / env dynamics per step, no ring and no host
 //   vec_learn    one workgroup per 4 sampled rows: target net on (s, s'), online net on (s, s'),
 //                double-DQN n-step Huber loss, backward to per-sample vectors (aql_learn_bwd's
 //                shape); block 0 also writes the next step's PER beta
@@ -33,17 +35,50 @@ constexpr int kWHead = kH * kWPitch;    // floats per head image
 constexpr int kThreads = 256;
 
 // ------------------------------------------------------------------ envs
-__device__ __forceinline__ void classic_reset_obs(const VecEnv& V, int e, uint64_t ctr, float* st) {
+// the reset observation of env e at Philox counter ctr (CartPole: 4 floats; MountainCar: 2 + zeros)
+__device__ __forceinline__ void classic_reset_obs(int kind, uint64_t seed, int e, uint64_t ctr, float* st) {
   float u[4];
-  uniform4(V.seed, (uint64_t)e, ctr, u);
-  if (V.kind == 0) {  // CartPole: U(-0.05, 0.05)^4
+  uniform4(seed, (uint64_t)e, ctr, u);
+  if (kind == 0) {  // CartPole: U(-0.05, 0.05)^4
 #pragma unroll
     for (int k = 0; k < 4; ++k) st[k] = -0.05f + 0.1f * u[k];
-  } else {            // MountainCar: position U(-0.6, -0.4), velocity 0
+  } else {          // MountainCar: position U(-0.6, -0.4), velocity 0
     st[0] = -0.6f + 0.2f * u[0];
     st[1] = 0.f;
     st[2] = 0.f;
     st[3] = 0.f;
+  }
+}
+
+// one step of env `kind` from state s with action a: next state nv[4] (MountainCar: 2 + zeros),
+// reward, terminal.  Shared by vec_classic_step_k and vec_rollout_k, so both step bit for bit alike.
+__device__ __forceinline__ void classic_dynamics(int kind, const float* s, int a, float* nv, float& r, bool& term) {
+  if (kind == 0) {  // CartPole (Barto et al. 1983; envs/classic.py CartPoleEnv, as aql_env_step)
+    const float x = s[0], xd = s[1], th = s[2], thd = s[3];
+    const float force = (a == 1) ? 10.f : -10.f;
+    const float ct = cosf(th), sn = sinf(th);
+    const float tmp = (force + 0.05f * thd * thd * sn) / 1.1f;
+    const float tha = (9.8f * sn - ct * tmp) / (0.5f * (4.f / 3.f - 0.1f * ct * ct / 1.1f));
+    const float xa = tmp - 0.05f * tha * ct / 1.1f;
+    nv[0] = x + 0.02f * xd;
+    nv[1] = xd + 0.02f * xa;
+    nv[2] = th + 0.02f * thd;
+    nv[3] = thd + 0.02f * tha;
+    r = 1.f;
+    term = nv[0] < -2.4f || nv[0] > 2.4f || nv[2] < -0.20943951f || nv[2] > 0.20943951f;
+  } else {          // MountainCar (Moore 1990; envs/classic.py MountainCarEnv)
+    float pos = s[0], v = s[1];
+    v += (float)(a - 1) * 0.001f + cosf(3.f * pos) * (-0.0025f);
+    v = fminf(fmaxf(v, -0.07f), 0.07f);
+    pos += v;
+    pos = fminf(fmaxf(pos, -1.2f), 0.6f);
+    if (pos == -1.2f && v < 0.f) v = 0.f;  // inelastic left wall
+    nv[0] = pos;
+    nv[1] = v;
+    nv[2] = 0.f;
+    nv[3] = 0.f;
+    r = -1.f;
+    term = pos >= 0.5f;
   }
 }
 
@@ -55,7 +90,7 @@ __global__ void vec_classic_reset_k(VecEnv V, const int64_t* step_counter, int* 
   const int slot = (int)(((int64_t)step * V.E + e) % V.F);
   float* gst = V.state + (size_t)e * vecs::STRIDE;
   float st[4];
-  classic_reset_obs(V, e, (uint64_t)step * 16 + 1, st);
+  classic_reset_obs(V.kind, V.seed, e, (uint64_t)step * 16 + 1, st);
   for (int k = 0; k < vecs::STRIDE; ++k) gst[k] = k < 4 ? st[k] : 0.f;
   for (int k = 0; k < V.obs; ++k) V.ring[(size_t)slot * V.obs + k] = st[k];
   new_frame[e] = slot;
@@ -71,34 +106,10 @@ __global__ void vec_classic_step_k(VecEnv V, const int* __restrict__ actions, co
   const int slot = (int)(((int64_t)(step + 1) * V.E + e) % V.F);
   float* gst = V.state + (size_t)e * vecs::STRIDE;
   const int a = actions[e];
-  float nv[4] = {0.f, 0.f, 0.f, 0.f};
+  float nv[4];
   float r;
   bool term;
-  if (V.kind == 0) {  // CartPole (Barto et al. 1983; envs/classic.py CartPoleEnv, as aql_env_step)
-    const float x = gst[0], xd = gst[1], th = gst[2], thd = gst[3];
-    const float force = (a == 1) ? 10.f : -10.f;
-    const float ct = cosf(th), sn = sinf(th);
-    const float tmp = (force + 0.05f * thd * thd * sn) / 1.1f;
-    const float tha = (9.8f * sn - ct * tmp) / (0.5f * (4.f / 3.f - 0.1f * ct * ct / 1.1f));
-    const float xa = tmp - 0.05f * tha * ct / 1.1f;
-    nv[0] = x + 0.02f * xd;
-    nv[1] = xd + 0.02f * xa;
-    nv[2] = th + 0.02f * thd;
-    nv[3] = thd + 0.02f * tha;
-    r = 1.f;
-    term = nv[0] < -2.4f || nv[0] > 2.4f || nv[2] < -0.20943951f || nv[2] > 0.20943951f;
-  } else {            // MountainCar (Moore 1990; envs/classic.py MountainCarEnv)
-    float pos = gst[0], v = gst[1];
-    v += (float)(a - 1) * 0.001f + cosf(3.f * pos) * (-0.0025f);
-    v = fminf(fmaxf(v, -0.07f), 0.07f);
-    pos += v;
-    pos = fminf(fmaxf(pos, -1.2f), 0.6f);
-    if (pos == -1.2f && v < 0.f) v = 0.f;  // inelastic left wall
-    nv[0] = pos;
-    nv[1] = v;
-    r = -1.f;
-    term = pos >= 0.5f;
-  }
+  classic_dynamics(V.kind, gst, a, nv, r, term);
   const float ep_ret = gst[vecs::EPRET] + r;
   const float ep_len = gst[vecs::EPLEN] + 1.f;
   const bool time_up = V.max_steps > 0 && ep_len >= (float)V.max_steps;  // TimeLimit ends with done = 1
@@ -113,7 +124,7 @@ __global__ void vec_classic_step_k(VecEnv V, const int* __restrict__ actions, co
       ep_log[e * 4 + 1] = ep_len;
       ep_log[e * 4 + 2] += 1.f;
     }
-    classic_reset_obs(V, e, (uint64_t)step * 16 + 7, nv);
+    classic_reset_obs(V.kind, V.seed, e, (uint64_t)step * 16 + 7, nv);
     gst[vecs::EPRET] = 0.f;
     gst[vecs::EPLEN] = 0.f;
   } else {
@@ -157,47 +168,66 @@ __device__ __forceinline__ void stage_heads(const VecNet& n, float* W) {
   }
 }
 
+// This thread's operands of the first two layers: its features.0 row and bias (unit j), its
+// advantage.0 / value.0 bias (head, unit j).  They do not depend on the rows.
+struct FwdOperands {
+  float w[kVecMaxObs], b0, b1;
+};
+
+__device__ __forceinline__ FwdOperands load_fwd_operands(const VecNet& n) {
+  const int t = threadIdx.x, j = t & (kH - 1), head = t >> 7;
+  FwdOperands o;
+#pragma unroll
+  for (int k = 0; k < kVecMaxObs; ++k) o.w[k] = k < n.obs ? n.w0[j * n.obs + k] : 0.f;
+  o.b0 = n.b0[j];
+  o.b1 = (head ? n.bv1 : n.ba1)[j];
+  return o;
+}
+
+// features.0: thread = (unit j, 4 rows).  L.x -> L.f
+__device__ __forceinline__ void fwd_features(const FwdOperands& o, FwdLds& L) {
+  const int t = threadIdx.x, j = t & (kH - 1), r0 = (t >> 7) * 4;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    float acc = o.b0;
+#pragma unroll
+    for (int k = 0; k < kVecMaxObs; ++k) acc = fmaf(o.w[k], L.x[(r0 + r) * kVecMaxObs + k], acc);
+    L.f[(r0 + r) * kH + j] = fmaxf(acc, 0.f);
+  }
+}
+
+// advantage.0 / value.0: thread = (head, unit j), all rows.  L.f -> L.h
+__device__ __forceinline__ void fwd_hidden(const FwdOperands& o, FwdLds& L) {
+  const int t = threadIdx.x, j = t & (kH - 1), head = t >> 7;
+  float acc[kRows];
+#pragma unroll
+  for (int r = 0; r < kRows; ++r) acc[r] = o.b1;
+  const float* Wh = L.W + head * kWHead + j;
+  for (int k = 0; k < kH; k += 4) {
+    const float w0 = Wh[(k + 0) * kWPitch], w1 = Wh[(k + 1) * kWPitch], w2 = Wh[(k + 2) * kWPitch],
+                w3 = Wh[(k + 3) * kWPitch];
+#pragma unroll
+    for (int r = 0; r < kRows; ++r) {
+      const float4 fv = *reinterpret_cast<const float4*>(&L.f[r * kH + k]);
+      acc[r] = fmaf(w0, fv.x, acc[r]);
+      acc[r] = fmaf(w1, fv.y, acc[r]);
+      acc[r] = fmaf(w2, fv.z, acc[r]);
+      acc[r] = fmaf(w3, fv.w, acc[r]);
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < kRows; ++r) L.h[r * 2 * kH + t] = fmaxf(acc[r], 0.f);
+}
+
 // Q of the kRows rows in L.x (weights of `n` already staged in L.W) -> L.f, L.h, L.q.
 // Begins and ends with a workgroup barrier.
 __device__ void vec_forward(const VecNet& n, FwdLds& L) {
-  const int t = threadIdx.x, j = t & (kH - 1), head = t >> 7;
+  const int t = threadIdx.x;
   __syncthreads();
-  {  // features.0: thread = (unit j, 4 rows)
-    const int r0 = head * 4;
-    float w[kVecMaxObs];
-#pragma unroll
-    for (int k = 0; k < kVecMaxObs; ++k) w[k] = k < n.obs ? n.w0[j * n.obs + k] : 0.f;
-    const float b = n.b0[j];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float acc = b;
-#pragma unroll
-      for (int k = 0; k < kVecMaxObs; ++k) acc = fmaf(w[k], L.x[(r0 + r) * kVecMaxObs + k], acc);
-      L.f[(r0 + r) * kH + j] = fmaxf(acc, 0.f);
-    }
-  }
+  const FwdOperands op = load_fwd_operands(n);
+  fwd_features(op, L);
   __syncthreads();
-  {  // advantage.0 / value.0: thread = (head, unit j), all rows
-    float acc[kRows];
-    const float b = (head ? n.bv1 : n.ba1)[j];
-#pragma unroll
-    for (int r = 0; r < kRows; ++r) acc[r] = b;
-    const float* Wh = L.W + head * kWHead + j;
-    for (int k = 0; k < kH; k += 4) {
-      const float w0 = Wh[(k + 0) * kWPitch], w1 = Wh[(k + 1) * kWPitch], w2 = Wh[(k + 2) * kWPitch],
-                  w3 = Wh[(k + 3) * kWPitch];
-#pragma unroll
-      for (int r = 0; r < kRows; ++r) {
-        const float4 fv = *reinterpret_cast<const float4*>(&L.f[r * kH + k]);
-        acc[r] = fmaf(w0, fv.x, acc[r]);
-        acc[r] = fmaf(w1, fv.y, acc[r]);
-        acc[r] = fmaf(w2, fv.z, acc[r]);
-        acc[r] = fmaf(w3, fv.w, acc[r]);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < kRows; ++r) L.h[r * 2 * kH + t] = fmaxf(acc[r], 0.f);
-  }
+  fwd_hidden(op, L);
   __syncthreads();
   {  // advantage.2 / value.2 and the dueling combine: a wave per row pair
     const int lane = t & 63, wave = t >> 6;
@@ -255,6 +285,132 @@ __global__ __launch_bounds__(kThreads) void vec_act_k(VecAct a) {
       best = r < A ? r : A - 1;
     }
     a.actions[e] = best;
+  }
+}
+
+// ------------------------------------------------------------------ greedy rollouts
+// This lane's operands of the output layers, held across env steps: output o < A is
+// advantage.2 row o, output A is value.2 (lanes `lane` and `lane + 64` of each row).
+struct OutOperands {
+  float lo[kVecMaxA + 1], hi[kVecMaxA + 1], b[kVecMaxA + 1];
+};
+
+__device__ __forceinline__ OutOperands load_out_operands(const VecNet& n) {
+  const int lane = threadIdx.x & 63;
+  OutOperands w;
+#pragma unroll
+  for (int o = 0; o <= kVecMaxA; ++o) {
+    const float* wo = o < n.A ? n.wa2 + o * kH : n.wv2;
+    w.lo[o] = o <= n.A ? wo[lane] : 0.f;
+    w.hi[o] = o <= n.A ? wo[lane + 64] : 0.f;
+    w.b[o] = o < n.A ? n.ba2[o] : o == n.A ? n.bv2[0] : 0.f;
+  }
+  return w;
+}
+
+// vec_forward with every step-invariant load taken by the caller: the same fma chains, sums
+// and reductions in the same order, so Q is bit-equal to vec_forward's.
+__device__ __forceinline__ void vec_forward_held(int A, const FwdOperands& op, const OutOperands& w, FwdLds& L) {
+  const int t = threadIdx.x;
+  __syncthreads();
+  fwd_features(op, L);
+  __syncthreads();
+  fwd_hidden(op, L);
+  __syncthreads();
+  {  // advantage.2 / value.2 and the dueling combine: a wave per row pair
+    const int lane = t & 63, wave = t >> 6;
+    for (int r = wave; r < kRows; r += 4) {
+      const float* hr = L.h + r * 2 * kH;
+      float advsum = 0.f, val = 0.f;
+#pragma unroll
+      for (int o = 0; o <= kVecMaxA; ++o) {
+        if (o > A) continue;  // (uniform)
+        const float* hb = o < A ? hr : hr + kH;
+        float p = fmaf(w.lo[o], hb[lane], w.hi[o] * hb[lane + 64]);
+        p = wave_sum(p);
+        if (o < A) {
+          p += w.b[o];
+          advsum += p;
+          if (lane == 0) L.q[r * 8 + o] = p;
+        } else {
+          val = p + w.b[o];
+        }
+      }
+      if (lane == 0) {
+        const float mean = advsum / (float)A;
+        for (int o = 0; o < A; ++o) L.q[r * 8 + o] = val + L.q[r * 8 + o] - mean;
+      }
+    }
+  }
+  __syncthreads();
+}
+
+// One workgroup plays kRows greedy episodes from reset to their first done.  Threads 0..7 each
+// own one episode (state, return and length in registers); all 256 threads run the forward.
+// A row that has ended, or lies past N, stays in L.x as it was and is never written again.
+__global__ __launch_bounds__(kThreads) void vec_rollout_k(VecRollout p) {
+  __shared__ FwdLds L;
+  __shared__ int any_live;
+  const int t = threadIdx.x;
+  const int e = blockIdx.x * kRows + t;
+  const int obs = p.obs, A = p.net.A;
+  const bool tracing = p.trace_obs != nullptr;
+  bool live = t < kRows && e < p.N;
+  float st[4] = {0.f, 0.f, 0.f, 0.f};
+  float ret = 0.f;
+  int len = 0;
+  if (t < kRows) {
+    // vec_classic_reset's draw at step counter 0 (rows past N repeat the last episode's)
+    classic_reset_obs(p.kind, p.seed, min(e, p.N - 1), 1, st);
+#pragma unroll
+    for (int k = 0; k < kVecMaxObs; ++k) L.x[t * kVecMaxObs + k] = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (k < obs) L.x[t * kVecMaxObs + k] = st[k];
+  }
+  stage_heads(p.net, L.W);
+  const FwdOperands op = load_fwd_operands(p.net);
+  const OutOperands wout = load_out_operands(p.net);
+  for (int step = 0; step < p.max_steps; ++step) {
+    vec_forward_held(A, op, wout, L);
+    if (t < 64) {  // (the owners' wave)
+      if (live) {
+        const float* row = L.q + t * 8;
+        int best = 0;  // vec_act_k's first argmax
+        float bv = row[0];
+        for (int k = 1; k < A; ++k)
+          if (row[k] > bv) { bv = row[k]; best = k; }
+        if (tracing && step < p.trace_T) {
+          const size_t at = (size_t)e * p.trace_T + step;
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            if (k < obs) p.trace_obs[at * obs + k] = st[k];
+          for (int k = 0; k < A; ++k) p.trace_q[at * A + k] = row[k];
+          p.trace_act[at] = best;
+        }
+        float nv[4], r;
+        bool term;
+        classic_dynamics(p.kind, st, best, nv, r, term);
+        ret += r;
+        len += 1;
+        if (term || len >= p.max_steps) {
+          p.returns[e] = ret;
+          p.lengths[e] = len;
+          p.ended[e] = term ? 1 : 2;
+          live = false;
+        } else {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            st[k] = nv[k];
+            if (k < obs) L.x[t * kVecMaxObs + k] = nv[k];
+          }
+        }
+      }
+      const bool any = __ballot(live) != 0ull;
+      if (t == 0) any_live = any;
+    }
+    __syncthreads();
+    if (!any_live) break;  // (uniform; the next write of any_live lies behind the forward's barriers)
   }
 }
 
@@ -438,9 +594,13 @@ void check_net(const VecNet& n, const char* who) {
     throw std::invalid_argument(std::string(who) + ": missing parameter tensor");
 }
 
+void check_env_kind(int kind, int obs) {
+  if (kind < 0 || kind > 1) throw std::invalid_argument("vec classic env: kind 0 (CartPole) / 1 (MountainCar)");
+  if (obs != (kind == 0 ? 4 : 2)) throw std::invalid_argument("vec classic env: obs must be 4 (CartPole) / 2");
+}
+
 void check_env(const VecEnv& V) {
-  if (V.kind < 0 || V.kind > 1) throw std::invalid_argument("vec classic env: kind 0 (CartPole) / 1 (MountainCar)");
-  if (V.obs != (V.kind == 0 ? 4 : 2)) throw std::invalid_argument("vec classic env: obs must be 4 (CartPole) / 2");
+  check_env_kind(V.kind, V.obs);
   if (V.E < 1 || V.F < 2 * V.E) throw std::invalid_argument("vec classic env: ring must hold >= 2 E rows");
   if (!V.state || !V.ring) throw std::invalid_argument("vec classic env: state / ring missing");
 }
@@ -467,6 +627,21 @@ void vec_act(const VecAct& a, hipStream_t s) {
   if (a.E < 1 || !a.ring || !a.hist || !a.eps || !a.q || !a.actions)
     throw std::invalid_argument("vec_act: E >= 1 with ring, hist, eps, q and actions");
   vec_act_k<<<(a.E + kRows - 1) / kRows, kThreads, 0, s>>>(a);
+  LAUNCH_CHECK();
+}
+
+void vec_rollout(const VecRollout& r, hipStream_t s) {
+  check_net(r.net, "vec_rollout");
+  check_env_kind(r.kind, r.obs);
+  if (r.net.obs != r.obs) throw std::invalid_argument("vec_rollout: the net's obs differs from the env's");
+  if (r.N < 1 || r.N > 1024) throw std::invalid_argument("vec_rollout: N must be in [1, 1024]");
+  if (r.max_steps < 1 || r.max_steps > 10000)
+    throw std::invalid_argument("vec_rollout: max_steps must be in [1, 10000]");
+  if (!r.returns || !r.lengths || !r.ended) throw std::invalid_argument("vec_rollout: returns, lengths and ended");
+  const int given = (r.trace_obs != nullptr) + (r.trace_q != nullptr) + (r.trace_act != nullptr);
+  if (given != 0 && given != 3) throw std::invalid_argument("vec_rollout: the trace is all three buffers or none");
+  if (given == 3 && r.trace_T < 1) throw std::invalid_argument("vec_rollout: trace_T >= 1 with a trace");
+  vec_rollout_k<<<(r.N + kRows - 1) / kRows, kThreads, 0, s>>>(r);
   LAUNCH_CHECK();
 }
 

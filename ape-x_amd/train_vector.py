@@ -12,7 +12,11 @@ synced every 2500, and ``model{t}.pth`` (the reference ``state_dict``) is writte
 ``--save-interval`` (5000) steps and at the last one.  One JSON line is printed per
 ``--log-interval`` steps (loss, grad norms, SGD and env steps per second, the actors' mean
 episode return) and, every ``--eval-interval`` steps, the greedy return of
-``--eval-episodes`` evaluation episodes.
+``--eval-episodes`` evaluation episodes.  ``--eval-mode``: ``step`` evaluates with the stepwise
+``evaluate()``; ``rollout`` with the one-launch ``rollout_evaluate()``; ``async`` launches the
+rollout on a weight snapshot beside training (:class:`VectorEvaluator`), syncs only the training
+stream at a log line, and reports a finished evaluation in the next record as
+``greedy_mean_return`` with ``greedy_step``, the step of its snapshot.
 """
 from __future__ import annotations
 
@@ -23,7 +27,10 @@ import time
 
 import torch
 
-from .engine.vector import VECTOR_ENVS, VectorApexEngine, VectorEngineConfig
+from .engine.vector import VECTOR_ENVS, VectorApexEngine, VectorEngineConfig, VectorEvaluator
+
+
+EVAL_MODES = ("step", "rollout", "async")
 
 
 def parser() -> argparse.ArgumentParser:
@@ -47,6 +54,9 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--log-interval", type=int, default=1000, help="steps between metric reads (host syncs)")
     p.add_argument("--eval-interval", type=int, default=0, help="steps between greedy evaluations (0 = off)")
     p.add_argument("--eval-episodes", type=int, default=10)
+    p.add_argument("--eval-mode", default="step", choices=EVAL_MODES,
+                   help="step: the stepwise evaluator; rollout: one vec_rollout launch; async: the rollout on a "
+                        "weight snapshot beside training, reported by the next log line")
     p.add_argument("--json-log", default=None, help="append one JSON record per log interval to this file")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--device", default="cuda:0")
@@ -71,6 +81,8 @@ def train(a) -> dict:
         raise RuntimeError("train_vector needs a GPU (the host-side trainer is apex_amd.trainers.apex_single)")
     eng = VectorApexEngine(cfg, a.device)
     eng.fill()
+    mode = a.eval_mode
+    asyn = VectorEvaluator(eng, a.eval_episodes) if mode == "async" and a.eval_interval > 0 else None
     if not a.no_graphs:
         eng.capture()
     jl = open(a.json_log, "a") if a.json_log else None
@@ -85,9 +97,20 @@ def train(a) -> dict:
             if t % a.save_interval == 0 or final:
                 eng.save(model_path(a.save_dir, t))
             ev = a.eval_interval > 0 and (t % a.eval_interval == 0 or final)
+            if ev and asyn is not None:
+                # snapshot + side-stream rollout; no log line and no sync of its own.  The last step's
+                # evaluation must run: wait out (and drop, they are superseded) earlier ones
+                launched = asyn.launch(tag=t)
+                while final and not launched:
+                    asyn.wait()
+                    launched = asyn.launch(tag=t)
+                ev = False
             if not (t % a.log_interval == 0 or final or ev):
                 continue
-            torch.cuda.synchronize(eng.device)
+            if asyn is not None:
+                torch.cuda.current_stream(eng.device).synchronize()  # the side stream keeps running
+            else:
+                torch.cuda.synchronize(eng.device)
             dt = max(time.perf_counter() - t_win, 1e-9)
             st = eng.learner.stats()
             ret, _, cnt = eng.shard.episode_stats()
@@ -99,8 +122,15 @@ def train(a) -> dict:
                     "episodes": int(cnt.sum().item()),
                     "actor_mean_return": float(ret[fresh].mean().item()) if bool(fresh.any()) else None}
             if ev:
-                g = eng.evaluate(a.eval_episodes)
+                g = eng.rollout_evaluate(a.eval_episodes) if mode == "rollout" else eng.evaluate(a.eval_episodes)
                 last["greedy_mean_return"] = sum(g) / len(g)
+            if asyn is not None:
+                res = None  # the newest evaluation that has landed (after the last step: the final one)
+                while (r := asyn.wait() if final else asyn.poll()) is not None:
+                    res = r
+                if res is not None:
+                    last["greedy_mean_return"] = sum(res["returns"]) / len(res["returns"])
+                    last["greedy_step"] = res["tag"]
             print(json.dumps(last), flush=True)
             if jl:
                 jl.write(json.dumps(last) + "\n")
