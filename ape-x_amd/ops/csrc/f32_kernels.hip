@@ -26,7 +26,11 @@
 //     chunks; LDS double buffer + register prefetch of the next k-block (one barrier per
 //     k-block; a sched_barrier pins the prefetch ahead of the MFMA block, otherwise the
 //     scheduler sinks late-needed loads next to their LDS store and exposes their latency);
-//     pitches padded so the fragment reads are bank-conflict free.
+//     pitches padded so the fragment reads are bank-conflict free.  The prefetch is a ring of
+//     D register stages (gemm_body<P, SS, D>, APEX_F32_PREFETCH): D = 2, 3 keep two or three
+//     k-blocks of loads in flight.  Every launch class runs D = 1: deeper rings measured
+//     slower or equal per launch and per step (profiles/r7_prefetch_ring.md) -- the waits of
+//     these GEMMs are not load latency.
 //   * k-chunk mapping: for a chunk of 8 k, lane (r = l & 31, h = l >> 5) holds elements
 //     k = 4h .. 4h+3 of its A row / B column (one ds_read_b128 when K-major, four ds_read_b32
 //     when MN-major); MFMA i of the chunk consumes element i of both -- the 32x32x2 MFMA's
@@ -52,8 +56,9 @@
 //    ds_read_b64_tr_b16 -- the hardware transpose -- for MN-major ones): 3-8 VALU per MFMA, one
 //    LDS image (the next k-block waits in registers) so the footprint stays at the fp32 form's.
 // The forward launches run the stage split (co-running with the actor's forward, they gain most
-// from the VALU they no longer issue); the backward pairs keep the register split (measured no
-// faster staged: profiles/r6_stage_split.md).
+// from the VALU they no longer issue), and so do the backward pairs since their input-gradient
+// halves moved to BK 32 tiles (profiles/r7_prefetch_ring.md; at BK 16 they measured no faster
+// staged: profiles/r6_stage_split.md).
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -284,7 +289,17 @@ __device__ __forceinline__ uint2 ds_tr16(const char* p) {
 // Every fp32 GEMM of the learner (gemm_body) on the bf16 matrix cores through split8: the
 // fp32-MFMA form (v_mfma_f32_32x32x2_f32) it replaced in round 5 ran 2142 vs 2378 learner
 // steps/s at the same fp32-class accuracy (profiles/r5_x6.md, tests/test_gpu_f32_net.py).
-template <class P, int SS>
+//
+// D = prefetch depth: a ring of D register stages.  The loads of k-block kb + D are issued
+// before compute(kb) and the LDS store after it takes k-block kb + 1, which has then had D - 1
+// whole iterations to land (D = 1: the one-block-ahead prefetch).  The k loop is unrolled by D so
+// every stage index is a compile-time constant (a runtime-indexed register array would live in
+// scratch).  For D > 1 the loads past the last k-block are issued unconditionally and never
+// stored -- a guarded prefetch makes the compiler drain with vmcnt(0): raw-buffer row loads may
+// run past the operand's range (zeros, or other bytes of the same operand), the other loaders
+// get the k-block index clamped to the last one.  Same k order, same staged values, same MFMA
+// k-slots at every depth: bit-identical results (tests/test_gpu_f32_prefetch.py).
+template <class P, int SS, int D>
 __device__ __forceinline__ void gemm_body(const typename P::Args& args, int block, float* lds,
                                           typename P::Smem& sm) {
   using G = Geo<P>;
@@ -304,8 +319,8 @@ __device__ __forceinline__ void gemm_body(const typename P::Args& args, int bloc
     for (int j = 0; j < G::TN; ++j)
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-  constexpr int NSET = 1;
-  f32x4 ra[NSET][G::NA], rb[NSET][G::NB];
+  static_assert(D >= 1 && D <= 3, "prefetch depth");
+  f32x4 ra[D][G::NA], rb[D][G::NB];
   f32x4 csum = zero4();
   typename RowAOf<P>::type rowa[G::NA];
   typename RowBOf<P>::type rowb[G::NB];
@@ -324,22 +339,24 @@ __device__ __forceinline__ void gemm_body(const typename P::Args& args, int bloc
     }
   }
 
-  auto gload = [&](int kb, auto S) {
+  auto gload = [&](int kbr, auto S) {
     constexpr int st = decltype(S)::value;
+    // pointer loaders (no raw-buffer range check): a k-block past the end reloads the last one
+    const int kbc = D > 1 ? min(kbr, ctx.kb1 - 1) : kbr;
 #pragma unroll
     for (int j = 0; j < G::NA; ++j) {
       const int q = t + 256 * j;
       if (G::CA % 256 == 0 || q < G::CA) {
-        if constexpr (HasRowA<P>::value) ra[st][j] = P::load_a_row(args, ctx, rowa[j], kb);
-        else ra[st][j] = P::load_a(args, ctx, sm, kb, q / G::RA, q % G::RA);
+        if constexpr (HasRowA<P>::value) ra[st][j] = P::load_a_row(args, ctx, rowa[j], kbr);
+        else ra[st][j] = P::load_a(args, ctx, sm, kbc, q / G::RA, q % G::RA);
       }
     }
 #pragma unroll
     for (int j = 0; j < G::NB; ++j) {
       const int q = t + 256 * j;
       if (G::CB % 256 == 0 || q < G::CB) {
-        if constexpr (HasRowB<P>::value) rb[st][j] = P::load_b_row(args, ctx, rowb[j], kb);
-        else rb[st][j] = P::load_b(args, ctx, sm, kb, q / G::RB, q % G::RB);
+        if constexpr (HasRowB<P>::value) rb[st][j] = P::load_b_row(args, ctx, rowb[j], kbr);
+        else rb[st][j] = P::load_b(args, ctx, sm, kbc, q / G::RB, q % G::RB);
       }
     }
   };
@@ -524,38 +541,95 @@ __device__ __forceinline__ void gemm_body(const typename P::Args& args, int bloc
     }
   };
 
+  using S1 = std::integral_constant<int, 1 % D>;
+  using S2 = std::integral_constant<int, 2 % D>;
   int kb = ctx.kb0;
   int cur = 0;
-  if (kb < ctx.kb1) {
+  if (kb < ctx.kb1) {  // block-uniform (a workgroup without k-blocks loads nothing)
     gload(kb, S0{});
+    if constexpr (D >= 2) gload(kb + 1, S1{});
+    if constexpr (D >= 3) gload(kb + 2, S2{});
     sstore(0, S0{});
   }
   __syncthreads();
-  if constexpr (SS == 2) {  // one LDS image (half the footprint): the next k-block waits in
-                            // registers and is stored after a second barrier
+  if constexpr (D == 1) {
+    if constexpr (SS == 2) {  // one LDS image (half the footprint): the next k-block waits in
+                              // registers and is stored after a second barrier
+      for (; kb < ctx.kb1; ++kb) {
+        const bool more = kb + 1 < ctx.kb1;
+        if (more) gload(kb + 1, S0{});
+        __builtin_amdgcn_sched_barrier(0);
+        compute(0);
+        if (more) {
+          __syncthreads();
+          sstore(0, S0{});
+        }
+        __syncthreads();
+      }
+    } else
     for (; kb < ctx.kb1; ++kb) {
       const bool more = kb + 1 < ctx.kb1;
       if (more) gload(kb + 1, S0{});
+      // every MFMA of the block is issued before the LDS store waits on the next block's
+      // global loads: unfenced, the scheduler sinks late-needed loads next to their store and
+      // exposes their latency
       __builtin_amdgcn_sched_barrier(0);
-      compute(0);
-      if (more) {
+      compute(cur);
+      if (more) sstore(cur ^ 1, S0{});
+      __syncthreads();
+      cur ^= 1;
+    }
+  } else {
+    // The ring loop has no exit and no condition inside an iteration of D k-blocks: it runs
+    // while all D stores of the iteration are needed, and the last 1..D k-blocks (already in
+    // LDS / in the stages, at compile-time indices: every iteration restores the ring's
+    // alignment) drain in a tail that loads nothing.  (With a skippable store or a mid-iteration
+    // exit the compiler guards the next overwrite of a stage with a near-full vmcnt drain at
+    // the head of every iteration.)
+    // one k-block: LDS holds kb; its MFMAs, then stage SN (k-block kb + 1) goes to LDS
+    auto mma = [&]() {
+      __builtin_amdgcn_sched_barrier(0);
+      compute(SS == 2 ? 0 : cur);
+    };
+    auto next = [&](auto SN) {
+      if constexpr (SS == 2) {
         __syncthreads();
-        sstore(0, S0{});
+        sstore(0, SN);
+      } else {
+        sstore(cur ^ 1, SN);
+        cur ^= 1;
       }
       __syncthreads();
+      ++kb;
+    };
+    if (kb < ctx.kb1) {
+      while (kb + D < ctx.kb1) {  // stage SL is free (stored an iteration ago) and takes kb + D
+        gload(kb + D, S0{});
+        mma();
+        next(S1{});
+        gload(kb + D, S1{});
+        mma();
+        next(S2{});
+        if constexpr (D >= 3) {
+          gload(kb + D, S2{});
+          mma();
+          next(S0{});
+        }
+      }
+      const int m = ctx.kb1 - kb;  // 1..D k-blocks left
+      mma();
+      if (m >= 2) {
+        next(S1{});
+        mma();
+        if constexpr (D >= 3) {
+          if (m >= 3) {
+            next(S2{});
+            mma();
+          }
+        }
+      }
+      __syncthreads();  // (the column-sum epilogue reuses the LDS tile)
     }
-  } else
-  for (; kb < ctx.kb1; ++kb) {
-    const bool more = kb + 1 < ctx.kb1;
-    if (more) gload(kb + 1, S0{});
-    // every MFMA of the block is issued before the LDS store waits on the next block's
-    // global loads: unfenced, the scheduler sinks late-needed loads next to their store and
-    // exposes their latency
-    __builtin_amdgcn_sched_barrier(0);
-    compute(cur);
-    if (more) sstore(cur ^ 1, S0{});
-    __syncthreads();
-    cur ^= 1;
   }
 #pragma unroll
   for (int mi = 0; mi < G::TM; ++mi)
@@ -605,20 +679,20 @@ struct BodyForm {
   static constexpr int value = SS == 3 ? 2 : SS;
 };
 
-template <class P, int SS>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SS == 3 ? 3 : 1))) void gemm_k(
+template <class P, int SS, int D>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SS == 3 || D > 1 ? 3 : 1))) void gemm_k(
     typename P::Args args) {
   __shared__ __attribute__((aligned(16))) float lds[LdsFloats<P, SS>::value];
   __shared__ typename P::Smem sm;
-  gemm_body<P, BodyForm<SS>::value>(args, xcd_chunk(blockIdx.x, gridDim.x), lds, sm);
+  gemm_body<P, BodyForm<SS>::value, D>(args, xcd_chunk(blockIdx.x, gridDim.x), lds, sm);
 }
 
 // Two independent GEMMs in one launch: blocks [0, n1) run P1, the rest P2 (P1 first: the
 // longer per-block problem starts early).
 // r (stage > 0): the learner's priority-tree write riding the launch as extra workgroups
 // (tree_dev.h tree_ride: the leaves in block 0, a level's recompute past the GEMM tiles).
-template <class P1, class P2, int SS>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SS == 3 ? 3 : 1))) void gemm2_k(
+template <class P1, class P2, int SS, int D>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SS == 3 || D > 1 ? 3 : 1))) void gemm2_k(
     typename P1::Args a1, typename P2::Args a2, int n1, TreeRide r) {
   __shared__ __attribute__((aligned(16))) float lds[MaxI<LdsFloats<P1, SS>::value, LdsFloats<P2, SS>::value>::value];
   __shared__ union {
@@ -628,9 +702,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SS == 3 ? 3
   int b = blockIdx.x;
   if (r.stage && tree_ride(r, r.nhost, lds, &b)) return;  // (grid-uniform stage, block-uniform role)
   if (b < n1)
-    gemm_body<P1, BodyForm<SS>::value>(a1, b, lds, sm.s1);
+    gemm_body<P1, BodyForm<SS>::value, D>(a1, b, lds, sm.s1);
   else
-    gemm_body<P2, BodyForm<SS>::value>(a2, b - n1, lds, sm.s2);
+    gemm_body<P2, BodyForm<SS>::value, D>(a2, b - n1, lds, sm.s2);
 }
 
 __device__ __forceinline__ F32Prob pick(const F32Set& s, int i) {
@@ -1480,8 +1554,11 @@ struct Conv3DgradPT {  // dy2[b][pi][ci] = (a2 > 0) * sum_{valid taps, co} dy3[b
   }
 };
 
-// BK 16 (half the LDS: more workgroups per CU beside the weight-gradient ones of the same
-// launch): conv3 backward 47.2 vs 50.0 us, conv2 65.3 vs 68.8 us at BK 32 (B = 512)
+// Under the register split BK 16 won (half the LDS: more workgroups per CU beside the
+// weight-gradient ones of the same launch: conv3 backward 47.2 vs 50.0 us, conv2 65.3 vs 68.8 us
+// at BK 32, B = 512).  On the stage-split single-image form the pairs run today both tiles fit 4
+// workgroups per CU and BK 32 halves the barriers: conv3 39.6 vs 42.7 us, conv2 53.1 vs 57.3 us,
+// whole step +2.5 % (profiles/r7_prefetch_ring.md): kBwdTileDefault.
 using Conv3DgradP = Conv3DgradPT<128, 32, 4, 16>;
 using Conv3DgradP32 = Conv3DgradPT<128, 32, 4, 32>;
 
@@ -1549,15 +1626,20 @@ struct Conv2DgradPT {
 using Conv2DgradP = Conv2DgradPT<16>;
 using Conv2DgradP32 = Conv2DgradPT<32>;
 
-// default: the forward GEMMs on the stage-split single-image form at >= 3 waves per SIMD (form
-// 3), the backward pairs on the register split.  Whole step, separate processes alternated on one
+// default: every learner GEMM on the stage-split single-image form at >= 3 waves per SIMD (form
+// 3).  Round 6 (the backward pairs' input gradients on BK 16 tiles) kept the backward pairs on
+// the register split: whole step, separate processes alternated on one
 // box (scripts/ab/apex_engine_ab.py, profiles/r6_stage_split.md): register split 2466, forward
 // form 2 2526.5, both directions form 2 2509; another box: register split 2434, forward form 2
 // 2478, forward form 3 2489 steps/s.  The backward pairs gain nothing (backward-only form 2:
 // 2341 vs 2345): their wgrad halves' LDS and the MN-major transposed reads eat the VALU saved.
 // The actor's small forward launches (256 envs, beside the learner's forward) on the register
 // split: 2497 vs 2489 (both rounds of an alternated A/B).
-constexpr int kStageSplitDefault = 3 + 16 * (0 + 1);  // (+ the actor's small launches on form 0)
+// Round 7 (profiles/r7_prefetch_ring.md): the backward pairs on form 3 WITH the BK 32
+// input-gradient tiles 2658 vs 2594 steps/s for the register split + BK 16 (form 3 + BK 16: 2555
+// vs 2560, the round-6 finding; register split + BK 32: 2566 vs 2594).
+constexpr int kStageSplitDefault = 3 + 4 * 3 + 16 * (0 + 1);  // (+ the actor's small launches on form 0)
+constexpr int kBwdTileDefault = 1;  // conv2 / conv3 input gradient: 1 = BK 32, 2 = BK 16
 
 // wgrad split sizing: ~target blocks over (n-tiles x splits)
 struct SplitPlan {
@@ -1599,20 +1681,55 @@ int stage_split_mask() {
   return g_stage_split;
 }
 
+// Prefetch depth of the GEMM bodies per launch class, read at launch time (a captured graph
+// keeps the depth it was captured with): mask = (D - 1) of the learner-sized forward launches
+// + 4 x (D - 1) of the backward pairs + 16 x (D - 1) of the forward launches below the learner's
+// size (the actor's / evaluator's), D = 1..3.  Every depth gives bit-identical results.
+constexpr int kPrefetchDefault = 0;
+int g_prefetch = -1;
+int prefetch_mask() {
+  if (g_prefetch < 0) {
+    const char* e = std::getenv("APEX_F32_PREFETCH");
+    g_prefetch = e ? std::atoi(e) : kPrefetchDefault;
+  }
+  return g_prefetch;
+}
+// cls: 0 = learner-sized forward, 1 = backward pair, 2 = small forward
+int prefetch_depth(int cls) { return std::min(3, 1 + ((prefetch_mask() >> (2 * cls)) & 3)); }
+
 // small: a launch below the learner's size (the actor's / evaluator's forward) -- bits 4-5 of the
 // mask, when set, give those launches a form of their own (form + 1; 0 = the forward form)
+template <class P, int D>
+void launch1_d(const typename P::Args& a, int blocks, hipStream_t s, int form) {
+  switch (form) {
+    case 1: gemm_k<P, 1, D><<<blocks, 256, 0, s>>>(a); break;
+    case 2: gemm_k<P, 2, D><<<blocks, 256, 0, s>>>(a); break;
+    case 3: gemm_k<P, 3, D><<<blocks, 256, 0, s>>>(a); break;
+    default: gemm_k<P, 0, D><<<blocks, 256, 0, s>>>(a);
+  }
+}
 template <class P>
 void launch1(const typename P::Args& a, int blocks, hipStream_t s, bool small = false) {
   if (blocks <= 0) return;
   const int m = stage_split_mask();
   const int form = small && ((m >> 4) & 3) ? ((m >> 4) & 3) - 1 : m & 3;
-  switch (form) {
-    case 1: gemm_k<P, 1><<<blocks, 256, 0, s>>>(a); break;
-    case 2: gemm_k<P, 2><<<blocks, 256, 0, s>>>(a); break;
-    case 3: gemm_k<P, 3><<<blocks, 256, 0, s>>>(a); break;
-    default: gemm_k<P, 0><<<blocks, 256, 0, s>>>(a);
+  switch (prefetch_depth(small ? 2 : 0)) {
+    case 2: launch1_d<P, 2>(a, blocks, s, form); break;
+    case 3: launch1_d<P, 3>(a, blocks, s, form); break;
+    default: launch1_d<P, 1>(a, blocks, s, form);
   }
   LAUNCH_CHECK();
+}
+
+template <class P1, class P2, int D>
+void launch2_d(const typename P1::Args& a1, const typename P2::Args& a2, int n1, int nb, const TreeRide& r,
+               hipStream_t s) {
+  switch ((stage_split_mask() >> 2) & 3) {
+    case 1: gemm2_k<P1, P2, 1, D><<<nb, 256, 0, s>>>(a1, a2, n1, r); break;
+    case 2: gemm2_k<P1, P2, 2, D><<<nb, 256, 0, s>>>(a1, a2, n1, r); break;
+    case 3: gemm2_k<P1, P2, 3, D><<<nb, 256, 0, s>>>(a1, a2, n1, r); break;
+    default: gemm2_k<P1, P2, 0, D><<<nb, 256, 0, s>>>(a1, a2, n1, r);
+  }
 }
 
 template <class P1, class P2>
@@ -1625,11 +1742,10 @@ void launch2(const typename P1::Args& a1, int n1, const typename P2::Args& a2, i
     r.nhost = n1 + n2;
   }
   const int nb = n1 + n2 + tree_ride_blocks(r);
-  switch ((stage_split_mask() >> 2) & 3) {
-    case 1: gemm2_k<P1, P2, 1><<<nb, 256, 0, s>>>(a1, a2, n1, r); break;
-    case 2: gemm2_k<P1, P2, 2><<<nb, 256, 0, s>>>(a1, a2, n1, r); break;
-    case 3: gemm2_k<P1, P2, 3><<<nb, 256, 0, s>>>(a1, a2, n1, r); break;
-    default: gemm2_k<P1, P2, 0><<<nb, 256, 0, s>>>(a1, a2, n1, r);
+  switch (prefetch_depth(1)) {
+    case 2: launch2_d<P1, P2, 2>(a1, a2, n1, nb, r, s); break;
+    case 3: launch2_d<P1, P2, 3>(a1, a2, n1, nb, r, s); break;
+    default: launch2_d<P1, P2, 1>(a1, a2, n1, nb, r, s);
   }
   LAUNCH_CHECK();
 }
@@ -1650,6 +1766,8 @@ void fwd_launch(const F32Set& set, hipStream_t s) {
 
 void f32_set_stage_split(int mask) { g_stage_split = mask; }
 int f32_stage_split() { return stage_split_mask(); }
+void f32_set_prefetch(int mask) { g_prefetch = mask; }
+int f32_prefetch() { return prefetch_mask(); }
 
 // ------------------------------------------------------------------ host launchers
 // Tiles (MI355X, measured): the learner's launches (2-3 passes of its batch: >= 1024 rows) on
@@ -1810,6 +1928,13 @@ void f32_conv_bwd(int layer, const void* x, const int* ids, const int* idx, cons
     const char* e = std::getenv("APEX_F32_BWD_HALF");
     return e ? std::atoi(e) : 0;
   }();
+  // tile 0: the default input-gradient tile, or APEX_F32_BWD_TILE (a whole-step A/B knob, read once)
+  static const int bwd_tile = [] {
+    const char* e = std::getenv("APEX_F32_BWD_TILE");
+    const int t = e ? std::atoi(e) : 0;
+    return t == 1 || t == 2 ? t : kBwdTileDefault;
+  }();
+  if (tile == 0) tile = bwd_tile;
   if (halves && layer != 1) {
     const int nw = (layer == 2 ? 512 / 64 : 576 / 64) * p.splits;
     const int nd = layer == 2 ? Conv2DgradP::tiles(B) : Conv3DgradP::tiles(B);
@@ -1818,7 +1943,7 @@ void f32_conv_bwd(int layer, const void* x, const int* ids, const int* idx, cons
     return;
   }
   switch (layer) {
-    case 3:  // tile 1: input gradient at BK 32 (the alternative to the default)
+    case 3:  // tile 1: input gradient at BK 32, 2: at BK 16
       if (tile == 1) launch2<ConvWgrad<3>, Conv3DgradP32>(g, (576 / 64) * p.splits, d, Conv3DgradP32::tiles(B), s, ride);
       else launch2<ConvWgrad<3>, Conv3DgradP>(g, (576 / 64) * p.splits, d, Conv3DgradP::tiles(B), s, ride);
       break;

@@ -536,6 +536,8 @@ PYBIND11_MODULE(_apex_hip, m) {
   m.def("f32_fc1_splits", &f32_fc1_splits);
   m.def("f32_set_stage_split", &f32_set_stage_split);
   m.def("f32_stage_split", &f32_stage_split);
+  m.def("f32_set_prefetch", &f32_set_prefetch);
+  m.def("f32_prefetch", &f32_prefetch);
   m.def("f32_fc1_bwd_split", [](uint64_t dz, uint64_t a3, uint64_t wfc1p, uint64_t dy3, uint64_t ws, int B,
                                 uint64_t s, py::object ride) {
     f32_fc1_bwd_split(P<const float>(dz), P<const float>(a3), P<const float>(wfc1p), P<float>(dy3), P<float>(ws), B,
@@ -549,6 +551,7 @@ PYBIND11_MODULE(_apex_hip, m) {
     return f32_fc1_finalize_job(half, G, P<const float>(ws), P<float>(grad));
   });
   m.def("f32_wgrad_splits", &f32_wgrad_splits, py::arg("layer"), py::arg("B"), py::arg("target") = 0);
+  m.def("f32_wgrad_kbps", &f32_wgrad_kbps, py::arg("layer"), py::arg("B"), py::arg("target") = 0);
   m.def("f32_wgrad_workspace_floats", &f32_wgrad_workspace_floats, py::arg("layer"), py::arg("B"),
         py::arg("target") = 0);
   m.def("f32_conv_bwd", [](int layer, uint64_t x, uint64_t ids, uint64_t idx, uint64_t dy, uint64_t w, uint64_t mask,

@@ -421,6 +421,12 @@ int f32_fc1_splits();
 // launch (graphs keep the form they captured).
 void f32_set_stage_split(int mask);
 int f32_stage_split();
+// GEMM prefetch depth D = 1..3 (k-blocks of operand loads in flight per workgroup): mask =
+// (D - 1) of the learner-sized forward launches + 4 x (D - 1) of the backward pairs + 16 x
+// (D - 1) of the forward launches below the learner's size; unset reads APEX_F32_PREFETCH.
+// Bit-identical at every depth; read at launch (graphs keep the depth they captured).
+void f32_set_prefetch(int mask);
+int f32_prefetch();
 int f32_fc1_fwd_multi(const F32Set& set, hipStream_t s);  // returns the slab count
 // target: conv2 / conv3 weight-gradient workgroups (<= 0: the default); the workspace, the
 // launch and the finalize job of one gradient must use the same value

@@ -7,6 +7,8 @@ as one JSON line.
 A variant is a comma-separated list of overrides ('-' = the defaults):
   ss=MASK        APEX_F32_STAGE_SPLIT: f32 GEMM forms, forward + 4 x backward pairs
                  (0 register split, 1 stage-split, 2 stage-split single LDS image, 3 = 2 at >= 3 waves/SIMD)
+  pf=MASK        APEX_F32_PREFETCH: f32 GEMM prefetch depth D, (D - 1) of the learner's forward
+                 + 4 x (D - 1) of the backward pairs + 16 x (D - 1) of the actor's small launches
   env:NAME=VAL   any other environment variable
   arg:--flag[=VAL]  a bench.py flag (e.g. arg:--actor-at=loss)
 e.g. ``python scripts/ab/apex_engine_ab.py - ss=4 ss=8 ss=8,arg:--actor-at=loss``.
@@ -32,6 +34,8 @@ def run(variant: str, steps: int, warmup: int, timeout: float) -> float:
     for item in ([] if variant == "-" else variant.split(",")):
         if item.startswith("ss="):
             env["APEX_F32_STAGE_SPLIT"] = item[3:]
+        elif item.startswith("pf="):
+            env["APEX_F32_PREFETCH"] = item[3:]
         elif item.startswith("env:"):
             k, v = item[4:].split("=", 1)
             env[k] = v

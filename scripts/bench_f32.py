@@ -6,7 +6,9 @@ three-term split; the percentage is of the 157.3 TF fp32 MFMA peak, for comparis
 
 ``python scripts/bench_f32.py [--B 512] [--iters 50] [--only NAME] [--graph 1]`` prints
 us/launch and achieved TFLOP/s (157.3 TF = fp32 MFMA peak); ``--graph 0`` launches
-eagerly (for rocprofv3 --pmc, one dispatch per launch)."""
+eagerly (for rocprofv3 --pmc, one dispatch per launch).  ``--prefetch D`` runs every GEMM at
+prefetch depth D (1..3 k-blocks of operand loads in flight), ``--stage-split MASK`` in the
+given GEMM forms (APEX_F32_STAGE_SPLIT's mask)."""
 import argparse
 import json
 import os
@@ -28,15 +30,22 @@ ap.add_argument("--json", action="store_true")
 ap.add_argument("--rounds", type=int, default=1, help="time every case this many times, round-robin; report the median")
 ap.add_argument("--c1-wgrad-s1", action="store_true", help="+ conv1 weight gradient at one sample per workgroup")
 ap.add_argument("--tile1", action="store_true", help="+ the alternative tiles: conv2 forward 64x64, "
-                                                   "conv2/conv3 input gradient BK 32")
+                                                   "conv2/conv3 input gradient BK 16 (@t2)")
 ap.add_argument("--tile2", action="store_true", help="+ forward tiles: conv2 128x64 as 4x1 waves (32x64 each), "
                                                    "conv3 128x64 (2x2 waves) and 128x32 (4x1)")
 ap.add_argument("--c1-grids", default="", help="extra conv1 forward cases at these workgroup counts")
 ap.add_argument("--wgrad-targets", default="", help="extra conv2/conv3 backward cases at these wgrad workgroup "
                                                     "targets, e.g. 512,1024 (default plan: the plain cases)")
+ap.add_argument("--prefetch", type=int, default=0, choices=[0, 1, 2, 3],
+                help="GEMM prefetch depth of every launch class (0: the defaults / APEX_F32_PREFETCH)")
+ap.add_argument("--stage-split", type=int, default=-1, help="GEMM form mask (-1: the defaults)")
 a = ap.parse_args()
 dev = torch.device("cuda")
 hip = ops.hip()
+if a.prefetch:
+    hip.f32_set_prefetch((a.prefetch - 1) * (1 + 4 + 16))
+if a.stage_split >= 0:
+    hip.f32_set_stage_split(a.stage_split)
 B, A = a.B, 18
 m = DuelingDQN.from_shapes((4, 84, 84), A).to(dev)
 m.flatten_parameters()
@@ -121,12 +130,12 @@ if a.c1_wgrad_s1:  # conv1 weight gradient, one sample per workgroup (+ its fina
         1, B, w1.data_ptr(), f[0].weight.grad.data_ptr(), f[0].bias.grad.data_ptr())], S(), 0)), 1)
 if a.tile1:
     cases["conv2_fwd@t1"] = ((lambda: hip.f32_conv_fwd_multi(2, set3(2), B, S(), tile=1)), 2 * P * 81 * 64 * 512)
-    cases["conv3_bwd@t1"] = ((lambda: hip.f32_conv_bwd(3, ws.a2.data_ptr(), 0, 0, ws.dy3.data_ptr(), net.w3t.data_ptr(),
+    cases["conv3_bwd@t2"] = ((lambda: hip.f32_conv_bwd(3, ws.a2.data_ptr(), 0, 0, ws.dy3.data_ptr(), net.w3t.data_ptr(),
                                                        ws.a2.data_ptr(), ws.dy2.data_ptr(), w3.data_ptr(), B, S(),
-                                                       tile=1)), 2 * 2 * B * 49 * 64 * 576)
-    cases["conv2_bwd@t1"] = ((lambda: hip.f32_conv_bwd(2, ws.a1.data_ptr(), 0, 0, ws.dy2.data_ptr(), net.w2t.data_ptr(),
+                                                       tile=2)), 2 * 2 * B * 49 * 64 * 576)
+    cases["conv2_bwd@t2"] = ((lambda: hip.f32_conv_bwd(2, ws.a1.data_ptr(), 0, 0, ws.dy2.data_ptr(), net.w2t.data_ptr(),
                                                        ws.a1.data_ptr(), ws.dy1.data_ptr(), w2.data_ptr(), B, S(),
-                                                       tile=1)), 2 * 2 * B * 81 * 64 * 512)
+                                                       tile=2)), 2 * 2 * B * 81 * 64 * 512)
 if a.tile2:
     cases["conv2_fwd@t2"] = ((lambda: hip.f32_conv_fwd_multi(2, set3(2), B, S(), tile=2)), 2 * P * 81 * 64 * 512)
     cases["conv3_fwd@t2"] = ((lambda: hip.f32_conv_fwd_multi(3, set3(3), B, S(), tile=2)), 2 * P * 49 * 64 * 576)
