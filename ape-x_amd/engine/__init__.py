@@ -1,3 +1,4 @@
 """GPU-resident Ape-X engine (one rank = actor shard + HBM replay + learner)."""
+from .dqn import DQNEngineConfig, DQNFrameEngine  # noqa: F401
 from .vector import (VECTOR_ENVS, MLPDQNLearner, VectorActorShard, VectorApexEngine,  # noqa: F401
                      VectorEngineConfig, VectorEvaluator)

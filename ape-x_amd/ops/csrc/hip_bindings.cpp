@@ -959,6 +959,27 @@ PYBIND11_MODULE(_apex_hip, m) {
                   P<const int64_t>(counter), P<float>(q), P<int>(actions)};
   });
   m.def("vec_act", [](const VecAct& a, uint64_t s) { vec_act(a, S(s)); });
+  py::class_<DqnFrame>(m, "DqnFrame");
+  // d: act_seed, hist, t, eps_start, eps_final, eps_decay, beta0, beta_horizon, eps_out, beta_out, q, actions,
+  //    reward, done, new_frame, [ep_log], C, filled, slot, max_prio, alpha; tt: the replay tables
+  m.def("make_dqn_frame", [](const VecNet& net, const VecEnv& env, const TreeHandle& tree, py::dict tt, py::dict d) {
+    auto g = [&](const char* k) { return d[k].cast<uint64_t>(); };
+    auto f64 = [&](const char* k) { return d[k].cast<double>(); };
+    DqnFrame f{};
+    f.net = net; f.env = env; f.tree = tree.d; f.tt = trans_table(tt);
+    f.act_seed = g("act_seed");
+    f.hist = P<int>(g("hist")); f.t = P<int64_t>(g("t"));
+    f.eps_start = f64("eps_start"); f.eps_final = f64("eps_final"); f.eps_decay = f64("eps_decay");
+    f.beta0 = f64("beta0"); f.beta_horizon = f64("beta_horizon");
+    f.eps_out = P<float>(g("eps_out")); f.beta_out = P<float>(g("beta_out"));
+    f.q = P<float>(g("q")); f.actions = P<int>(g("actions"));
+    f.reward = P<float>(g("reward")); f.done = P<float>(g("done")); f.new_frame = P<int>(g("new_frame"));
+    f.ep_log = P<float>(d.contains("ep_log") ? g("ep_log") : (uint64_t)0);
+    f.C = d["C"].cast<int>(); f.filled = P<int64_t>(g("filled")); f.slot = P<int>(g("slot"));
+    f.max_prio = P<const float>(g("max_prio")); f.alpha = d["alpha"].cast<float>();
+    return f;
+  });
+  m.def("dqn_frame", [](const DqnFrame& f, uint64_t s) { dqn_frame(f, S(s)); });
   py::class_<VecRollout>(m, "VecRollout");
   // d: kind, N, obs, max_steps, seed, returns, lengths, ended [+ trace_obs, trace_q, trace_act, trace_T]
   m.def("make_vec_rollout", [](const VecNet& net, py::dict d) {

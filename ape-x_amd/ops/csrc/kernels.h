@@ -753,6 +753,35 @@ struct VecGrad {
 int64_t vec_param_count(int obs, int A);
 int vec_grad_blocks(int64_t n);
 void vec_grad(const VecGrad& g, hipStream_t s);
+// The actor side of one frame of the single-process prioritized DQN (reference DQN.py) in ONE
+// launch of one workgroup, E <= 8 envs: epsilon(t) / beta(t) in fp64, vec_act's forward and
+// draw on the online net, vec_classic_step's env step, frame_hist_step's FrameStack advance,
+// the transition of env e into replay slot (filled + e) mod C, its leaf at max_prio^alpha with
+// every level of its path, then filled += E and t += 1.  max_prio is read, never written.
+struct DqnFrame {
+  VecNet net;              // the online net (acted on in place: no published copy)
+  VecEnv env;
+  uint64_t act_seed;       // Philox key (act_seed, e), counter t: vec_act's draw
+  int* hist;               // [E][4]
+  int64_t* t;              // frame counter
+  double eps_start, eps_final, eps_decay;   // eps(t) = final + (start - final) exp(-t / decay)
+  double beta0, beta_horizon;               // beta(t) = min(1, beta0 + t (1 - beta0) / horizon)
+  float* eps_out;          // [1]
+  float* beta_out;         // [1] per_sample's beta_ptr
+  float* q;                // [E][A]
+  int* actions;            // [E]
+  float *reward, *done;    // [E]
+  int* new_frame;          // [E]
+  float* ep_log;           // [E][4] or null
+  TransTable tt;           // replay tables [C]
+  int C;
+  int64_t* filled;
+  int* slot;               // [E] out: the replay slots written
+  TreeDesc tree;
+  const float* max_prio;
+  float alpha;
+};
+void dqn_frame(const DqnFrame& f, hipStream_t s);
 
 // ---- central-replay experience transport over HIP IPC (ipc_kernels.hip, parallel/ipc.py)
 struct IpcIngest {

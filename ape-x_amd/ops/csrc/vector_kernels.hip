@@ -13,6 +13,9 @@
 //                                         envs/classic.py in fp32)
 //   vec_act      one workgroup per 8 envs: both heads' 128x128 weights staged (transposed) in LDS,
 //                Q[E, A], then select_actions_k's draw in the same launch
+//   dqn_frame    one workgroup, <= 8 envs: the actor side of one DQN.py frame (eps(t) / beta(t), vec_act's
+//                forward and draw on the online net, the env step, the FrameStack advance, the replay
+//                insert at the running max priority and its tree walk) in one launch (engine/dqn.py)
 //   vec_rollout  one workgroup per 8 greedy episodes, reset to first done in one launch: heads staged
 //                once, then forward / first argmax / env dynamics per step, no ring and no host
 //   vec_learn    one workgroup per 4 sampled rows: target net on (s, s'), online net on (s, s'),
@@ -23,12 +26,13 @@
 //                sum-of-squares partial per workgroup in grad_sumsq's format
 #include "common.h"
 #include "kernels.h"
+#include "tree_dev.h"
 
 namespace apex {
 
 namespace {
 
-constexpr int kH = kVecHidden;          // 128
+constexpr int kH = kVecHidden;         // 128
 constexpr int kRows = 8;                // rows per forward pass of a workgroup
 constexpr int kWPitch = kH + 1;         // transposed weight image [k][j], padded: conflict-free both ways
 constexpr int kWHead = kH * kWPitch;    // floats per head image
@@ -98,14 +102,13 @@ __global__ void vec_classic_reset_k(VecEnv V, const int64_t* step_counter, int* 
   if (ep_log) for (int c = 0; c < 4; ++c) ep_log[e * 4 + c] = 0.f;
 }
 
-__global__ void vec_classic_step_k(VecEnv V, const int* __restrict__ actions, const int64_t* step_counter,
-                                   float* reward, float* done, int* new_frame, float* ep_log) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= V.E) return;
-  const int64_t step = step_counter ? step_counter[0] : 0;
+// Env e's step at counter `step` with action a: dynamics, TimeLimit, episode log, the reset draw
+// on done, the new observation into its ring row.  Shared by vec_classic_step_k and dqn_frame_k,
+// so both step bit for bit alike.
+__device__ __forceinline__ void classic_env_step(const VecEnv& V, int e, int64_t step, int a, float* reward,
+                                                 float* done, int* new_frame, float* ep_log) {
   const int slot = (int)(((int64_t)(step + 1) * V.E + e) % V.F);
   float* gst = V.state + (size_t)e * vecs::STRIDE;
-  const int a = actions[e];
   float nv[4];
   float r;
   bool term;
@@ -135,6 +138,13 @@ __global__ void vec_classic_step_k(VecEnv V, const int* __restrict__ actions, co
   for (int k = 0; k < 4; ++k) gst[k] = nv[k];
   for (int k = 0; k < V.obs; ++k) V.ring[(size_t)slot * V.obs + k] = nv[k];
   new_frame[e] = slot;
+}
+
+__global__ void vec_classic_step_k(VecEnv V, const int* __restrict__ actions, const int64_t* step_counter,
+                                   float* reward, float* done, int* new_frame, float* ep_log) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= V.E) return;
+  classic_env_step(V, e, step_counter ? step_counter[0] : 0, actions[e], reward, done, new_frame, ep_log);
 }
 
 // ------------------------------------------------------------------ MLP dueling forward
@@ -285,6 +295,76 @@ __global__ __launch_bounds__(kThreads) void vec_act_k(VecAct a) {
       best = r < A ? r : A - 1;
     }
     a.actions[e] = best;
+  }
+}
+
+// ------------------------------------------------------------------ one DQN.py frame
+// The actor side of one frame of the single-process prioritized DQN in one workgroup: schedules,
+// vec_act_k's forward and draw, the env step, the FrameStack advance, the replay insert at the
+// running max priority and the tree walk.  Threads 0..E-1 each own one env after the forward.
+// The tree walk (update_levels_block) needs no LDS beyond the E slots: the head image stays.
+__global__ __launch_bounds__(kThreads) void dqn_frame_k(DqnFrame f) {
+  __shared__ FwdLds L;
+  __shared__ int sids[kRows];
+  const int t = threadIdx.x;
+  const int E = f.env.E;
+  // both counters are read by every thread here and advanced by thread 0 behind the last barrier
+  const int64_t step = f.t[0];
+  const int64_t filled = f.filled[0];
+  if (t < kRows * kVecMaxObs) {
+    const int r = t / kVecMaxObs, k = t % kVecMaxObs;
+    const int e = min(r, E - 1);  // rows past E repeat the last env (never written), as vec_act_k
+    L.x[t] = k < f.net.obs ? f.env.ring[(size_t)f.hist[e * 4 + 3] * f.net.obs + k] : 0.f;
+  }
+  // eps(t), beta(t) in fp64, rounded to fp32 once (algo/schedules.py)
+  const double st = (double)step;
+  const float eps = (float)(f.eps_final + (f.eps_start - f.eps_final) * exp(-st / f.eps_decay));
+  if (t == 0) {
+    f.eps_out[0] = eps;
+    f.beta_out[0] = (float)fmin(1.0, f.beta0 + st * (1.0 - f.beta0) / f.beta_horizon);
+  }
+  stage_heads(f.net, L.W);
+  vec_forward(f.net, L);
+  if (t < E) {
+    const int e = t, A = f.net.A;
+    const float* row = L.q + t * 8;
+    // vec_act_k's draw: first argmax; explore iff !(u0 > eps); min(int(u1 A), A - 1)
+    int best = 0;
+    float bv = row[0];
+    for (int k = 1; k < A; ++k)
+      if (row[k] > bv) { bv = row[k]; best = k; }
+    for (int k = 0; k < A; ++k) f.q[(size_t)e * A + k] = row[k];
+    float u[4];
+    uniform4(f.act_seed, (uint64_t)e, (uint64_t)step, u);
+    if (!(u[0] > eps)) {
+      const int r = (int)(u[1] * (float)A);
+      best = r < A ? r : A - 1;
+    }
+    f.actions[e] = best;
+    classic_env_step(f.env, e, step, best, f.reward, f.done, f.new_frame, f.ep_log);
+    // FrameStack advance (frame_hist_step_k) and the transition (hist before, a, r, hist after, done)
+    int4* hp = reinterpret_cast<int4*>(f.hist) + e;
+    const int4 h0 = *hp;
+    const int nf = f.new_frame[e];
+    const float d = f.done[e];
+    const int4 h1 = d > 0.f ? make_int4(nf, nf, nf, nf) : make_int4(h0.y, h0.z, h0.w, nf);
+    *hp = h1;
+    if (d > 0.f && f.ep_log) f.ep_log[e * 4 + 3] += f.ep_log[e * 4 + 0];  // sum of finished returns
+    const int j = (int)((filled + e) % f.C);
+    reinterpret_cast<int4*>(f.tt.s_ids)[j] = h0;
+    reinterpret_cast<int4*>(f.tt.s2_ids)[j] = h1;
+    f.tt.action[j] = best;
+    f.tt.reward[j] = f.reward[e];
+    f.tt.done[j] = d;
+    // insert at the running max priority (write_leaf's "no priority given"); max_prio stays
+    write_leaf(f.tree, j, f.max_prio[0], f.alpha);
+    sids[e] = j;
+    f.slot[e] = j;
+  }
+  update_levels_block(f.tree, sids, E, 1, f.tree.levels);  // (each level begins with a barrier)
+  if (t == 0) {
+    f.filled[0] = filled + E;
+    f.t[0] = step + 1;
   }
 }
 
@@ -627,6 +707,23 @@ void vec_act(const VecAct& a, hipStream_t s) {
   if (a.E < 1 || !a.ring || !a.hist || !a.eps || !a.q || !a.actions)
     throw std::invalid_argument("vec_act: E >= 1 with ring, hist, eps, q and actions");
   vec_act_k<<<(a.E + kRows - 1) / kRows, kThreads, 0, s>>>(a);
+  LAUNCH_CHECK();
+}
+
+void dqn_frame(const DqnFrame& f, hipStream_t s) {
+  check_net(f.net, "dqn_frame");
+  check_env(f.env);
+  if (f.net.obs != f.env.obs) throw std::invalid_argument("dqn_frame: the net's obs differs from the env's");
+  if (f.env.E > kRows) throw std::invalid_argument("dqn_frame: at most 8 envs (one forward pass of a workgroup)");
+  if (f.C < f.env.E || f.tree.size[0] != f.C || f.tree.levels < 1 || !f.tree.leaf_sum || !f.tree.leaf_min)
+    throw std::invalid_argument("dqn_frame: the tree must have one leaf per replay slot, capacity >= E");
+  if (!f.hist || !f.t || !f.eps_out || !f.beta_out || !f.q || !f.actions || !f.reward || !f.done || !f.new_frame ||
+      !f.filled || !f.slot || !f.max_prio || !f.tt.s_ids || !f.tt.s2_ids || !f.tt.action || !f.tt.reward ||
+      !f.tt.done)
+    throw std::invalid_argument("dqn_frame: missing buffer");
+  if (!(f.eps_decay > 0.0) || !(f.beta_horizon > 0.0))
+    throw std::invalid_argument("dqn_frame: epsilon decay and beta horizon must be > 0");
+  dqn_frame_k<<<1, kThreads, 0, s>>>(f);
   LAUNCH_CHECK();
 }
 

@@ -14,6 +14,9 @@ BASELINE config 1: CartPole on CPU.  Semantics kept from the reference:
 
 ``python -m apex_amd.trainers.dqn --env CartPole-v0 --max-step 100000`` (or
 ``--eval N`` to play a saved checkpoint greedily, the reference's ``training=False``).
+``--engine gpu`` runs the same loop device-resident on
+:class:`apex_amd.engine.dqn.DQNFrameEngine` (GPU env, six launches per frame); without a GPU it
+raises ``RuntimeError(GPU_ENGINE_ERROR)``.
 """
 from __future__ import annotations
 
@@ -154,6 +157,49 @@ class train_DQN:  # noqa: N801  (reference class name)
         return returns
 
 
+GPU_ENGINE_ERROR = "--engine gpu needs a ROCm GPU (torch.cuda.is_available() is False); use --engine host"
+
+
+def train_gpu(a) -> list[dict]:
+    """``--engine gpu``: the same loop on :class:`apex_amd.engine.dqn.DQNFrameEngine` (same
+    flags, same ``model{t}.pth`` artefacts).  One JSON line per ``--log-interval`` frames; the
+    records are returned."""
+    import json
+    import time
+
+    if not torch.cuda.is_available():
+        raise RuntimeError(GPU_ENGINE_ERROR)
+    from ..engine.dqn import DQNEngineConfig, DQNFrameEngine
+
+    max_step, save_interval = int(a.max_step), int(a.save_interval)
+    log_interval = max(1, int(a.log_interval))
+    cfg = DQNEngineConfig(env_id=a.env, batch_size=a.batch_size, seed=0 if a.seed is None else a.seed)
+    eng = DQNFrameEngine(cfg, a.device if a.device is not None else "cuda:0")
+    os.makedirs(a.save_dir, exist_ok=True)
+    records = []
+    episodes, ret_sum, t_win, f_win = 0, 0.0, time.perf_counter(), 0
+    for t in range(max_step):
+        if eng._graph is None and t == eng.first_learning_frame + 1 and max_step > t + 8:
+            eng.capture(warmup_iters=0)   # (the frames so far were the warm-up)
+        eng.frame()
+        if t % save_interval == 0 or t == max_step - 1:
+            eng.save(os.path.join(a.save_dir, f"model{t}.pth"))
+        ev = a.eval_interval and (t + 1) % a.eval_interval == 0
+        if (t + 1) % log_interval == 0 or t == max_step - 1 or ev:
+            st = eng.stats()   # (syncs)
+            now = time.perf_counter()
+            n_ep = st["episodes"] - episodes
+            rec = {"frame": t, "loss": st["loss"] if eng.learn_steps else None, "lr": st["lr"], "eps": st["eps"],
+                   "frames_per_s": (t + 1 - f_win) / max(now - t_win, 1e-9), "episodes": st["episodes"],
+                   "mean_return": (st["return_sum"] - ret_sum) / n_ep if n_ep else None}
+            if ev:
+                rec["eval_return"] = float(np.mean(eng.rollout_evaluate(10)))
+            print(json.dumps(rec), flush=True)
+            records.append(rec)
+            episodes, ret_sum, t_win, f_win = st["episodes"], st["return_sum"], time.perf_counter(), t + 1
+    return records
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description="Prioritized double-DQN (DQN.py)")
     p.add_argument("--env", default="CartPole-v0")
@@ -164,7 +210,15 @@ def main(argv=None):
     p.add_argument("--device", default=None)
     p.add_argument("--eval", type=int, default=None, metavar="IDX", help="load model{IDX}.pth and play greedily")
     p.add_argument("--render", action="store_true")
+    p.add_argument("--engine", choices=["host", "gpu"], default="host",
+                   help="gpu: the GPU-resident engine (apex_amd.engine.dqn) instead of the host loop")
+    p.add_argument("--save-interval", type=float, default=1e4, help="(gpu engine) model{t}.pth every N frames")
+    p.add_argument("--log-interval", type=int, default=1000, help="(gpu engine) one JSON line per N frames")
+    p.add_argument("--eval-interval", type=int, default=0,
+                   help="(gpu engine) greedy return of 10 rollouts every N frames (0: never)")
     a = p.parse_args(argv)
+    if a.engine == "gpu" and a.eval is None:
+        return train_gpu(a)
     t = train_DQN(a.env, max_step=a.max_step, batch_size=a.batch_size, seed=a.seed, save_dir=a.save_dir,
                   device=a.device)
     if a.eval is None:
