@@ -25,6 +25,12 @@ What runs where (all device-side, no host sync inside an iteration):
   online and target NoisyNets + proposal hard copy online -> target, AQL_dis.py:92,104-105).
   K learner steps are captured in one hipGraph.
 
+Greedy evaluation stays on the device too.  :meth:`AQLEngine.evaluate` is the stepwise
+yardstick (an evaluation shard of its own, the acting kernels at eps 0 with the online net in
+eval mode: NoisyNet means); :meth:`AQLEngine.rollout_evaluate` plays the same episodes in ONE
+``aql_rollout`` launch, bit-equal for equal seeds; :class:`AQLEvaluator` runs that launch on a
+side stream from a weight snapshot, beside training (``train_aql --eval-mode``).
+
 Iteration = one actor step of all E envs + ``E // batch`` learner steps: the reference's
 replay ratio (``total_ep_len // batch_size`` SGD steps per recorded batch, AQL_dis.py:118).
 Weights are published to the actors every iteration (set_worker_weights, AQL_dis.py:115)
@@ -606,6 +612,12 @@ class AQLEngine:
         self._g_actor = self._g_learn = self._g_iter = None
         self._ep_read = 0
         self.target_syncs = collections.deque(maxlen=4096)  # iterations after which the target was synced
+        # greedy evaluation: the registered TimeLimit (greedy_eval's), the eval-mode handle of the
+        # online net (NoisyNet means; same parameter storage, the module stays in train mode)
+        self.eval_limit = int(getattr(self.host_env, "_max_episode_steps", None) or 10_000)
+        self.eval_net = self.learner.fused_on._net(noisy=False)
+        self._eval = None
+        self._rollout = None
 
     @staticmethod
     def _s() -> int:
@@ -805,3 +817,194 @@ class AQLEngine:
     @property
     def transitions_per_iteration(self) -> int:
         return self.E
+
+    # ------------------------------------------------------------------ evaluation
+    def _eval_seed(self, seed: int | None) -> int:
+        sd = (self.cfg.seed * 7919 + 0xE7A1 + self.learner_steps) if seed is None else int(seed)
+        return sd & 0xFFFFFFFFFFFF
+
+    def evaluate(self, episodes: int = 10, seed: int | None = None, max_episode_steps: int | None = None) -> list[float]:
+        """Greedy returns of ``episodes`` episodes, one env each, with the ONLINE network in eval
+        mode (NoisyNet means: the reference's ``q.eval()`` evaluation branch), stepwise: per env
+        step ``aql_propose`` -> ``aql_candidate_q`` -> ``aql_select`` (eps 0) -> ``aql_env_step``.
+        It runs on an evaluation shard of its own -- a second env block and scratch transition
+        rows -- so the training envs, the replay and the tree are untouched.  ``seed`` is the env
+        seed (default: ``cfg.seed``, a constant and the learner-step count, 48 bits); the same
+        seed and weights give the same episodes.  Returns are fp32 sums in step order up to each
+        env's first done; a finished env goes on stepping (the kernel resets it) and is ignored.
+
+        ``aql_select`` draws a 24-bit uniform and explores when it is <= eps, so at eps 0 a step
+        still takes a random candidate with probability 2^-24 (as ``VectorApexEngine.evaluate``)."""
+        h, dev, n = self.hip, self.device, int(episodes)
+        if n < 1:
+            raise ValueError("evaluate: episodes >= 1")
+        limit = int(self.eval_limit if max_episode_steps is None else max_episode_steps)
+        if self._eval is None or self._eval["n"] != n:
+            f32 = dict(dtype=torch.float32, device=dev)
+            i32 = dict(dtype=torch.int32, device=dev)
+            ev = {"n": n, "obs_buf": torch.zeros(n, self.obs, **f32), "phys": torch.zeros(n, 4, **f32),
+                  "ep_len": torch.zeros(n, **i32), "ep_ret": torch.zeros(n, **f32), "ep_count": torch.zeros(1, **i32),
+                  "ep_log": torch.zeros(64, 2, **f32), "amu": torch.zeros(n, self.T, self.adim, **f32),
+                  "q": torch.zeros(n, self.T, **f32), "act_idx": torch.zeros(n, **i32),
+                  "env_act": torch.zeros(n, self.adim, **f32), "eps": torch.zeros(n, **f32),
+                  "counter": torch.zeros(1, dtype=torch.int64, device=dev),
+                  "ws": torch.zeros(h.aql_workspace_floats(), **f32),
+                  # scratch transition rows (C = n), the way actor_step(into=...) feeds a packet buffer
+                  "st": torch.zeros(n, self.obs, **f32), "st2": torch.zeros(n, self.obs, **f32),
+                  "rew": torch.zeros(n, **f32), "done": torch.zeros(n, **f32),
+                  "amu_row": torch.zeros(n, self.T, self.adim, **f32), "act": torch.zeros(n, **i32),
+                  "filled": torch.zeros(1, dtype=torch.int64, device=dev), "slots": torch.zeros(n, **i32),
+                  "zero": torch.zeros(n, **f32)}
+            ev["ins"] = h.make_aql_insert(dict(st=ev["st"].data_ptr(), st2=ev["st2"].data_ptr(),
+                                               rew=ev["rew"].data_ptr(), done=ev["done"].data_ptr(),
+                                               amu=ev["amu_row"].data_ptr(), act=ev["act"].data_ptr(), C=n,
+                                               filled=ev["filled"].data_ptr(), slots=ev["slots"].data_ptr()))
+            self._eval = ev
+        ev = self._eval
+        sd = self._eval_seed(seed)
+        env = h.make_aql_env(dict(
+            kind=self.kind, E=n, obs=self.obs, adim=self.adim, T=self.T, max_steps=limit,
+            obs_buf=ev["obs_buf"].data_ptr(), phys=ev["phys"].data_ptr(), ep_len=ev["ep_len"].data_ptr(),
+            ep_ret=ev["ep_ret"].data_ptr(), dynA=self.dynA.data_ptr(), dynB=self.dynB.data_ptr(),
+            dynw=self.dynw.data_ptr(), seed=sd, counter=ev["counter"].data_ptr(),
+            ep_count=ev["ep_count"].data_ptr(), ep_log=ev["ep_log"].data_ptr(), log_cap=ev["ep_log"].shape[0]))
+        s, net = self._s(), self.eval_net
+        h.aql_env_reset(env, s)
+        ev["counter"].zero_()
+        ret = torch.zeros(n, dtype=torch.float32, device=dev)
+        got = torch.zeros(n, dtype=torch.bool, device=dev)
+        for t in range(limit):
+            h.aql_propose(net, ev["obs_buf"].data_ptr(), n, self.low.data_ptr(), self.high.data_ptr(),
+                          self.var.data_ptr(), sd ^ 0x9909, ev["counter"].data_ptr(), ev["amu"].data_ptr(), 0, s)
+            h.aql_candidate_q(net, ev["ws"].data_ptr(), ev["obs_buf"].data_ptr(), ev["amu"].data_ptr(), n,
+                              ev["q"].data_ptr(), s)
+            h.aql_select(ev["q"].data_ptr(), ev["amu"].data_ptr(), n, self.T, self.adim, ev["eps"].data_ptr(),
+                         sd ^ 0xA9C1, ev["counter"].data_ptr(), ev["act_idx"].data_ptr(), ev["env_act"].data_ptr(), s)
+            h.aql_env_step(env, ev["env_act"].data_ptr(), ev["act_idx"].data_ptr(), ev["amu"].data_ptr(), ev["ins"], s)
+            ev["counter"].add_(1)
+            ret = torch.where(got, ret, ret + ev["rew"])   # fp32, step order, up to the first done
+            got |= ev["done"] > 0
+            if (t + 1) % 50 == 0 and bool(got.all()):
+                break
+        return ret.tolist()
+
+    def rollout_evaluate(self, episodes: int = 10, seed: int | None = None,
+                         max_episode_steps: int | None = None) -> list[float]:
+        """``evaluate()`` in one launch: ``aql_rollout`` plays the ``episodes`` greedy episodes
+        from reset to their first done inside one kernel on the current stream, then one
+        read-back.  Same contract, same default seed and, for the same seed, the same floats.
+        The online weights are read in place (the caller's stream order protects them)."""
+        n = int(episodes)
+        limit = int(self.eval_limit if max_episode_steps is None else max_episode_steps)
+        if self._rollout is None or self._rollout.n != n:
+            self._rollout = AQLRolloutBuffers(self, self.eval_net, n)
+        self._rollout.launch(self._eval_seed(seed), limit)
+        return self._rollout.returns.tolist()
+
+
+class AQLRolloutBuffers:
+    """Device outputs of ``aql_rollout`` for ``n`` episodes of one net handle + the launch."""
+
+    def __init__(self, engine: AQLEngine, net, n: int):
+        self.engine, self.hip, self.net, self.n = engine, engine.hip, net, int(n)
+        dev = engine.device
+        self.returns = torch.zeros(self.n, dtype=torch.float32, device=dev)
+        self.lengths = torch.zeros(self.n, dtype=torch.int32, device=dev)
+        self.ended = torch.zeros(self.n, dtype=torch.int32, device=dev)
+
+    def descriptor(self, seed: int, max_steps: int, trace: dict | None = None, **over) -> dict:
+        """The launch's arguments: seeds as ``AQLEngine.evaluate`` derives them from the env
+        seed.  ``trace``: the tensors ``obs`` f32 [n, Tr, obs], ``amu`` f32 [n, Tr, T, adim],
+        ``q`` f32 [n, Tr, T], ``act`` i32 [n, Tr] and ``rew`` f32 [n, Tr]."""
+        e, sd = self.engine, int(seed)
+        d = dict(kind=e.kind, N=self.n, max_steps=int(max_steps), env_seed=sd, prop_seed=sd ^ 0x9909,
+                 sel_seed=sd ^ 0xA9C1, low=e.low.data_ptr(), high=e.high.data_ptr(), var=e.var.data_ptr(),
+                 dynA=e.dynA.data_ptr(), dynB=e.dynB.data_ptr(), dynw=e.dynw.data_ptr(),
+                 returns=self.returns.data_ptr(), lengths=self.lengths.data_ptr(), ended=self.ended.data_ptr())
+        if trace is not None:
+            d.update({"trace_" + k: trace[k].data_ptr() for k in ("obs", "amu", "q", "act", "rew")},
+                     trace_T=int(trace["obs"].shape[1]))
+        d.update(over)
+        return d
+
+    def launch(self, seed: int, max_steps: int, trace: dict | None = None) -> None:
+        """One ``aql_rollout`` launch on the current stream."""
+        self.hip.aql_rollout(self.hip.make_aql_rollout(self.net, self.descriptor(seed, max_steps, trace)),
+                             torch.cuda.current_stream().cuda_stream)
+
+
+class AQLEvaluator:
+    """Greedy evaluation beside training: ``launch()`` snapshots the online flat parameters on
+    the training stream (``copy_f32``; no noise buffers -- evaluation uses the NoisyNet means)
+    and plays the episodes with ``aql_rollout`` on a side stream; training goes on in place and
+    ``poll()`` / ``wait()`` hand the result over once it has landed in pinned host memory.
+    While a launch is in flight a further ``launch()`` does nothing (the snapshot may still be
+    read by the running kernel): evaluations conflate, as the reference's evaluator does.
+    All launches are eager, issued between graph replays; no captured graph gains a node."""
+
+    def __init__(self, engine: AQLEngine, episodes: int = 10, max_episode_steps: int | None = None):
+        self.engine = engine
+        self.hip, self.device = engine.hip, engine.device
+        self.n = int(episodes)
+        self.limit = int(engine.eval_limit if max_episode_steps is None else max_episode_steps)
+        cfg = engine.cfg
+        self.model = AQL(env=engine.host_env, propose_sample=cfg.propose_sample, uniform_sample=cfg.uniform_sample,
+                         action_var=cfg.action_var, device=self.device).to(self.device)   # the snapshot
+        for p in self.model.parameters():
+            p.requires_grad_(False)
+        self.flat = flatten_module_params(self.model)
+        assert self.flat.numel() == engine.learner.P
+        self.fused = FusedAQL(self.model)
+        self.stream = torch.cuda.Stream(device=self.device)
+        self.ro = AQLRolloutBuffers(engine, self.fused._net(noisy=False), self.n)
+        self.host = {"returns": torch.zeros(self.n, dtype=torch.float32).pin_memory(),
+                     "lengths": torch.zeros(self.n, dtype=torch.int32).pin_memory(),
+                     "ended": torch.zeros(self.n, dtype=torch.int32).pin_memory()}
+        self.snapshot_taken = torch.cuda.Event()
+        self.results_landed = torch.cuda.Event()
+        self._pending = False   # a launch whose result is still on its way to the host
+        self._tag = None
+        self._done = collections.deque()   # landed results not yet handed over
+
+    def launch(self, seed: int | None = None, tag=None) -> bool:
+        """Start one evaluation of the online weights as they are at this point of the current
+        stream.  ``False`` (and nothing done) while the previous one has not landed."""
+        if self._pending:
+            if not self.results_landed.query():
+                return False
+            self._harvest()  # the pinned buffers are about to be reused
+        eng = self.engine
+        sd = eng._eval_seed(seed)
+        self.hip.copy_f32(self.flat.data_ptr(), eng.learner.flat.data_ptr(), eng.learner.P,
+                          torch.cuda.current_stream().cuda_stream)
+        self.snapshot_taken.record()
+        with torch.cuda.stream(self.stream):
+            self.stream.wait_event(self.snapshot_taken)
+            self.ro.launch(sd, self.limit)
+            for k, hbuf in self.host.items():
+                hbuf.copy_(getattr(self.ro, k), non_blocking=True)
+            self.results_landed.record()
+        self._pending, self._tag = True, tag
+        return True
+
+    def _harvest(self) -> None:
+        self._pending = False
+        self._done.append({"tag": self._tag, "returns": self.host["returns"].tolist(),
+                           "lengths": self.host["lengths"].tolist(), "ended": self.host["ended"].tolist()})
+
+    def poll(self) -> dict | None:
+        """The oldest finished evaluation not yet handed over (each exactly once), or ``None``."""
+        if self._pending and self.results_landed.query():
+            self._harvest()
+        return self._done.popleft() if self._done else None
+
+    def wait(self) -> dict | None:
+        """As ``poll()``, but blocks until the launch in flight has landed: on the results event
+        only, never on the device.  ``None`` if nothing was launched."""
+        if self._done:
+            return self._done.popleft()
+        if not self._pending:
+            return None
+        self.results_landed.synchronize()
+        self._harvest()
+        return self._done.popleft()

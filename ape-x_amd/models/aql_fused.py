@@ -63,17 +63,24 @@ class FusedAQL:
             self._tensors["ao_b2"] = q.action_out[2].bias
         self._cache = None
 
-    def _net(self):
-        noisy = int(self.model.q.training)
+    def _net(self, noisy: bool | None = None):
+        """The kernels' handle over the model's parameter storage.  ``noisy``: apply the
+        NoisyLinear noise (mu + sigma * eps) or not (the means: the reference's ``q.eval()``);
+        ``None`` follows ``model.q.training``.  An explicit value does not touch the module's
+        mode: an eval-mode handle can sit beside the training one over the same storage."""
+        noisy = int(self.model.q.training if noisy is None else bool(noisy))
         ptrs = {k: int(t.data_ptr()) for k, t in self._tensors.items()}
         key = (noisy, tuple(ptrs.values()))
-        if self._cache is None or self._cache[0] != key:
+        if self._cache is None:
+            self._cache = {}
+        hit = self._cache.get(noisy)
+        if hit is None or hit[0] != key:
             for k, t in self._tensors.items():
                 assert t.is_contiguous() and t.dtype == torch.float32 and t.device == self.device, k
             ints = dict(obs=self.obs, adim=self.adim, cont=int(self.cont), T=self.T, na=self.na,
                         uniform=int(self.model.uniform_sample), propose=int(self.model.propose_sample), noisy=noisy)
-            self._cache = (key, self.hip.make_aql_net(ints, ptrs))
-        return self._cache[1]
+            hit = self._cache[noisy] = (key, self.hip.make_aql_net(ints, ptrs))
+        return hit[1]
 
     @staticmethod
     def _s() -> int:

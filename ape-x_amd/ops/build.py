@@ -44,6 +44,7 @@ HIP_SOURCES = [
     "conv_bwd_kernels.hip",
     "aql_kernels.hip",
     "aql_engine_kernels.hip",
+    "aql_rollout_kernels.hip",
     "conv1_kernels.hip",
     "fc_kernels.hip",
     "loss_heads_kernels.hip",

@@ -41,6 +41,7 @@
 
 #include <cstdlib>
 
+#include "aql_dev.h"
 #include "common.h"
 #include "kernels.h"
 #include "opt_dev.h"
@@ -1087,41 +1088,13 @@ __global__ __launch_bounds__(256) void aql_update_k(const AqlStep* __restrict__ 
 }
 
 // ------------------------------------------------------------------ vector envs
-constexpr int kBwObs = 24, kBwAct = 4;
-
-__device__ __forceinline__ float env_normal(uint64_t seed, int e, int i, int kind, uint64_t ctr) {
-  float u[4];
-  uniform4(seed, ((uint64_t)kind << 48) | ((uint64_t)(uint32_t)e << 8) | (uint32_t)i, ctr, u);
-  return std_normal(u[0], u[1]);
-}
-__device__ __forceinline__ float env_uniform(uint64_t seed, int e, int i, int kind, uint64_t ctr) {
-  float u[4];
-  uniform4(seed, ((uint64_t)kind << 48) | ((uint64_t)(uint32_t)e << 8) | (uint32_t)i, ctr, u);
-  return u[2];
-}
+// (the reset draw and the dynamics are shared with the one-launch rollout: aql_dev.h)
+using aqld::kBwAct;
+using aqld::kBwObs;
 
 // reset env e (one wave): new observation into obs_buf / phys
 __device__ void env_reset_one(const AqlEnv& V, int e, int lane, uint64_t ctr) {
-  float* o = V.obs_buf + (size_t)e * V.obs;
-  if (V.kind == 0) {  // s ~ N(0, 0.1)
-    if (lane < kBwObs) o[lane] = 0.1f * env_normal(V.seed, e, lane, 1, ctr);
-  } else if (V.kind == 1) {  // CartPole: U(-0.05, 0.05)^4
-    if (lane < 4) {
-      const float v = -0.05f + 0.1f * env_uniform(V.seed, e, lane, 1, ctr);
-      o[lane] = v;
-      V.phys[(size_t)e * 4 + lane] = v;
-    }
-  } else {  // Pendulum: th ~ U(-pi, pi), thdot ~ U(-1, 1)
-    const float th = -3.14159265f + 6.2831853f * env_uniform(V.seed, e, 0, 1, ctr);
-    const float thd = -1.f + 2.f * env_uniform(V.seed, e, 1, 1, ctr);
-    if (lane == 0) {
-      V.phys[(size_t)e * 4] = th;
-      V.phys[(size_t)e * 4 + 1] = thd;
-      o[0] = cosf(th);
-      o[1] = sinf(th);
-      o[2] = thd;
-    }
-  }
+  aqld::env_reset_state(V.kind, V.seed, e, lane, ctr, V.obs_buf + (size_t)e * V.obs, V.phys + (size_t)e * 4);
   if (lane == 0) {
     V.ep_len[e] = 0;
     V.ep_ret[e] = 0.f;
@@ -1142,61 +1115,9 @@ __device__ __forceinline__ void env_step_wave(const AqlEnv& V, int e, int lane, 
                                               uint64_t ctr) {
   const int obs = V.obs;
   const float* s = V.obs_buf + (size_t)e * obs;
-  float s2 = 0.f, r = 0.f;
-  bool term = false;
-  if (V.kind == 0) {  // BipedalWalker-shaped (envs/classic.py BipedalWalkerShapedEnv.step)
-    float a[kBwAct], pen = 0.f;
-#pragma unroll
-    for (int d = 0; d < kBwAct; ++d) {
-      a[d] = fminf(fmaxf(a_in[d], -1.f), 1.f);
-      pen += fabsf(a[d]);
-    }
-    if (lane < kBwObs) {
-      float z = 0.01f * env_normal(V.seed, e, lane, 0, ctr);
-      for (int k = 0; k < kBwObs; ++k) z = fmaf(V.dynA[lane * kBwObs + k], s[k], z);
-#pragma unroll
-      for (int d = 0; d < kBwAct; ++d) z = fmaf(V.dynB[lane * kBwAct + d], a[d], z);
-      s2 = tanhf(z);
-    }
-    const float progress = 0.05f * wave_sum(lane < kBwObs ? V.dynw[lane] * s2 : 0.f);
-    r = progress - 0.00035f * 80.f * pen;
-    const float s0 = __shfl(s2, 0, 64);
-    if (fabsf(s0) > 0.995f) {  // "hull touches ground"
-      r = -100.f;
-      term = true;
-    }
-  } else if (V.kind == 1) {  // CartPole (Barto et al. 1983; envs/classic.py CartPoleEnv)
-    float* ph = V.phys + (size_t)e * 4;
-    const float x = ph[0], xd = ph[1], th = ph[2], thd = ph[3];
-    const float force = ((int)a_in[0] == 1) ? 10.f : -10.f;
-    const float ct = cosf(th), sn = sinf(th);
-    const float tmp = (force + 0.05f * thd * thd * sn) / 1.1f;
-    const float tha = (9.8f * sn - ct * tmp) / (0.5f * (4.f / 3.f - 0.1f * ct * ct / 1.1f));
-    const float xa = tmp - 0.05f * tha * ct / 1.1f;
-    const float nv[4] = {x + 0.02f * xd, xd + 0.02f * xa, th + 0.02f * thd, thd + 0.02f * tha};
-    if (lane < 4) s2 = nv[lane];
-    r = 1.f;
-    term = nv[0] < -2.4f || nv[0] > 2.4f || nv[2] < -0.20943951f || nv[2] > 0.20943951f;
-    __builtin_amdgcn_wave_barrier();
-    if (lane < 4) ph[lane] = nv[lane];
-  } else {  // Pendulum (envs/classic.py PendulumEnv)
-    float* ph = V.phys + (size_t)e * 4;
-    const float th = ph[0], thd = ph[1];
-    const float u = fminf(fmaxf(a_in[0], -2.f), 2.f);
-    const float an = remainderf(th, 6.2831853f);  // normalised angle in [-pi, pi]
-    const float cost = an * an + 0.1f * thd * thd + 0.001f * u * u;
-    float nthd = thd + (-3.f * 10.f / 2.f * sinf(th + 3.14159265f) + 3.f * u) * 0.05f;
-    const float nth = th + nthd * 0.05f;
-    nthd = fminf(fmaxf(nthd, -8.f), 8.f);
-    const float nv[3] = {cosf(nth), sinf(nth), nthd};
-    if (lane < 3) s2 = nv[lane];
-    r = -cost;
-    __builtin_amdgcn_wave_barrier();
-    if (lane == 0) {
-      ph[0] = nth;
-      ph[1] = nthd;
-    }
-  }
+  float s2, r;
+  bool term;
+  aqld::env_dynamics(V, e, lane, s, V.phys + (size_t)e * 4, a_in, ctr, s2, r, term);
   const int len = V.ep_len[e] + 1;
   const bool done = term || len >= V.max_steps;  // TimeLimit sets done (stored as terminal)
   // raw transition into the replay ring

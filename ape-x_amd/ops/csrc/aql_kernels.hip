@@ -14,6 +14,7 @@
 //   MVN(mu, diag(var)) (Box-Muller on Philox) or Categorical(softmax(logits))
 //   (model.py:361-374 order: uniform first, then proposal samples).
 // * aql_select: per-row epsilon-greedy over the T candidates + gather of the env action.
+#include "aql_dev.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -61,50 +62,15 @@ __global__ __launch_bounds__(256) void aql_candidate_q_k(AQLNet net, const float
   const int T = net.T, ng = (T + kAqGroup - 1) / kAqGroup, items = B * ng;
   for (int it = blockIdx.x * 4 + wave; it < items; it += gridDim.x * 4) {  // wave-uniform loop
     const int b = it / ng, t0 = (it - b * ng) * kAqGroup, t1 = min(T, t0 + kAqGroup);
-    const float* s = state + (size_t)b * net.obs;
-    // q_feature: obs -> 64 -> 64 (ReLU both)
-    float acc = net.qf_b1[lane];
-    for (int i = 0; i < net.obs; ++i) acc += net.qf_w1[lane * net.obs + i] * s[i];
-    hbuf[wave][lane] = fmaxf(acc, 0.f);
-    __builtin_amdgcn_wave_barrier();
-    acc = net.qf_b2[lane];
-#pragma unroll 8
-    for (int j = 0; j < AQ_H; ++j) acc += qf2s[lane * (AQ_H + 1) + j] * hbuf[wave][j];
-    xbuf[wave][AQ_H + lane] = fmaxf(acc, 0.f);
-    __builtin_amdgcn_wave_barrier();
-    float sadv = b1eff[lane];  // advantage1 bias + its state half
-#pragma unroll 8
-    for (int j = 0; j < AQ_H; ++j) sadv += w1s[lane * AQ_PITCH + AQ_H + j] * xbuf[wave][AQ_H + j];
+    // the state half, then every candidate of the group on top of it (aql_dev.h)
+    const float sadv = aqld::q_state(net.qf_w1, net.obs, net.qf_b1, net.qf_b2, state + (size_t)b * net.obs, net.obs,
+                                     qf2s, w1s, b1eff, hbuf[wave], xbuf[wave] + AQ_H, lane);
     for (int t = t0; t < t1; ++t) {
       const int c = b * T + t;
-      // action encoder
-      if (net.cont) {
-        const float* a = a_mu + (size_t)c * net.adim;
-        float h0 = net.ao_b1[lane], h1 = net.ao_b1[lane + 64];
-        for (int d = 0; d < net.adim; ++d) {
-          const float ad = a[d];
-          h0 += net.ao_w1[lane * net.adim + d] * ad;
-          h1 += net.ao_w1[(lane + 64) * net.adim + d] * ad;
-        }
-        __builtin_amdgcn_wave_barrier();
-        hbuf[wave][lane] = fmaxf(h0, 0.f);
-        hbuf[wave][lane + 64] = fmaxf(h1, 0.f);
-        __builtin_amdgcn_wave_barrier();
-        acc = net.ao_b2[lane];
-#pragma unroll 8
-        for (int j = 0; j < AQ_CAT; ++j) acc += ao2s[lane * AQ_PITCH + j] * hbuf[wave][j];
-        xbuf[wave][lane] = fmaxf(acc, 0.f);
-      } else {
-        xbuf[wave][lane] = fmaxf(net.ao_w1[lane] * a_mu[c] + net.ao_b1[lane], 0.f);
-      }
-      __builtin_amdgcn_wave_barrier();
-      // advantage1 (NoisyLinear 128 -> 64): the action half on top of the state half; advantage2 (64 -> 1)
-      acc = sadv;
-#pragma unroll 8
-      for (int j = 0; j < AQ_H; ++j) acc += w1s[lane * AQ_PITCH + j] * xbuf[wave][j];
-      const float qv = wave_sum(w2eff[lane] * fmaxf(acc, 0.f)) + b2eff;
+      const float* a = net.cont ? a_mu + (size_t)c * net.adim : a_mu + c;
+      const float qv = aqld::q_cand(net, net.ao_w1, net.adim, a, w1s, ao2s, w2eff, b2eff, sadv, hbuf[wave],
+                                    xbuf[wave], lane);
       if (lane == 0) q[c] = qv;
-      __builtin_amdgcn_wave_barrier();
     }
   }
 }
@@ -118,15 +84,8 @@ __global__ __launch_bounds__(256) void aql_candidate_q_k(AQLNet net, const float
 constexpr int kPropStates = 4, kPropPitch = 132;
 
 __device__ __forceinline__ void noisy_eff_elem(const AQLNet& net, float* __restrict__ ws, int i) {
-  const int n1 = AQ_H * AQ_CAT;
-  auto eff = [&](const float* mu, const float* sg, const float* ep, int k) {
-    return net.noisy ? mu[k] + sg[k] * ep[k] : mu[k];
-  };
-  if (i < 0) return;
-  if (i < n1) ws[i] = eff(net.a1_wmu, net.a1_wsig, net.a1_weps, i);
-  else if (i < n1 + AQ_H) ws[i] = eff(net.a1_bmu, net.a1_bsig, net.a1_beps, i - n1);
-  else if (i < n1 + 2 * AQ_H) ws[i] = eff(net.a2_wmu, net.a2_wsig, net.a2_weps, i - n1 - AQ_H);
-  else if (i == n1 + 2 * AQ_H) ws[i] = eff(net.a2_bmu, net.a2_bsig, net.a2_beps, 0);
+  if (i < 0 || i > AQ_H * AQ_CAT + 2 * AQ_H) return;
+  ws[i] = aqld::noisy_eff_val(net, i);
 }
 
 __global__ __launch_bounds__(256) void aql_propose_k(AQLNet net, const float* __restrict__ state, int B,
@@ -179,82 +138,43 @@ __global__ __launch_bounds__(256) void aql_propose_k(AQLNet net, const float* __
   const int j = t & 127, hs = t >> 7;
 #pragma unroll
   for (int s2 = hs; s2 < kPropStates; s2 += 2) {
-    float acc = net.f_b[j];
-    for (int i = 0; i < net.obs; ++i) acc += fw[j * 65 + i] * sst[s2][i];
-    emb[s2][j] = fmaxf(acc, 0.f);
+    emb[s2][j] = aqld::prop_embed(fw + j * 65, sst[s2], net.obs, net.f_b[j]);
   }
   __syncthreads();
   // dist_feature: Linear(128 -> 128) + ReLU + Linear(128 -> A)
   {
-    const float bj = net.df_b1[j];
-    float a0 = bj, a1 = bj;
-    const float* wr = w1 + j * kPropPitch;
-#pragma unroll 8
-    for (int i = 0; i < AQ_CAT; i += 4) {
-      const f32x4 w = *reinterpret_cast<const f32x4*>(wr + i);
-      const f32x4 e0 = *reinterpret_cast<const f32x4*>(&emb[hs][i]);
-      const f32x4 e1 = *reinterpret_cast<const f32x4*>(&emb[hs + 2][i]);
-      a0 += w[0] * e0[0]; a0 += w[1] * e0[1]; a0 += w[2] * e0[2]; a0 += w[3] * e0[3];
-      a1 += w[0] * e1[0]; a1 += w[1] * e1[1]; a1 += w[2] * e1[2]; a1 += w[3] * e1[3];
-    }
-    hid[hs][j] = fmaxf(a0, 0.f);
-    hid[hs + 2][j] = fmaxf(a1, 0.f);
+    const float* const e2[2] = {emb[hs], emb[hs + 2]};
+    float h2[2];
+    aqld::prop_hidden<2>(w1 + j * kPropPitch, e2, net.df_b1[j], h2);
+    hid[hs][j] = h2[0];
+    hid[hs + 2][j] = h2[1];
   }
   __syncthreads();
   const int A = net.na;  // continuous: action dim; discrete: number of actions
   const int b = b0 + wave;  // sampling: one wave per state
   const bool valid = b < B;
   if (lane < A) {
-    float acc = net.df_b2[lane];
-    for (int i = 0; i < AQ_CAT; ++i) acc += w2[lane * kPropPitch + i] * hid[wave][i];
+    const float acc = aqld::prop_out(w2 + lane * kPropPitch, hid[wave], net.df_b2[lane]);
     mu[wave][lane] = acc;
     if (mu_out && valid) mu_out[(size_t)b * A + lane] = acc;
   }
   __syncthreads();
   const uint64_t ctr = counter ? (uint64_t)counter[0] : 0ull;
   const int U = net.uniform, T = net.T;
-  float u[4];
   if (net.cont) {
     if (!valid) return;
     float* out = a_mu + (size_t)b * T * A;
-    for (int e = lane; e < T * A; e += 64) {
-      const int tt = e / A, d = e % A;
-      uniform4(seed, (uint64_t)b * 4096 + e, ctr, u);
-      out[e] = tt < U ? low[d] + (high[d] - low[d]) * u[0] : mu[wave][d] + sqrtf(var[d]) * std_normal(u[1], u[2]);
-    }
+    for (int e = lane; e < T * A; e += 64)
+      out[e] = aqld::prop_sample_cont(e, A, U, b, seed, ctr, low, high, var, mu[wave]);
   } else {
-    if (lane == 0 && valid) {  // uniform without replacement: partial Fisher-Yates over 0..A-1
-      for (int i = 0; i < A; ++i) perm[wave][i] = i;
-      for (int i = 0; i < U; ++i) {
-        uniform4(seed, (uint64_t)b * 4096 + 4000 + i, ctr, u);
-        const int jj = i + min((int)(u[0] * (float)(A - i)), A - i - 1);
-        const int tmp = perm[wave][i];
-        perm[wave][i] = perm[wave][jj];
-        perm[wave][jj] = tmp;
-      }
-    }
+    if (lane == 0 && valid) aqld::prop_perm(perm[wave], A, U, b, seed, ctr);
     __syncthreads();
     if (!valid) return;
     float* out = a_mu + (size_t)b * T;
-    float mx = -INFINITY;
-    for (int i = 0; i < A; ++i) mx = fmaxf(mx, mu[wave][i]);
-    float z = 0.f;
-    for (int i = 0; i < A; ++i) z += expf(mu[wave][i] - mx);
-    for (int tt = lane; tt < T; tt += 64) {
-      if (tt < U) {
-        out[tt] = (float)perm[wave][tt];
-      } else {  // inverse-CDF categorical sample of softmax(logits)
-        uniform4(seed, (uint64_t)b * 4096 + tt, ctr, u);
-        const float target = u[0] * z;
-        float c = 0.f;
-        int k = A - 1;
-        for (int i = 0; i < A; ++i) {
-          c += expf(mu[wave][i] - mx);
-          if (c > target) { k = i; break; }
-        }
-        out[tt] = (float)k;
-      }
-    }
+    float mx, z;
+    aqld::prop_softmax_norm(mu[wave], A, mx, z);
+    for (int tt = lane; tt < T; tt += 64)
+      out[tt] = aqld::prop_sample_disc(tt, A, U, b, seed, ctr, perm[wave], mu[wave], mx, z);
   }
 }
 
@@ -264,21 +184,7 @@ __global__ void aql_select_k(const float* __restrict__ q, const float* __restric
   const int lane = threadIdx.x & 63;
   const int b = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   if (b >= B) return;
-  float best = -INFINITY;
-  int arg = 0x7fffffff;
-  for (int t = lane; t < T; t += 64) {
-    const float v = q[(size_t)b * T + t];
-    if (v > best || (v == best && t < arg)) { best = v; arg = t; }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o, 64);
-    const int oa = __shfl_xor(arg, o, 64);
-    if (ov > best || (ov == best && oa < arg)) { best = ov; arg = oa; }
-  }
-  float u[4];
-  uniform4(seed, (uint64_t)b, counter ? (uint64_t)counter[0] : 0ull, u);
-  if (u[0] <= eps[b]) arg = min((int)(u[1] * (float)T), T - 1);  // random candidate (model.py:331-333)
+  const int arg = aqld::select_cand(q + (size_t)b * T, T, eps[b], seed, b, counter ? (uint64_t)counter[0] : 0ull, lane);
   if (lane == 0) act_idx[b] = arg;
   for (int d = lane; d < adim; d += 64) env_act[(size_t)b * adim + d] = a_mu[((size_t)b * T + arg) * adim + d];
 }

@@ -890,6 +890,26 @@ PYBIND11_MODULE(_apex_hip, m) {
                            uint64_t s) {
     aql_env_step(e, P<const float>(env_act), P<const int>(act_idx), P<const float>(amu), ins, S(s));
   });
+  py::class_<AqlRollout>(m, "AqlRollout");
+  // d: kind, N, max_steps, env_seed, prop_seed, sel_seed, low, high, var, dynA, dynB, dynw, returns, lengths,
+  // ended [+ trace_obs, trace_amu, trace_q, trace_act, trace_rew, trace_T]
+  m.def("make_aql_rollout", [](const AQLNet& net, py::dict d) {
+    auto opt = [&](const char* k) { return d.contains(k) ? d[k].cast<uint64_t>() : (uint64_t)0; };
+    AqlRollout r{};
+    r.net = net;
+    r.kind = d["kind"].cast<int>(); r.N = d["N"].cast<int>(); r.max_steps = d["max_steps"].cast<int>();
+    r.env_seed = d["env_seed"].cast<uint64_t>(); r.prop_seed = d["prop_seed"].cast<uint64_t>();
+    r.sel_seed = d["sel_seed"].cast<uint64_t>();
+    r.low = P<const float>(opt("low")); r.high = P<const float>(opt("high")); r.var = P<const float>(opt("var"));
+    r.dynA = P<const float>(opt("dynA")); r.dynB = P<const float>(opt("dynB")); r.dynw = P<const float>(opt("dynw"));
+    r.returns = P<float>(opt("returns")); r.lengths = P<int>(opt("lengths")); r.ended = P<int>(opt("ended"));
+    r.trace_obs = P<float>(opt("trace_obs")); r.trace_amu = P<float>(opt("trace_amu"));
+    r.trace_q = P<float>(opt("trace_q")); r.trace_act = P<int>(opt("trace_act"));
+    r.trace_rew = P<float>(opt("trace_rew"));
+    r.trace_T = d.contains("trace_T") ? d["trace_T"].cast<int>() : 0;
+    return r;
+  });
+  m.def("aql_rollout", [](const AqlRollout& r, uint64_t s) { aql_rollout(r, S(s)); });
   py::class_<AqlTail>(m, "AqlTail");
   m.def("make_aql_tail", [](const AqlEnv& env, const AqlInsert& ins, const TreeHandle& tree, py::dict d) {
     auto g = [&](const char* k) { return d[k].cast<uint64_t>(); };

@@ -653,6 +653,31 @@ struct AqlTail {
   double beta0, beta_omb, beta_max_step, beta_workers;
 };
 void aql_act_tail(const AqlTail& a, hipStream_t s);
+// N greedy episodes from reset to their first done in one launch (aql_rollout_kernels.hip; one
+// workgroup per episode, the weights staged once): episode b starts at aql_env_reset's draw for
+// env b and every step is aql_propose -> aql_candidate_q -> aql_select (eps 0) -> aql_env_step
+// at step counter t = 0, 1, ... with the same Philox keys and arithmetic.  The critic's
+// NoisyLinear layers use mu + sigma * eps if net.noisy, the means otherwise (evaluation).  The
+// trace (all five pointers or none) records the first trace_T steps of every episode; rows past
+// an episode's end and rows >= N are never written.
+struct AqlRollout {
+  AQLNet net;
+  int kind;            // 0 BipedalWalker-shaped, 1 CartPole, 2 Pendulum
+  int N, max_steps;    // episodes; TimeLimit: the episode ends once its length reaches it
+  uint64_t env_seed, prop_seed, sel_seed;  // AqlEnv::seed, aql_propose's and aql_select's seeds
+  const float *low, *high, *var;           // action bounds / proposal variance [adim] (continuous)
+  const float *dynA, *dynB, *dynw;         // BipedalWalker-shaped dynamics
+  float* returns;      // [N] sum of rewards (fp32, step order)
+  int* lengths;        // [N] steps taken
+  int* ended;          // [N] 1 terminal, 2 time limit
+  float* trace_obs;    // optional [N][trace_T][obs]: the observation acted on
+  float* trace_amu;    // optional [N][trace_T][T][adim]: the candidate set
+  float* trace_q;      // optional [N][trace_T][T]
+  int* trace_act;      // optional [N][trace_T]: the chosen candidate
+  float* trace_rew;    // optional [N][trace_T]
+  int trace_T;
+};
+void aql_rollout(const AqlRollout& r, hipStream_t s);
 // rows 0..E-1 of the staging tables ``src`` -> ring slots (dst.filled + e) % dst.C (slot list in dst.slots)
 void aql_apply_staged(const AqlInsert& src, const AqlInsert& dst, int E, int obs, int TA, hipStream_t s);
 

@@ -25,6 +25,13 @@ Reference cadences and artefacts kept:
   from greedy episodes (the reference's ``training=False`` branch: ``q.eval()``, eps 0,
   AQL_dis.py:151-167) and ``learner/steps_per_sec`` / ``actor/env_steps_per_sec``.
 
+``--eval-mode`` selects the greedy evaluator of ``--eval-interval``: ``host`` (default: a CPU
+copy of the online net on a host env, :func:`greedy_eval`), ``rollout`` (one ``aql_rollout``
+launch on the GPU, ``AQLEngine.rollout_evaluate``: same keys and tags) or ``async`` (that launch
+on a weight snapshot on a side stream, ``AQLEvaluator``: a landed result rides in the next log
+record as ``greedy_mean_return`` + ``greedy_iteration``, the iterations completed when the
+snapshot was taken; the last one is drained at the end of the run).  Single-GPU engine only.
+
 Losses are accumulated on the device (no host sync per learner step); the host reads
 them once per ``--log-interval`` iterations.
 
@@ -45,14 +52,26 @@ import numpy as np
 import torch
 
 from . import envs
-from .engine.aql import AQLEngine, AQLEngineConfig
+from .engine.aql import AQLEngine, AQLEngineConfig, AQLEvaluator
 from .models.aql import AQL
 from .utils.checkpoint import load_model, load_train_state, save_model, save_train_state
 from .utils.tb import NullWriter, SummaryWriter
 
 
+EVAL_MODES = ("host", "rollout", "async")
+
+
+class _Parser(argparse.ArgumentParser):
+    def parse_args(self, args=None, namespace=None):
+        a = super().parse_args(args, namespace)
+        if a.gpus > 1 and a.eval_mode != "host":
+            self.error(f"--eval-mode {a.eval_mode} is for the single-GPU engine: with --gpus {a.gpus} rank 0's "
+                       "evaluator is the host one (--eval-mode host)")
+        return a
+
+
 def parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(description="AQL_dis on MI355X (GPU-resident AQL engine)")
+    p = _Parser(description="AQL_dis on MI355X (GPU-resident AQL engine)")
     p.add_argument("--env", default="CartPole-v0", help="CartPole-v0/v1, Pendulum-v0/v1, BipedalWalker-v3")
     p.add_argument("--max-step", type=int, default=1_000_000, help="iterations (AQL_dis max_step)")
     p.add_argument("--n-envs", type=int, default=256, help="GPU envs (the reference's workers)")
@@ -78,6 +97,10 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--log-interval", type=int, default=20, help="iterations between metric reads (host syncs)")
     p.add_argument("--eval-interval", type=int, default=0, help="iterations between greedy evaluations (0 = off)")
     p.add_argument("--eval-episodes", type=int, default=10)
+    p.add_argument("--eval-mode", default="host", choices=EVAL_MODES,
+                   help="host: a CPU copy of the online net on a host env (greedy_eval); rollout: one aql_rollout "
+                        "launch on the GPU; async: that launch on a weight snapshot beside training, reported by "
+                        "the next log line (single-GPU engine only)")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--device", default="cuda:0")
     p.add_argument("--no-graphs", action="store_true")
@@ -275,6 +298,10 @@ def _loop(a, eng: AQLEngine, iterate, envs_per_iter: int, episodes, start: int, 
     the recorded batches that reached the replay (CentralAQLEngine.data_iterations), and the
     logged step counts / rates read the device SGD counter (one sync per log window)."""
     ep_idx, last = 0, {}
+    mode = getattr(a, "eval_mode", "host")
+    if central is not None and mode != "host":
+        raise ValueError("the central form evaluates on the host (--eval-mode host)")
+    asyn = AQLEvaluator(eng, a.eval_episodes) if mode == "async" and a.eval_interval > 0 else None
     t_win, it_win, steps_win = time.perf_counter(), start, eng.learner_steps
     jl = open(a.json_log, "a") if a.json_log else None
     it = start  # the next iteration to complete
@@ -295,8 +322,17 @@ def _loop(a, eng: AQLEngine, iterate, envs_per_iter: int, episodes, start: int, 
                     central.refresh_steps()
                 save_engine(eng, model_path(a.save_dir, hi))
             log_now = _crossed(lo, hi, a.log_interval, 1 - start) or hi == a.max_step - 1
-            ev = a.eval_interval > 0 and (_crossed(lo, hi, a.eval_interval, 1) or hi == a.max_step - 1)
+            final = hi == a.max_step - 1
+            ev = a.eval_interval > 0 and (_crossed(lo, hi, a.eval_interval, 1) or final)
+            # async: snapshot + side-stream rollout, no log line and no sync of its own.  A record
+            # reports what landed BEFORE this iteration's launch, so its greedy_iteration (the
+            # iterations completed when the snapshot was taken) never runs ahead of the record
+            launch = ev and asyn is not None
+            if launch:
+                ev = False
             if not (log_now or ev):
+                if launch:
+                    asyn.launch(tag=hi + 1)  # (conflates with one still in flight)
                 continue
             if central is not None:
                 central.refresh_steps()
@@ -321,20 +357,41 @@ def _loop(a, eng: AQLEngine, iterate, envs_per_iter: int, episodes, start: int, 
                 last["packets_applied"] = sum(central.applied.values())
                 last["learner_spins"] = central.spins
             if ev:
-                ret = greedy_eval(eng, a.eval_episodes, seed=a.seed + 7 * hi)
+                ret = (eng.rollout_evaluate(a.eval_episodes) if mode == "rollout"
+                       else greedy_eval(eng, a.eval_episodes, seed=a.seed + 7 * hi))
                 for k, r in enumerate(ret):
                     writer.add_scalar("evaluator/episode_reward", r, eng.learner_steps)
                 last["greedy_mean_return"] = float(np.mean(ret))
+            if asyn is not None:
+                res = None  # the newest evaluation that has landed (last iteration: wait out the one in flight)
+                while (r := asyn.wait() if final else asyn.poll()) is not None:
+                    res = r
+                if res is not None:
+                    _report_async(res, last, writer, eng)
             print(json.dumps(last), flush=True)
             if jl:
                 jl.write(json.dumps(last) + "\n")
                 jl.flush()
+            if launch:
+                asyn.launch(tag=hi + 1)
             t_win, it_win, steps_win = time.perf_counter(), hi + 1, eng.learner_steps
+        if asyn is not None and (res := asyn.wait()) is not None:
+            # the last iteration's evaluation: drained (nothing stays in flight) into the returned
+            # record and the event file; it forces no log line of its own
+            last = dict(last)
+            _report_async(res, last, writer, eng)
     finally:
         writer.flush()
         if jl:
             jl.close()
     return last
+
+
+def _report_async(res: dict, rec: dict, writer, eng: AQLEngine) -> None:
+    for r in res["returns"]:
+        writer.add_scalar("evaluator/episode_reward", r, eng.learner_steps)
+    rec["greedy_mean_return"] = float(np.mean(res["returns"]))
+    rec["greedy_iteration"] = res["tag"]
 
 
 def main(argv=None) -> int:
