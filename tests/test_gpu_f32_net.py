@@ -297,14 +297,14 @@ def test_gemm_layers_are_fp32_class(cuda):
 
 
 
-@pytest.mark.parametrize("B", [96, 384])
+@pytest.mark.parametrize("B", [96, 384, 343])
 def test_stage_split_gemms_bit_identical(cuda, B):
     """The stage-split GEMM form (each staged fp32 element split once into bf16 hi / mid / lo
     planes in LDS, fragments read back as ready MFMA operands -- ds_read_b128 for K-major,
     ds_read_b64_tr_b16 for MN-major operands) against the per-wave register split: the same
     terms in the same MFMA k-slots, so every forward activation (3-problem learner launch:
-    B = 384 takes the learner-sized tiles), every input gradient and every weight gradient is
-    BIT-identical."""
+    B = 384 takes the learner-sized tiles, B = 343 with ragged last tiles and a non-empty
+    xcd_chunk tail), every input gradient and every weight gradient is BIT-identical."""
     from apex_amd import ops
     from apex_amd.models.fused import forward_multi
     from apex_amd.models.fused_f32 import F32DuelingNet, F32Workspace

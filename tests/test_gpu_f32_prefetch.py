@@ -33,11 +33,12 @@ def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
-@pytest.mark.parametrize("B", [96, 384])
+@pytest.mark.parametrize("B", [96, 384, 343])
 def test_prefetch_depths_bit_identical(cuda, B):
     """Every activation, the three Q rows, dz, every input gradient and every parameter
     gradient of the 3-problem learner pass (B = 96: the small tiles, B = 384: the learner-sized
-    ones) at depths 1..3 under the four GEMM forms against depth 1 of the register split."""
+    ones, B = 343: those with ragged last tiles and a non-empty xcd_chunk tail) at depths 1..3
+    under the four GEMM forms against depth 1 of the register split."""
     from apex_amd import ops
     from apex_amd.models.fused import forward_multi
     from apex_amd.models.fused_f32 import F32DuelingNet, F32Workspace
