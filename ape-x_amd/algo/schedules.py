@@ -7,6 +7,7 @@
   (ApeX.py:39 horizon 1000, DQN.py:40, AQL.py:51 horizon max_step).
 * DQN epsilon decay: eps(t) = eps_final + (eps_start - eps_final) exp(-t / decay)
   (DQN.py:41).
+* AQL.py learning rate: CosineAnnealingLR's closed form (AQL.py:44-45), ``cosine_lr``.
 """
 from __future__ import annotations
 
@@ -28,6 +29,13 @@ def beta_by_frame(frame_idx: int, beta_start: float = 0.4, horizon: float = 1000
 
 def epsilon_by_frame(frame_idx: int, eps_start: float = 1.0, eps_final: float = 0.01, decay: float = 500.0) -> float:
     return eps_final + (eps_start - eps_final) * math.exp(-1.0 * frame_idx / decay)
+
+
+def cosine_lr(k: int, lr0: float, T_max: float, eta_min: float) -> float:
+    """``CosineAnnealingLR``'s closed form after ``k`` scheduler steps (AQL.py:44-45: both Adams,
+    ``T_max = max_step``, ``eta_min = lr / 1000``; SGD step k, 0-based, runs at ``cosine_lr(k)``):
+    eta_min + (lr0 - eta_min) (1 + cos(pi k / T_max)) / 2, in double precision."""
+    return eta_min + (lr0 - eta_min) * (1.0 + math.cos(math.pi * k / T_max)) / 2.0
 
 
 def step_scheduler_early(scheduler) -> None:

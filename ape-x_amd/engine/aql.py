@@ -221,7 +221,11 @@ def target_sync_due(cfg: AQLEngineConfig, iteration: int, steps_before: int, ste
 class AQLLearner:
     """Device-resident AQL learner over an :class:`AQLReplay` (see module docstring)."""
 
-    def __init__(self, model: AQL, target: AQL, replay: AQLReplay, cfg: AQLEngineConfig):
+    def __init__(self, model: AQL, target: AQL, replay: AQLReplay, cfg: AQLEngineConfig,
+                 step_opts: dict | None = None):
+        """``step_opts``: extra options of the update launch's descriptors (``make_aql_step``:
+        ``keep_noise``, ``no_proposal_copy``, ``cos_T_max`` / ``cos_eta_min`` / ``cos_lr0`` -- the
+        single-process trainer's step, engine/aql_frame.py); ``None`` changes nothing."""
         self.hip = h = ops.hip()
         self.cfg, self.model, self.target, self.replay = cfg, model, target, replay
         dev = replay.device
@@ -315,7 +319,8 @@ class AQLLearner:
             self.G = h.aql_grad_set_step_snap(self.G, self.step_snap.data_ptr(), self.step_ctr.data_ptr())
             self.G_levels = h.aql_grad_set_levels(self.G, r.tree, r.wlist.data_ptr(), B, lo=2)
             kw = dict(p=self.flat.data_ptr(), m=self.m.data_ptr(), v=self.v.data_ptr(), n=self.P, P_q=self.P_q,
-                      norms_q=self.norms_q.data_ptr(), norms_p=self.norms_p.data_ptr(), update=1)
+                      norms_q=self.norms_q.data_ptr(), norms_p=self.norms_p.data_ptr(), update=1,
+                      **(step_opts or {}))
             nb = h.aql_step_nbytes()
             self.step_desc = torch.zeros(2, nb, dtype=torch.uint8, device=dev)
             self.pub_desc = torch.zeros(nb, dtype=torch.uint8, device=dev)

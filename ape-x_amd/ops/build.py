@@ -45,6 +45,7 @@ HIP_SOURCES = [
     "aql_kernels.hip",
     "aql_engine_kernels.hip",
     "aql_rollout_kernels.hip",
+    "aql_frame_kernels.hip",
     "conv1_kernels.hip",
     "fc_kernels.hip",
     "loss_heads_kernels.hip",

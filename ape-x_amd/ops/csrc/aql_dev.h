@@ -1,9 +1,10 @@
 // Device bodies shared by the stepwise AQL acting kernels (aql_kernels.hip: aql_propose_k,
-// aql_candidate_q_k; aql_engine_kernels.hip: the vector envs) and the one-launch greedy rollout
-// (aql_rollout_kernels.hip).  Each function is the per-state / per-candidate / per-env body of
-// one kernel with its operands passed as pointers: the callers choose where a matrix lives (LDS
-// or global) and how the work is spread over threads, the arithmetic order is fixed here -- so
-// the rollout reproduces the stepwise kernels bit for bit.  Every multiply-add of the network
+// aql_candidate_q_k; aql_engine_kernels.hip: the vector envs), the one-launch greedy rollout
+// (aql_rollout_kernels.hip) and the one-launch acting frame (aql_frame_kernels.hip).  Each
+// function is the per-state / per-candidate / per-env body of one kernel with its operands
+// passed as pointers: the callers choose where a matrix lives (LDS or global) and how the work
+// is spread over threads, the arithmetic order is fixed here -- so the rollout and the frame
+// reproduce the stepwise kernels bit for bit.  Every multiply-add of the network
 // bodies is an explicit fmaf: left to -ffp-contract=fast, the compiler fused a dot product in
 // one caller and (after vectorising two chains into packed mul + add) not in another.
 #pragma once
@@ -87,6 +88,74 @@ __device__ __forceinline__ float q_cand(const AQLNet& net, const float* ao1, int
   const float qv = wave_sum(w2eff[lane] * fmaxf(acc, 0.f)) + b2eff;
   __builtin_amdgcn_wave_barrier();
   return qv;
+}
+
+// q_cand for four candidates at once (a[c]: candidate c's action): every weight read from LDS
+// serves four candidates, whose activations sit interleaved ([unit][4]: one 16-byte broadcast
+// read per unit) -- 6 LDS cycles per unit and four candidates instead of 16.  Each candidate's
+// fma chain is q_cand's, in q_cand's order: the same bits.  hb: 512, xb: 256 floats of this
+// wave's scratch, 16-byte aligned.
+__device__ __forceinline__ void q_cand4(const AQLNet& net, const float* ao1, int pa, const float* const (&a)[4],
+                                        const float* w1s, const float* ao2s, const float* w2eff, float b2eff,
+                                        float sadv, float* hb, float* xb, int lane, float (&qv)[4]) {
+  float acc[4];
+  if (net.cont) {
+    f32x4 h0, h1;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      h0[c] = net.ao_b1[lane];
+      h1[c] = net.ao_b1[lane + 64];
+    }
+    for (int d = 0; d < net.adim; ++d) {
+      const float w0 = ao1[lane * pa + d], w1 = ao1[(lane + 64) * pa + d];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const float ad = a[c][d];
+        h0[c] = fmaf(w0, ad, h0[c]);
+        h1[c] = fmaf(w1, ad, h1[c]);
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      h0[c] = fmaxf(h0[c], 0.f);
+      h1[c] = fmaxf(h1[c], 0.f);
+    }
+    __builtin_amdgcn_wave_barrier();
+    *reinterpret_cast<f32x4*>(hb + 4 * lane) = h0;
+    *reinterpret_cast<f32x4*>(hb + 4 * (lane + 64)) = h1;
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int c = 0; c < 4; ++c) acc[c] = net.ao_b2[lane];
+#pragma unroll 8
+    for (int j = 0; j < kCat; ++j) {
+      const float w = ao2s[lane * kPitch + j];
+      const f32x4 x = *reinterpret_cast<const f32x4*>(hb + 4 * j);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc[c] = fmaf(w, x[c], acc[c]);
+    }
+    f32x4 xo;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) xo[c] = fmaxf(acc[c], 0.f);
+    *reinterpret_cast<f32x4*>(xb + 4 * lane) = xo;
+  } else {
+    f32x4 xo;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) xo[c] = fmaxf(fmaf(ao1[lane * pa], a[c][0], net.ao_b1[lane]), 0.f);
+    *reinterpret_cast<f32x4*>(xb + 4 * lane) = xo;
+  }
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int c = 0; c < 4; ++c) acc[c] = sadv;
+#pragma unroll 8
+  for (int j = 0; j < kH; ++j) {
+    const float w = w1s[lane * kPitch + j];
+    const f32x4 x = *reinterpret_cast<const f32x4*>(xb + 4 * j);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) acc[c] = fmaf(w, x[c], acc[c]);
+  }
+#pragma unroll
+  for (int c = 0; c < 4; ++c) qv[c] = wave_sum(w2eff[lane] * fmaxf(acc[c], 0.f)) + b2eff;
+  __builtin_amdgcn_wave_barrier();
 }
 
 // first argmax of q[0..T) by one wave (lowest index on ties), then aql_select_k's epsilon draw:
@@ -297,6 +366,60 @@ __device__ __forceinline__ void env_dynamics(const AqlEnv& V, int e, int lane, c
     if (lane == 0) {
       ph[0] = nth;
       ph[1] = nthd;
+    }
+  }
+}
+
+// reset env e (one wave): new observation into obs_buf / phys
+__device__ __forceinline__ void env_reset_one(const AqlEnv& V, int e, int lane, uint64_t ctr) {
+  env_reset_state(V.kind, V.seed, e, lane, ctr, V.obs_buf + (size_t)e * V.obs, V.phys + (size_t)e * 4);
+  if (lane == 0) {
+    V.ep_len[e] = 0;
+    V.ep_ret[e] = 0.f;
+  }
+}
+
+// One env's step by one wave: dynamics, reward, the raw transition into replay slot `slot`,
+// episode bookkeeping / reset.  `a`: this env's action vector (adim floats; the discrete envs'
+// action index as a float), `aidx`: its candidate index.
+__device__ __forceinline__ void env_step_wave(const AqlEnv& V, int e, int lane, const float* a_in, int aidx,
+                                              const float* __restrict__ amu, const AqlInsert& I, int64_t slot,
+                                              uint64_t ctr) {
+  const int obs = V.obs;
+  const float* s = V.obs_buf + (size_t)e * obs;
+  float s2, r;
+  bool term;
+  env_dynamics(V, e, lane, s, V.phys + (size_t)e * 4, a_in, ctr, s2, r, term);
+  const int len = V.ep_len[e] + 1;
+  const bool done = term || len >= V.max_steps;  // TimeLimit sets done (stored as terminal)
+  // raw transition into the replay ring
+  if (lane < obs) {
+    I.st[slot * obs + lane] = s[lane];
+    I.st2[slot * obs + lane] = s2;
+  }
+  const int TA = V.T * V.adim;
+  for (int k = lane; k < TA; k += 64) I.amu[slot * TA + k] = amu[(size_t)e * TA + k];
+  if (lane == 0) {
+    I.act[slot] = aidx;
+    I.rew[slot] = r;
+    I.done[slot] = done ? 1.f : 0.f;
+    I.slots[e] = (int)slot;
+  }
+  __builtin_amdgcn_wave_barrier();
+  if (done) {
+    if (lane == 0) {
+      const int k = atomicAdd(V.ep_count, 1);
+      float* lg = V.ep_log + (size_t)(k % V.log_cap) * 2;
+      lg[0] = V.ep_ret[e] + r;
+      lg[1] = (float)len;
+    }
+    __builtin_amdgcn_wave_barrier();
+    env_reset_one(V, e, lane, ctr);
+  } else {
+    if (lane < obs) V.obs_buf[(size_t)e * obs + lane] = s2;
+    if (lane == 0) {
+      V.ep_len[e] = len;
+      V.ep_ret[e] += r;
     }
   }
 }

@@ -963,8 +963,10 @@ __device__ __forceinline__ void update_block(const AqlStep& D, int bid, float g,
     b2 = D.v[im];
     pm = D.p[im];
     gm = D.G.grad[im];
-    if (kind == 2) {
-      const AqlNoise& z = D.P.layer[l];
+    const AqlNoise& z = D.P.layer[l];
+    if (D.keep_noise) {  // (AQL.py never resets the noise: the epsilon in memory stays)
+      ep = kind == 2 ? z.weps[e] : z.beps[e];
+    } else if (kind == 2) {
       const int o = (int)(e / z.in), c = (int)(e - (int64_t)o * z.in);
       ep = noise_w(D.P.seed, l, o, c, st);
     } else {
@@ -972,7 +974,12 @@ __device__ __forceinline__ void update_block(const AqlStep& D, int bid, float g,
     }
   }
   float lr;
-  const AdamRule rule = make_rule(D.hp, (int64_t)st, lr);
+  AdamParams hp = D.hp;
+  if (D.cosine) {  // CosineAnnealingLR's closed form at step st, in fp64, rounded once
+    hp.lr0 = (float)(D.cos_eta_min + (D.cos_lr0 - D.cos_eta_min) * (1.0 + cos(M_PI * (double)st / D.cos_T_max)) / 2.0);
+    hp.lr_gamma = 1.f;
+  }
+  const AdamRule rule = make_rule(hp, (int64_t)st, lr);
   const NormInfo nq = reduce_norms(D.G.part, D.nblk, D.hp.max_norm, D.hp.grad_scale);
   __syncthreads();  // reduce_norms' LDS is reused
   const NormInfo np = reduce_norms(D.G.part + D.nblk, D.nblk, D.hp.max_norm, D.hp.grad_scale);
@@ -992,7 +999,7 @@ __device__ __forceinline__ void update_block(const AqlStep& D, int bid, float g,
   D.v[i] = b;
   D.p[i] = pn;
   if (D.pub_p) D.pub_p[i] = pn;
-  if (prop) D.P.dst[i - D.P_q] = pn;
+  if (prop && !D.no_proposal_copy) D.P.dst[i - D.P_q] = pn;
   if (kind >= 2) {
     const AqlNoise& z = D.P.layer[l];
     const float mun = rule(pm, opaque(gm * nq.clip), a2, b2);
@@ -1001,11 +1008,11 @@ __device__ __forceinline__ void update_block(const AqlStep& D, int bid, float g,
     D.p[im] = mun;
     if (D.pub_p) D.pub_p[im] = mun;
     if (kind == 2) {
-      z.weps[e] = ep;
+      if (!D.keep_noise) z.weps[e] = ep;
       if (D.pub_weps[l]) D.pub_weps[l][e] = ep;
       z.weff[e] = fmaf(pn, ep, mun);
     } else {
-      z.beps[e] = ep;
+      if (!D.keep_noise) z.beps[e] = ep;
       if (D.pub_beps[l]) D.pub_beps[l][e] = ep;
       z.beff[e] = fmaf(pn, ep, mun);
     }
@@ -1058,6 +1065,7 @@ __global__ __launch_bounds__(NT) void aql_grad_k(AqlGrad G) {
 // final (the backward launch's priority write, aql_learn_set_tree).  Replaces opt_step2_k +
 // aql_post_k with the same arithmetic (bit-identical, tests/test_gpu_aql_engine.py).
 int aql_update_noise_blocks(const AqlStep& d) {
+  if (d.keep_noise) return 0;  // the target's noise and effective weights stay
   const int64_t n = (int64_t)d.P.layer[2].out * d.P.layer[2].in + d.P.layer[2].out +
                     (int64_t)d.P.layer[3].out * d.P.layer[3].in + d.P.layer[3].out;
   return (int)((n + 255) / 256);
@@ -1092,64 +1100,13 @@ __global__ __launch_bounds__(256) void aql_update_k(const AqlStep* __restrict__ 
 using aqld::kBwAct;
 using aqld::kBwObs;
 
-// reset env e (one wave): new observation into obs_buf / phys
-__device__ void env_reset_one(const AqlEnv& V, int e, int lane, uint64_t ctr) {
-  aqld::env_reset_state(V.kind, V.seed, e, lane, ctr, V.obs_buf + (size_t)e * V.obs, V.phys + (size_t)e * 4);
-  if (lane == 0) {
-    V.ep_len[e] = 0;
-    V.ep_ret[e] = 0.f;
-  }
-}
+using aqld::env_reset_one;  // (reset, step + insert of one env by one wave: aql_dev.h, shared with aql_frame)
+using aqld::env_step_wave;
 
 __global__ __launch_bounds__(256) void aql_env_reset_k(AqlEnv V) {
   const int e = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (e >= V.E) return;
   env_reset_one(V, e, threadIdx.x & 63, 0xFFFFFFFFull);
-}
-
-// One env's step by one wave: dynamics, reward, the raw transition into replay slot `slot`,
-// episode bookkeeping / reset.  `a`: this env's action vector (adim floats; the discrete envs'
-// action index as a float), `aidx`: its candidate index.
-__device__ __forceinline__ void env_step_wave(const AqlEnv& V, int e, int lane, const float* a_in, int aidx,
-                                              const float* __restrict__ amu, const AqlInsert& I, int64_t slot,
-                                              uint64_t ctr) {
-  const int obs = V.obs;
-  const float* s = V.obs_buf + (size_t)e * obs;
-  float s2, r;
-  bool term;
-  aqld::env_dynamics(V, e, lane, s, V.phys + (size_t)e * 4, a_in, ctr, s2, r, term);
-  const int len = V.ep_len[e] + 1;
-  const bool done = term || len >= V.max_steps;  // TimeLimit sets done (stored as terminal)
-  // raw transition into the replay ring
-  if (lane < obs) {
-    I.st[slot * obs + lane] = s[lane];
-    I.st2[slot * obs + lane] = s2;
-  }
-  const int TA = V.T * V.adim;
-  for (int k = lane; k < TA; k += 64) I.amu[slot * TA + k] = amu[(size_t)e * TA + k];
-  if (lane == 0) {
-    I.act[slot] = aidx;
-    I.rew[slot] = r;
-    I.done[slot] = done ? 1.f : 0.f;
-    I.slots[e] = (int)slot;
-  }
-  __builtin_amdgcn_wave_barrier();
-  if (done) {
-    if (lane == 0) {
-      const int k = atomicAdd(V.ep_count, 1);
-      float* lg = V.ep_log + (size_t)(k % V.log_cap) * 2;
-      lg[0] = V.ep_ret[e] + r;
-      lg[1] = (float)len;
-    }
-    __builtin_amdgcn_wave_barrier();
-    env_reset_one(V, e, lane, ctr);
-  } else {
-    if (lane < obs) V.obs_buf[(size_t)e * obs + lane] = s2;
-    if (lane == 0) {
-      V.ep_len[e] = len;
-      V.ep_ret[e] += r;
-    }
-  }
 }
 
 __global__ __launch_bounds__(256) void aql_env_step_k(AqlEnv V, const float* __restrict__ act,
@@ -1396,6 +1353,8 @@ void aql_step_check(const AqlStep& d) {
     throw std::invalid_argument("aql_step: counter / proposal copy");
   if (d.draw && (!d.filled || !d.beta || !d.L.idx || !d.L.w))
     throw std::invalid_argument("aql_step: the next step's draw needs filled / beta / idx / w");
+  if (d.cosine && !(d.cos_T_max > 0.0))
+    throw std::invalid_argument("aql_step: the cosine schedule needs T_max > 0");
   for (int k = 0; k < 2; ++k) {
     const int64_t nw = (int64_t)d.P.layer[k].out * d.P.layer[k].in, nb = d.P.layer[k].out;
     for (int64_t o : {d.mu_w[k], d.sig_w[k]})

@@ -851,6 +851,15 @@ PYBIND11_MODULE(_apex_hip, m) {
       d.pub_weps[0] = P<float>(g("pub_weps0")); d.pub_weps[1] = P<float>(g("pub_weps1"));
       d.pub_beps[0] = P<float>(g("pub_beps0")); d.pub_beps[1] = P<float>(g("pub_beps1"));
     }
+    // the single-process trainer's step (AQL.py): all optional, off by default
+    if (p.contains("keep_noise")) d.keep_noise = p["keep_noise"].cast<int>();
+    if (p.contains("no_proposal_copy")) d.no_proposal_copy = p["no_proposal_copy"].cast<int>();
+    if (p.contains("cos_T_max")) {
+      d.cosine = 1;
+      d.cos_T_max = p["cos_T_max"].cast<double>();
+      d.cos_eta_min = p["cos_eta_min"].cast<double>();
+      d.cos_lr0 = p["cos_lr0"].cast<double>();
+    }
     aql_step_check(d);
     HIP_CHECK(hipMemcpy(reinterpret_cast<void*>(desc), &d, sizeof(AqlStep), hipMemcpyHostToDevice));
     int nb = 0;
@@ -910,6 +919,33 @@ PYBIND11_MODULE(_apex_hip, m) {
     return r;
   });
   m.def("aql_rollout", [](const AqlRollout& r, uint64_t s) { aql_rollout(r, S(s)); });
+  // one env's acting frame of the single-process AQL trainer (aql_frame_kernels.hip)
+  py::class_<AqlFrame>(m, "AqlFrame");
+  m.def("make_aql_frame", [](const AQLNet& net, const AqlEnv& env, const AqlInsert& ins, const TreeHandle& tree,
+                             py::dict d) {
+    auto g = [&](const char* k) { return d[k].cast<uint64_t>(); };
+    auto opt = [&](const char* k) { return d.contains(k) ? d[k].cast<uint64_t>() : (uint64_t)0; };
+    AqlFrame f{};
+    f.net = net;
+    f.V = env;
+    f.I = ins;
+    f.tree = tree.d;
+    f.prop_seed = g("prop_seed"); f.sel_seed = g("sel_seed"); f.eps_seed = g("eps_seed");
+    f.low = P<const float>(opt("low")); f.high = P<const float>(opt("high")); f.var = P<const float>(opt("var"));
+    f.t = P<int64_t>(g("t")); f.filled = P<int64_t>(g("filled"));
+    f.max_prio = P<const float>(g("max_prio")); f.alpha = d["alpha"].cast<float>();
+    f.eps_hi = d["eps_hi"].cast<float>(); f.eps_lo = d["eps_lo"].cast<float>(); f.eps_p = d["eps_p"].cast<float>();
+    f.beta0 = d["beta0"].cast<double>(); f.beta_max_step = d["beta_max_step"].cast<double>();
+    f.beta_out = P<float>(g("beta_out")); f.act_idx = P<int>(g("act_idx")); f.env_act = P<float>(g("env_act"));
+    f.eps_out = P<float>(g("eps_out")); f.reward = P<float>(g("reward")); f.done = P<float>(g("done"));
+    f.q_out = P<float>(opt("q_out"));
+    return f;
+  });
+  m.def("aql_frame", [](const AqlFrame& f, uint64_t s) { aql_frame(f, S(s)); });
+  m.def("aql_frame_eps", [](uint64_t eps_seed, uint64_t t, float eps_hi, float eps_lo, float eps_p, uint64_t eps_out,
+                            uint64_t s) {
+    aql_frame_eps(eps_seed, P<const int64_t>(t), eps_hi, eps_lo, eps_p, P<float>(eps_out), S(s));
+  });
   py::class_<AqlTail>(m, "AqlTail");
   m.def("make_aql_tail", [](const AqlEnv& env, const AqlInsert& ins, const TreeHandle& tree, py::dict d) {
     auto g = [&](const char* k) { return d[k].cast<uint64_t>(); };

@@ -605,6 +605,15 @@ struct AqlStep {
   float* pub_weps[2];
   float* pub_beps[2];
   const int* gate;  // step gate (AqlLearn::gate); the step index is aql_update's gate_j
+  // The single-process trainer's step (AQL.py; all off by default).  keep_noise: no fresh noise
+  // for either critic -- the online effective weights are recomputed from the updated mu / sigma
+  // and the noise in memory (aql_post(regen = 0)'s arithmetic), the target's noise and effective
+  // weights are not touched (no noise workgroups).  no_proposal_copy: the target's proposal
+  // parameters are left alone.  cosine: both Adam steps use CosineAnnealingLR's closed form
+  // lr(k) = eta_min + (lr0 - eta_min) (1 + cos(pi k / T_max)) / 2 at the step counter k,
+  // evaluated in fp64 and rounded to fp32 once (it is the lr written to norms_q / norms_p [3]).
+  int keep_noise, no_proposal_copy, cosine;
+  double cos_lr0, cos_eta_min, cos_T_max;
 };
 void aql_step_check(const AqlStep& d);
 int aql_update_grid(const AqlStep& d, int* noise_blocks);
@@ -678,6 +687,37 @@ struct AqlRollout {
   int trace_T;
 };
 void aql_rollout(const AqlRollout& r, hipStream_t s);
+// One env's whole acting frame of the single-process AQL trainer (AQL.py) in one launch
+// (aql_frame_kernels.hip, one 512-thread workgroup): proposal -> candidate set -> critic with the
+// online net in train mode -> this frame's epsilon -> epsilon-greedy selection -> env step ->
+// the transition into ring slot `filled mod C` with its leaf at max_prio^alpha and every level of
+// its path -> filled += 1, the learner's beta(t), t += 1.  The Philox keys are the stepwise
+// kernels' (aql_propose / aql_select / aql_env_step) for env 0 at counter t.
+struct AqlFrame {
+  AQLNet net;          // the ONLINE net, noisy = 1 (train mode)
+  AqlEnv V;            // E = 1; V.counter is the frame counter `t`
+  AqlInsert I;         // the replay ring; I.filled is `filled`; I.slots[0] receives the slot
+  TreeDesc tree;
+  uint64_t prop_seed, sel_seed, eps_seed;
+  const float *low, *high, *var;  // action bounds / proposal variance [adim] (continuous)
+  int64_t* t;          // frame counter (+1)
+  int64_t* filled;     // (+1)
+  const float* max_prio;
+  float alpha;
+  float eps_hi, eps_lo, eps_p;  // epsilon = u > eps_p ? eps_hi : eps_lo (AQL.py: 0.5, 0.05, 0.1)
+  double beta0, beta_max_step;  // beta(t) = min(1, beta0 + t (1 - beta0) / beta_max_step)
+  float* beta_out;     // [1]
+  int* act_idx;        // [1] the selected candidate
+  float* env_act;      // [adim] its action
+  float* eps_out;      // [1]
+  float* reward;       // [1]
+  float* done;         // [1]
+  float* q_out;        // optional [T]: the frame's Q row (tests)
+};
+void aql_frame(const AqlFrame& f, hipStream_t s);
+// this frame's epsilon alone (the launch-by-launch yardstick): aql_frame's draw into eps_out[0]
+void aql_frame_eps(uint64_t eps_seed, const int64_t* t, float eps_hi, float eps_lo, float eps_p, float* eps_out,
+                   hipStream_t s);
 // rows 0..E-1 of the staging tables ``src`` -> ring slots (dst.filled + e) % dst.C (slot list in dst.slots)
 void aql_apply_staged(const AqlInsert& src, const AqlInsert& dst, int E, int obs, int TA, hipStream_t s);
 

@@ -17,6 +17,11 @@ annealed over ``max_step``, behaviour epsilon 0.5 w.p. .9 else 0.05).
 ``train_AQL_dis`` = AQL_dis.py (BatchRecorder of CPU AQL workers, weights broadcast
 every outer iteration, ``total_ep_len // batch`` SGD steps per iteration, target sync
 every 20 iterations, checkpoint every 200).
+
+``python -m apex_amd.trainers.aql --engine gpu`` (the non-``--dis`` form) runs ``AQL.py``'s loop
+device-resident on :class:`apex_amd.engine.aql_frame.AQLFrameEngine` (GPU env, five launches
+per frame, same ``model{t}.pth`` artefacts); without a GPU it raises
+``RuntimeError(GPU_ENGINE_ERROR)``.
 """
 from __future__ import annotations
 
@@ -343,6 +348,60 @@ class train_AQL_dis(_AQLBase):  # AQL_dis.py train_DQN
         return getattr(self.recoder, "episodes", self.recoder.episode_idx)
 
 
+GPU_ENGINE_ERROR = "--engine gpu needs a ROCm GPU (torch.cuda.is_available() is False); use --engine host"
+
+
+def train_gpu(a) -> list[dict]:
+    """``--engine gpu``: ``AQL.py``'s loop on :class:`apex_amd.engine.aql_frame.AQLFrameEngine`.
+    Frames run in windows that end at the next save / log / evaluation frame, with no host sync
+    inside a window.  One JSON line per ``--log-interval`` frames (frames/s, the loss means from
+    the device accumulators, beta, lr, finished-episode returns) and per ``--eval-interval``
+    frames (the greedy return of 10 rollouts); the records are returned."""
+    import json
+
+    if not torch.cuda.is_available():
+        raise RuntimeError(GPU_ENGINE_ERROR)
+    from ..engine.aql_frame import AQLFrameConfig, AQLFrameEngine
+
+    max_step = int(a.max_step or 1e6)
+    save_interval = max(1, int(a.save_interval))
+    log_interval = max(1, int(a.log_interval))
+    eval_interval = max(0, int(a.eval_interval))
+    cfg = AQLFrameConfig(env_id=a.env or "Pendulum-v0", max_step=max_step, save_interval=save_interval,
+                         track_losses=True, seed=0 if a.seed is None else a.seed)
+    eng = AQLFrameEngine(cfg, a.device if a.device is not None else "cuda:0")
+    os.makedirs(a.save_dir, exist_ok=True)
+    records = []
+    t_win, f_win = 0.0, 0
+    t = 0   # frames done
+    while t < max_step:
+        # the window ends with the next frame after which something is due on the host
+        stops = [max_step - 1, t - t % save_interval + (0 if t % save_interval == 0 else save_interval),
+                 t - t % log_interval + log_interval - 1]
+        if eval_interval:
+            stops.append(t - t % eval_interval + eval_interval - 1)
+        last = min(stops)
+        t_win += eng.run(last + 1 - t)
+        t = last + 1
+        if last % save_interval == 0 or last == max_step - 1:
+            eng.save(last, a.save_dir)
+        ev = eval_interval and t % eval_interval == 0
+        if t % log_interval == 0 or last == max_step - 1 or ev:
+            st = eng.stats()   # (syncs)
+            lq, lp, n = eng.learner.take_loss_means()
+            eps_done = eng.finished_episodes()
+            rec = {"frame": last, "frames_per_s": (t - f_win) / max(t_win, 1e-9),
+                   "loss_q": lq if n else None, "loss_proposal": lp if n else None, "beta": st["beta"],
+                   "lr": st["lr"] if n else None, "episodes": len(eps_done),
+                   "mean_return": float(np.mean([r for r, _ in eps_done])) if eps_done else None}
+            if ev:
+                rec["eval_return"] = float(np.mean(eng.rollout_evaluate(10)))
+            print(json.dumps(rec), flush=True)
+            records.append(rec)
+            t_win, f_win = 0.0, t
+    return records
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description="AQL trainers (AQL.py / AQL_dis.py)")
     p.add_argument("--dis", action="store_true", help="multi-worker AQL_dis trainer")
@@ -350,7 +409,20 @@ def main(argv=None):
     p.add_argument("--max-step", type=float, default=None)
     p.add_argument("--n-workers", type=int, default=10)
     p.add_argument("--save-dir", default=".")
+    p.add_argument("--engine", choices=["host", "gpu"], default="host",
+                   help="(without --dis) gpu: the GPU-resident engine (apex_amd.engine.aql_frame) instead of the "
+                        "host loop")
+    p.add_argument("--seed", type=int, default=None, help="(gpu engine) the engine's seed")
+    p.add_argument("--device", default=None, help="(gpu engine) the device, default cuda:0")
+    p.add_argument("--save-interval", type=float, default=1e4, help="(gpu engine) model{t}.pth every N frames")
+    p.add_argument("--log-interval", type=int, default=1000, help="(gpu engine) one JSON line per N frames")
+    p.add_argument("--eval-interval", type=int, default=0,
+                   help="(gpu engine) greedy return of 10 rollouts every N frames (0: never)")
     a = p.parse_args(argv)
+    if a.engine == "gpu":
+        if a.dis:
+            p.error("--engine gpu applies to the single-process trainer; the distributed form is apex_amd.train_aql")
+        return train_gpu(a)
     if a.dis:
         t = train_AQL_dis(a.env or "CartPole-v0", max_step=a.max_step or 1e6, n_workers=a.n_workers,
                           save_dir=a.save_dir)
