@@ -1,0 +1,403 @@
+"""The fused Ape-X engine over HOST environments: gym-API Atari emulators stepped on the CPU
+under the HBM replay, the on-device n-step batcher and the fused learner of
+:mod:`apex_amd.engine.apex`.
+
+``ActorShard`` hard-wires the GPU sprite game.  :class:`HostEnvShard` is the same shard with a
+different front end: a raw vector env (:mod:`apex_amd.envs.raw_vector` protocol) hands over the
+two unpooled RGB frames of every env's observation, one H2D copy moves them, and one kernel
+(``host_env_ingest``, ops/csrc/host_env_kernels.hip) does the pixel work of the host pipeline --
+max-pool, grey, fp64 area resize, round, transpose -- straight into the frame ring at the slot
+``vec_env_step`` would have written, with the same reward / done / new_frame / ep_log outputs.
+The actor forward with its eps-greedy epilogue, ``nstep_emit``, ``write_batch`` and the
+learner graph are shared with the GPU-env engine, unchanged.
+
+:class:`HostEnvEngine` overlaps the two sides on ONE stream: per iteration it enqueues the
+actor forward, copies the actions out, enqueues ``k`` learner steps, and only then steps the
+emulators on the host -- the GPU trains while the CPU emulates.
+
+Out of scope here: double-banked env groups (stepping one half of the envs while the other
+half's forward runs), a device evaluator, and the multi-GPU topologies (``parallel/``,
+``engine/central.py``); worker processes / threads for the emulators live behind the vector-env
+protocol, not in this module.
+"""
+from __future__ import annotations
+
+import copy
+import time
+from dataclasses import dataclass, field
+
+import numpy as np
+import torch
+
+from .. import ops
+from ..algo.schedules import actor_epsilon
+from ..envs.preprocess import area_weights
+from ..models.dqn import DuelingDQN
+from ..models.fused import make_hip_net, make_workspace
+from ..utils.checkpoint import save_model
+from .hbm_replay import HBMReplay
+from .learner import DQNLearner, LearnerConfig, forward_q
+
+OUT = 84          # the warp's output side (kHostEnvOut)
+TAP_WIDTH = 8     # weights per output index in the tap tables (kHostEnvTaps)
+
+
+# ---------------------------------------------------------------------------- tap tables
+def tap_tables(n_in: int, n_out: int = OUT, width: int = TAP_WIDTH):
+    """``area_weights(n_out, n_in)`` in compact form: (first [n_out] int32, count [n_out] int32,
+    weight [n_out, width] float64) -- output ``o`` reads inputs ``first[o] .. first[o] + count[o] - 1``.
+    The weights are the dense matrix's own values, so the dense rebuild is exact."""
+    if n_in < n_out:
+        raise ValueError(f"the warp only shrinks: {n_in} input pixels < {n_out} output pixels")
+    w = area_weights(n_out, n_in)
+    nz = w > 0
+    first = nz.argmax(1)
+    last = n_in - 1 - nz[:, ::-1].argmax(1)
+    count = last - first + 1
+    if int(count.max()) > width:
+        raise ValueError(f"{int(count.max())} taps per output pixel ({n_in} -> {n_out}) exceed the table width {width}")
+    weight = np.zeros((n_out, width), dtype=np.float64)
+    for o in range(n_out):
+        weight[o, :count[o]] = w[o, first[o]:first[o] + count[o]]
+    return first.astype(np.int32), count.astype(np.int32), weight
+
+
+def dense_from_taps(first, count, weight, n_in: int) -> np.ndarray:
+    """The dense [n_out, n_in] matrix a tap table stands for."""
+    w = np.zeros((len(first), n_in), dtype=np.float64)
+    for o in range(len(first)):
+        w[o, first[o]:first[o] + count[o]] = weight[o, :count[o]]
+    return w
+
+
+class Ingest:
+    """Device tap tables + params of ``host_env_ingest`` for one (H, W, ring) geometry, and the
+    launch.  Construction raises ``ValueError`` for H or W below 84 or an over-wide tap count."""
+
+    def __init__(self, E: int, H: int, W: int, frame_bytes: int, frame_capacity: int, clip_rewards: bool, device):
+        tabs = [tap_tables(H), tap_tables(W)]  # (raises before the device is touched)
+        self.hip = ops.hip()
+        assert self.hip.HOST_ENV_TAPS == TAP_WIDTH
+        self._keep = []
+        self.taps = []
+        for first, count, weight in tabs:
+            t = [torch.from_numpy(a).to(device) for a in (first, count, weight)]
+            self._keep.append(t)
+            self.taps.append(self.hip.make_host_env_taps(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(),
+                                                         int(count.max())))
+        self.params = self.hip.HostEnvParams(E, frame_bytes, frame_capacity, int(clip_rewards), H, W)
+
+    def __call__(self, raw, reward_in, done_in, frames, step_counter, reset: bool, reward, done, new_frame, hist, acc,
+                 ep_log) -> None:
+        self.hip.host_env_ingest(raw.data_ptr(), reward_in.data_ptr(), done_in.data_ptr(), self.taps[0], self.taps[1],
+                                 frames.data_ptr(), self.params, step_counter.data_ptr(), bool(reset),
+                                 reward.data_ptr(), done.data_ptr(), new_frame.data_ptr(), hist.data_ptr(),
+                                 acc.data_ptr(), ep_log.data_ptr(), torch.cuda.current_stream().cuda_stream)
+
+
+# ---------------------------------------------------------------------------- shard
+class HostEnvShard:
+    """``ActorShard``'s interface (``st``, ``q``, ``actions``, ``reward``, ``done``, ``new_frame``,
+    ``slot``, ``prio``, ``ep_log``, ``step_counter``, ``eps``, ``act_args()``, ``observe()``,
+    ``episode_stats()``) over a host vector env.  ``ep_log`` column 3 is the episode's unclipped
+    score."""
+
+    def __init__(self, replay, n_envs: int, n_actions: int, raw_shape, n_step: int = 3, gamma: float = 0.99,
+                 eps_base: float = 0.4, eps_alpha: float = 7.0, actor_offset: int = 0, total_actors: int | None = None,
+                 seed: int = 0, mode: str = "reference", clip_rewards: bool = True):
+        self.replay = replay
+        self.E, self.A, self.n = int(n_envs), int(n_actions), int(n_step)
+        assert replay.n_envs == self.E, "replay slot layout is sized for this shard's env count"
+        H, W, C = (int(x) for x in raw_shape)
+        if C != 3:
+            raise ValueError("raw emulator frames must be RGB [H, W, 3]")
+        dev = replay.device
+        self.device = dev
+        self.seed = int(seed)
+        E, A, n = self.E, self.A, self.n
+        self.ingest = Ingest(E, H, W, replay.frame_bytes, replay.frame_capacity, clip_rewards, dev)
+        self.hip = self.ingest.hip
+        total = total_actors if total_actors is not None else E
+        ids = torch.arange(actor_offset, actor_offset + E, dtype=torch.float64)
+        self.eps = torch.as_tensor(actor_epsilon(ids.numpy(), total, eps_base, eps_alpha), dtype=torch.float32,
+                                   device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.new_frame = torch.zeros(E, **i32)
+        self.ep_log = torch.zeros(E, 4, **f32)
+        self.acc = torch.zeros(E, 4, **f32)      # running (return, raw return, length, -) per env
+        self.q = torch.zeros(E, A, **f32)
+        self.actions = torch.zeros(E, **i32)
+        self.reward = torch.zeros(E, **f32)
+        self.done = torch.zeros(E, **f32)
+        self.slot = torch.zeros(E, **i32)
+        self.prio = torch.zeros(E, **f32)
+        self.obs = torch.zeros(E, 4, 84, 84, dtype=torch.uint8, device=dev)
+        self.step_counter = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.st = {
+            "win_ids": torch.zeros(E, n, 4, **i32), "win_a": torch.zeros(E, n, **i32),
+            "win_r": torch.zeros(E, n, **f32), "win_q": torch.zeros(E, n, A, **f32),
+            "win_meta": torch.zeros(E, 4, **i32), "hist": torch.zeros(E, 4, **i32),
+            "drain_ids": torch.zeros(E, n, 4, **i32), "drain_a": torch.zeros(E, n, **i32),
+            "drain_r": torch.zeros(E, n, **f32), "drain_q": torch.zeros(E, n, **f32),
+            "drain_meta": torch.zeros(E, 2, **i32), "drain_s2": torch.zeros(E, 4, **i32),
+        }
+        if mode not in ("reference", "textbook"):
+            raise ValueError("mode must be 'reference' or 'textbook'")
+        st_ptrs = {k: v.data_ptr() for k, v in self.st.items()}
+        self.nstep = self.hip.make_nstep(E, A, n, replay.capacity, float(gamma), 0 if mode == "reference" else 1,
+                                         st_ptrs, replay.trans_ptrs())
+        # host staging (pinned: the copies below are truly asynchronous) and the device twins
+        self.raw_host = torch.zeros(E, 2, H, W, 3, dtype=torch.uint8).pin_memory()
+        self.raw_np = self.raw_host.numpy()
+        self.raw_dev = torch.zeros(E, 2, H, W, 3, dtype=torch.uint8, device=dev)
+        self.reward_host = torch.zeros(E, dtype=torch.float32).pin_memory()
+        self.done_host = torch.zeros(E, dtype=torch.float32).pin_memory()
+        self.actions_host = torch.zeros(E, dtype=torch.int32).pin_memory()
+        self.reward_in = torch.zeros(E, **f32)
+        self.done_in = torch.zeros(E, **f32)
+        self.event = torch.cuda.Event()
+        self.raw_bytes_per_step = self.raw_host.numel() + 8 * E
+
+    def _ingest(self, reset: bool) -> None:
+        self.ingest(self.raw_dev, self.reward_in, self.done_in, self.replay.frames, self.step_counter, reset,
+                    self.reward, self.done, self.new_frame, self.st["hist"], self.acc, self.ep_log)
+
+    def reset(self, vec) -> None:
+        """Start every env; the start frames fill the stacks (``vec_env_reset``'s outputs).  The
+        copy out of the pinned buffer is ordered like a step's (see :meth:`finish`)."""
+        vec.reset(self.raw_np)
+        self.raw_dev.copy_(self.raw_host, non_blocking=True)
+        self._ingest(True)
+
+    def observe(self) -> torch.Tensor:
+        """Current stacked observations u8 [E,4,84,84] (gathered from the frame ring)."""
+        self.replay.gather_frames(self.st["hist"], self.obs)
+        return self.obs
+
+    def act_args(self) -> tuple:
+        """(eps, rng seed, step counter, actions) pointers for the heads kernel's eps-greedy
+        epilogue -- ``ActorShard.act_args``."""
+        return (self.eps.data_ptr(), self.seed ^ 0x5E1EC7, self.step_counter.data_ptr(), self.actions.data_ptr())
+
+    def select(self, q: torch.Tensor | None = None) -> None:
+        """eps-greedy on ``self.q`` (or ``q``) with the standalone kernel: the same draw as the
+        heads epilogue (for a policy that does not pick the actions itself)."""
+        if q is not None and q.data_ptr() != self.q.data_ptr():
+            self.q.copy_(q)
+        self.hip.select_actions(self.q.data_ptr(), self.E, self.A, self.eps.data_ptr(), self.seed ^ 0x5E1EC7,
+                                self.step_counter.data_ptr(), self.actions.data_ptr(),
+                                torch.cuda.current_stream().cuda_stream)
+
+    def begin(self) -> None:
+        """After the forward picked ``self.actions``: start their copy to the host and mark the
+        point the host has to wait for."""
+        self.actions_host.copy_(self.actions, non_blocking=True)
+        self.event.record()
+
+    def finish(self, vec) -> None:
+        """Wait for the actions, step the host envs, ship the pairs and run the device half of
+        the actor step (ingest, n-step emit, tree write; the write advances ``step_counter``).
+
+        One staging buffer is enough: iteration t's H2D copies are enqueued BEFORE iteration
+        t+1's forward on the same stream, and the host waits for the event recorded after that
+        forward before it writes the pinned buffers again -- when the wait returns, every copy
+        that read them has completed.  (The same holds for the pinned reward / done / actions
+        buffers, and for the copy :meth:`reset` starts.)"""
+        self.event.synchronize()
+        r, d = vec.step(self.actions_host.numpy(), self.raw_np)
+        self.reward_host.numpy()[:] = r
+        self.done_host.numpy()[:] = d
+        self.raw_dev.copy_(self.raw_host, non_blocking=True)
+        self.reward_in.copy_(self.reward_host, non_blocking=True)
+        self.done_in.copy_(self.done_host, non_blocking=True)
+        self._ingest(False)
+        s = torch.cuda.current_stream().cuda_stream
+        self.hip.nstep_emit(self.nstep, self.q.data_ptr(), self.actions.data_ptr(), self.reward.data_ptr(),
+                            self.done.data_ptr(), self.new_frame.data_ptr(), self.step_counter.data_ptr(),
+                            self.slot.data_ptr(), self.prio.data_ptr(), s, False)
+        self.replay.write_batch(pre=(self.slot, self.prio, self.replay.filled), bump=self.step_counter)
+
+    def step_host(self, vec) -> None:
+        """Both halves back to back (``self.actions`` already chosen)."""
+        self.begin()
+        self.finish(vec)
+
+    def episode_stats(self) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(last episode return, last episode length, finished episode count) per env."""
+        return self.ep_log[:, 0], self.ep_log[:, 1], self.ep_log[:, 2]
+
+    def episode_scores(self) -> torch.Tensor:
+        """Last episode's unclipped score per env (``ep_log`` column 3)."""
+        return self.ep_log[:, 3]
+
+
+# ---------------------------------------------------------------------------- engine
+@dataclass
+class HostEnvConfig:
+    """The ``EngineConfig`` fields that apply to host envs; ``n_envs`` / ``n_actions`` come from
+    the vector env."""
+    replay_capacity: int = 2_000_000
+    alpha: float = 0.6
+    threshold_size: int = 50_000
+    learner_steps_per_actor_step: int = 1     # k >= 0 learner steps enqueued per iteration
+    publish_param_interval: int = 25
+    target_update_interval: int = 2500
+    nstep_mode: str = "reference"
+    eps_base: float = 0.4
+    eps_alpha: float = 7.0
+    actor_offset: int = 0
+    total_actors: int | None = None
+    clip_rewards: bool = True
+    action_repeat: int = 4                    # emulator frames per env step (frames/s accounting only)
+    use_graphs: bool = True
+    warmup_learner_steps: int = 3             # eager learner steps before the graph is captured
+    exact_mass: bool = False
+    seed: int = 1122
+    learner: LearnerConfig = field(default_factory=LearnerConfig)
+
+
+class HostEnvEngine:
+    def __init__(self, cfg: HostEnvConfig, vec, device: str | torch.device = "cuda", model=None):
+        k = cfg.learner_steps_per_actor_step
+        if not isinstance(k, int) or isinstance(k, bool) or k < 0:
+            raise ValueError("learner_steps_per_actor_step must be an int >= 0")
+        self.cfg = cfg
+        self.vec = vec
+        self.device = torch.device(device)
+        lc = cfg.learner
+        E, A = len(vec), int(vec.n_actions)
+        self.E, self.A = E, A
+        torch.manual_seed(cfg.seed)
+        self.replay = HBMReplay(cfg.replay_capacity, E, lc.n_step, cfg.alpha, self.device, exact_mass=cfg.exact_mass,
+                                seed=cfg.seed)
+        self.actor = HostEnvShard(self.replay, E, A, vec.raw_shape, lc.n_step, lc.gamma, cfg.eps_base, cfg.eps_alpha,
+                                  cfg.actor_offset, cfg.total_actors, cfg.seed, cfg.nstep_mode, cfg.clip_rewards)
+        model = model if model is not None else DuelingDQN.from_shapes((4, 84, 84), A)
+        self.learner = DQNLearner(model, self.replay, lc)
+        self.actor_model = copy.deepcopy(self.learner.model)
+        self.actor_model._flat = None
+        self.actor_flat = self.actor_model.flatten_parameters()
+        for p in self.actor_model.parameters():
+            p.requires_grad_(False)
+            p.grad = None
+        self.hip_net = lc.forward == "hip"
+        if self.hip_net:
+            self.actor_net = make_hip_net(self.actor_model, lc.dtype)
+            self.actor_ws = make_workspace(E, A, self.device, lc.dtype)
+            self.actor_ws.q = self.actor.q  # the heads kernel writes the actor's Q in place
+        self.publish_params()
+        self.learn_steps = 0
+        self.actor_steps = 0
+        self._g_learn = None
+        self._learning = False
+        self.actor.reset(vec)
+
+    # ------------------------------------------------------------------ bodies
+    def publish_params(self) -> None:
+        """Learner -> actor weights (``ApexEngine.publish_params``)."""
+        self.learner.copy_params_to(self.actor_flat)
+        if self.hip_net:
+            self.actor_net.copy_packed_from(self.learner.net)
+
+    def _forward(self) -> None:
+        a = self.actor
+        if self.hip_net:  # conv1 reads the stacks from the ring; the heads kernel picks the actions
+            self.actor_net(self.replay.frames, self.actor_ws, a.st["hist"], act=a.act_args())
+            return
+        with torch.no_grad():
+            q = forward_q(self.actor_model, a.observe(), self.cfg.learner.dtype == "bf16")
+        a.select(q)
+
+    def _learn_body(self) -> None:
+        self.learner.forward_phase()
+        self.learner.optimize()
+
+    def _learner_step(self) -> None:
+        if self._g_learn is not None:
+            self._g_learn.replay()
+        else:
+            self._learn_body()
+        self.learn_steps += 1
+        if self.learn_steps % self.cfg.publish_param_interval == 0:
+            self.publish_params()
+        if self.learn_steps % self.cfg.target_update_interval == 0:
+            self.learner.sync_target()
+
+    def capture(self) -> None:
+        """Warm up with ``warmup_learner_steps`` eager learner steps on a side stream (real
+        steps, counted, cadences kept), then capture one learner step as a hipGraph.  The
+        replay must hold transitions.  Called by :meth:`iteration` when learning starts; with
+        ``use_graphs=False`` the same warm-up steps run and nothing is captured, so both
+        modes execute the same sequence of steps."""
+        if self._learning:
+            return
+        self._learning = True
+        cur = torch.cuda.current_stream(self.device)
+        s = torch.cuda.Stream(device=self.device)
+        s.wait_stream(cur)
+        with torch.cuda.stream(s):
+            for _ in range(self.cfg.warmup_learner_steps):
+                self._learner_step()
+        cur.wait_stream(s)
+        if not self.cfg.use_graphs:
+            return
+        torch.cuda.synchronize(self.device)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            self._learn_body()
+        # (capture records, it does not run: the step counters are untouched)
+        self._g_learn = g
+
+    def held(self) -> int:
+        """Transitions in the replay, from the host's own count (no device read)."""
+        return min(self.actor_steps * self.E, self.replay.capacity)
+
+    def iteration(self) -> None:
+        """Actor forward + action copy-out | k learner steps | host env step + device ingest.
+        The learner steps are already queued when the host starts emulating; the host's only
+        wait is for the event recorded right after the forward."""
+        self._forward()
+        self.actor.begin()
+        k = self.cfg.learner_steps_per_actor_step
+        if k and self.held() >= max(self.cfg.threshold_size, 1):
+            if not self._learning:
+                self.capture()
+            for _ in range(k):
+                self._learner_step()
+        self.actor.finish(self.vec)
+        self.actor_steps += 1
+
+    def run(self, n_iterations: int) -> float:
+        torch.cuda.synchronize(self.device)
+        t0 = time.perf_counter()
+        for _ in range(n_iterations):
+            self.iteration()
+        torch.cuda.synchronize(self.device)
+        return time.perf_counter() - t0
+
+    # ------------------------------------------------------------------ reporting
+    @property
+    def frames_per_actor_step(self) -> int:
+        return self.E * int(self.cfg.action_repeat)
+
+    def stats(self) -> dict:
+        """Host view of the learner's last step and the finished episodes (forces a sync)."""
+        out = {"learn_steps": self.learn_steps, "actor_steps": self.actor_steps, "replay_size": len(self.replay)}
+        if self.learn_steps:
+            out.update(self.learner.stats())
+        log = self.actor.ep_log.cpu()
+        fin = log[:, 2] > 0
+        out["episodes"] = int(log[:, 2].sum().item())
+        if bool(fin.any()):
+            out["episode_reward"] = float(log[fin, 0].mean())
+            out["episode_length"] = float(log[fin, 1].mean())
+            out["episode_score"] = float(log[fin, 3].mean())
+        return out
+
+    def state_dict(self):
+        return self.learner.state_dict()
+
+    def save(self, path: str) -> str:
+        """``torch.save(state_dict)`` with the reference keys (utils/checkpoint.py)."""
+        return save_model(self.learner.model, path)

@@ -52,6 +52,7 @@ HIP_SOURCES = [
     "f32_kernels.hip",
     "ipc_kernels.hip",
     "vector_kernels.hip",
+    "host_env_kernels.hip",
     "comm.cpp",
     "ipc.cpp",
 ]

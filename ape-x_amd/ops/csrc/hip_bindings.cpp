@@ -1083,4 +1083,26 @@ PYBIND11_MODULE(_apex_hip, m) {
   m.def("vec_param_count", &vec_param_count);
   m.def("vec_grad_blocks", &vec_grad_blocks);
   m.def("vec_grad", [](const VecGrad& g, uint64_t s) { vec_grad(g, S(s)); });
+
+  // ---- host gym-API envs (engine/host_env.py)
+  py::class_<HostEnvTaps>(m, "HostEnvTaps").def_readonly("max_count", &HostEnvTaps::max_count);
+  m.def("make_host_env_taps", [](uint64_t first, uint64_t count, uint64_t weight, int max_count) {
+    return HostEnvTaps{P<const int>(first), P<const int>(count), P<const double>(weight), max_count};
+  }, py::arg("first"), py::arg("count"), py::arg("weight"), py::arg("max_count"));
+  m.attr("HOST_ENV_TAPS") = kHostEnvTaps;
+  py::class_<HostEnvParams>(m, "HostEnvParams")
+      .def(py::init([](int E, int frame_bytes, int F, int clip, int H, int W) {
+             return HostEnvParams{E, frame_bytes, F, clip, H, W};
+           }),
+           py::arg("E"), py::arg("frame_bytes"), py::arg("F"), py::arg("clip_rewards"), py::arg("H"), py::arg("W"));
+  m.def("host_env_ingest", [](uint64_t raw, uint64_t reward_in, uint64_t done_in, const HostEnvTaps& rows,
+                              const HostEnvTaps& cols, uint64_t frames, const HostEnvParams& p, uint64_t step,
+                              bool reset, uint64_t reward, uint64_t done, uint64_t new_frame, uint64_t hist,
+                              uint64_t acc, uint64_t ep_log, uint64_t s) {
+    host_env_ingest(P<const uint8_t>(raw), P<const float>(reward_in), P<const float>(done_in), rows, cols,
+                    P<uint8_t>(frames), p, P<const int64_t>(step), reset, P<float>(reward), P<float>(done),
+                    P<int>(new_frame), P<int>(hist), P<float>(acc), P<float>(ep_log), S(s));
+  }, py::arg("raw"), py::arg("reward_in"), py::arg("done_in"), py::arg("rows"), py::arg("cols"), py::arg("frames"),
+     py::arg("params"), py::arg("step"), py::arg("reset"), py::arg("reward"), py::arg("done"), py::arg("new_frame"),
+     py::arg("hist"), py::arg("acc"), py::arg("ep_log"), py::arg("s"));
 }

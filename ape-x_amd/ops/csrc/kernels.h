@@ -848,6 +848,36 @@ struct DqnFrame {
 };
 void dqn_frame(const DqnFrame& f, hipStream_t s);
 
+// ---- host_env_kernels.hip (host gym-API Atari envs under the fused Ape-X engine, engine/host_env.py)
+constexpr int kHostEnvOut = 84, kHostEnvTaps = 8;
+// area_weights(84, n) of envs/preprocess.py in compact form: output index o reads inputs
+// first[o] .. first[o] + count[o] - 1 with weight[o][0 .. count[o])
+struct HostEnvTaps {
+  const int* first;       // [84]
+  const int* count;       // [84]
+  const double* weight;   // [84][kHostEnvTaps]
+  int max_count;          // host copy of max(count): checked against kHostEnvTaps before any launch
+};
+struct HostEnvParams {
+  int E;              // envs in this shard
+  int frame_bytes;    // 84*84
+  int F;              // frame-ring capacity (frames)
+  int clip_rewards;
+  int H, W;           // raw emulator frame (210 x 160 for ALE)
+};
+// One launch per actor step.  raw: [E][2][H][W][3] u8, the two unpooled frames of each env's
+// observation.  Env e's plane = round_half_even(rows (0.299 R + 0.587 G + 0.114 B)(max(raw[e][0],
+// raw[e][1])) cols) in fp64, stored transposed (frames[slot][w * 84 + h]) at vec_env_step_k's ring
+// slot: ((t + 1) E + e) mod F, or (t E + e) mod F with `reset` (which also fills hist[e][0..3],
+// zeroes ep_log and acc and leaves reward / done alone).  A step writes reward (sign of reward_in
+// under clip_rewards) / done / new_frame, advances acc[e] = (return, raw return, length, -) and on a
+// done sets ep_log[e] = (return, length, count + 1, raw return).  Throws std::invalid_argument for
+// H or W below 84, a tap count above kHostEnvTaps or misaligned raw / frames, before any launch.
+void host_env_ingest(const uint8_t* raw, const float* reward_in, const float* done_in, const HostEnvTaps& rows,
+                     const HostEnvTaps& cols, uint8_t* frames, const HostEnvParams& p, const int64_t* step_counter,
+                     bool reset, float* reward, float* done, int* new_frame, int* hist, float* acc, float* ep_log,
+                     hipStream_t s);
+
 // ---- central-replay experience transport over HIP IPC (ipc_kernels.hip, parallel/ipc.py)
 struct IpcIngest {
   int kind;                         // 0: Ape-X DQN packets (frames + rows into per-link regions)

@@ -1,0 +1,123 @@
+"""Ape-X on HOST Atari environments under the fused GPU learner:
+``python -m apex_amd.train_host --env SeaquestNoFrameskip-v4 --envs 16 [arguments.py flags]``.
+
+The reference's ``actor.py --env <id>`` case on one GPU: ``--envs`` emulators built by
+``envs.core.make`` (the synthetic ALE-surface emulator of this package, or real ALE wherever gym
+registers the id) are stepped on the host with the reference's start / repeat / life / FIRE
+semantics (``envs.raw_vector.RawAtariVector``); their raw frames are preprocessed on the GPU
+into the HBM frame ring, and the replay, n-step batcher and fused learner are the flagship
+engine's (``engine.host_env.HostEnvEngine``).  ``apex_amd.train`` remains the CLI of the
+GPU-resident envs.
+
+Flags: the reference's (``--env``, ``--episode_life``, ``--clip_rewards``, ``--replay_buffer_size``,
+``--threshold_size``, ``--batch_size``, intervals, ...) plus ``--envs``, ``--learner-steps`` (learner
+steps enqueued per env step), ``--max-step`` (learner steps, 0 = forever), ``--save-path``,
+``--resume`` (model + ``.train.pt`` sidecar, as ``apex_amd.train``) and ``--log-dir``.  Logged every
+``--bps_interval`` learner steps: ``learner/loss``, ``learner/grad_norm``, ``learner/BPS``,
+``actor/episode_reward`` (clipped return), ``actor/episode_length``, ``actor/episode_score``
+(unclipped game score), ``actor/frames_per_sec`` and ``replay/size``.
+"""
+from __future__ import annotations
+
+import sys
+import time
+
+import torch
+
+from .config import args_to_config, build_parser, preset
+
+
+def parser():
+    p = build_parser(preset("origin"), description="Ape-X DQN on MI355X over host gym-API Atari envs")
+    p.add_argument("--envs", type=int, default=16, help="host emulators stepped per actor step")
+    p.add_argument("--learner-steps", type=int, default=1, help="learner steps enqueued per env step (k >= 0)")
+    p.add_argument("--save-path", default="model.pth")
+    p.add_argument("--resume", default=None, help="model.pth (+ .train.pt sidecar) to resume from")
+    p.add_argument("--log-dir", default=None, help="event-file directory (default runs/<time>-<env>-host)")
+    p.add_argument("--no-tb", action="store_true")
+    return p
+
+
+def main(argv=None) -> int:
+    args = parser().parse_args(argv)
+    cfg = args_to_config(args)
+    if not torch.cuda.is_available():
+        raise SystemExit("apex_amd.train_host runs the GPU engine; use apex_amd.roles.* on CPU")
+    device = torch.device("cuda", 0)
+    torch.cuda.set_device(device)
+
+    from .engine.host_env import HostEnvConfig, HostEnvEngine
+    from .engine.learner import LearnerConfig
+    from .envs.core import make
+    from .envs.preprocess import PreprocessSpec
+    from .envs.raw_vector import RawAtariVector
+    from .train import load_engine, save_engine
+
+    L, R = cfg.learner, cfg.replay
+    spec = PreprocessSpec.from_args(cfg.env)
+    vec = RawAtariVector([make(cfg.env.env) for _ in range(args.envs)], spec)
+    vec.seed(cfg.seed)
+    lc = LearnerConfig(batch_size=R.batch_size, n_step=cfg.n_steps, gamma=cfg.gamma, lr=L.lr, rms_alpha=L.rms_alpha,
+                       rms_eps=L.rms_eps, centered=L.centered, max_norm=L.max_norm, lr_gamma=L.lr_gamma,
+                       lr_step_size=L.lr_step_size, beta=R.beta, optimizer=L.optimizer, forward=cfg.kernel.forward,
+                       dtype=cfg.kernel.dtype, seed=cfg.seed)
+    ecfg = HostEnvConfig(replay_capacity=R.replay_buffer_size, alpha=R.alpha, threshold_size=R.threshold_size,
+                         learner_steps_per_actor_step=args.learner_steps,
+                         publish_param_interval=L.publish_param_interval,
+                         target_update_interval=L.target_update_interval, nstep_mode=cfg.actor.nstep_mode,
+                         eps_base=cfg.actor.eps_base, eps_alpha=cfg.actor.eps_alpha,
+                         clip_rewards=bool(cfg.env.clip_rewards), action_repeat=spec.skip,
+                         use_graphs=cfg.kernel.use_graphs, exact_mass=R.exact_mass, seed=cfg.seed, learner=lc)
+    eng = HostEnvEngine(ecfg, vec, device)
+    counters = {}
+    if args.resume:
+        counters = load_engine(eng.learner, args.resume)
+        eng.publish_params()
+    start = int(counters.get("learn_steps", 0))
+    eng.learn_steps = start
+    print(f"{cfg.env.env}: {len(vec)} host envs, {vec.n_actions} actions, raw {vec.raw_shape}; "
+          f"training from step {start}", flush=True)
+
+    writer = None
+    if not args.no_tb:
+        from .utils.tb import SummaryWriter
+
+        writer = SummaryWriter(args.log_dir, comment=f"-{cfg.env.env}-host")
+    max_step = int(L.max_step)
+    bps_every = max(1, L.bps_interval)
+    t_last, step_last, act_last, next_log = time.perf_counter(), start, 0, start + bps_every
+    next_save = (start // L.save_interval + 1) * L.save_interval if L.save_interval else None
+    while not max_step or eng.learn_steps < max_step:
+        eng.iteration()
+        step = eng.learn_steps
+        if step >= next_log:
+            next_log = step + bps_every
+            st = eng.stats()  # (synchronises)
+            now = time.perf_counter()
+            dt = now - t_last
+            line = {"learner/loss": st["loss"], "learner/grad_norm": st["grad_norm"],
+                    "learner/grad_norm_l2": st["grad_norm_l2"], "learner/BPS": (step - step_last) / dt,
+                    "actor/frames_per_sec": (eng.actor_steps - act_last) * eng.frames_per_actor_step / dt}
+            if "episode_reward" in st:
+                line["actor/episode_reward"] = st["episode_reward"]
+                line["actor/episode_length"] = st["episode_length"]
+                line["actor/episode_score"] = st["episode_score"]
+            line["replay/size"] = float(st["replay_size"])
+            t_last, step_last, act_last = now, step, eng.actor_steps
+            print(f"Step: {step} " + " ".join(f"{k}={v:.4g}" for k, v in line.items()), flush=True)
+            if writer is not None:
+                for k, v in line.items():
+                    writer.add_scalar(k, v, step)
+        if next_save is not None and step >= next_save:
+            next_save = (step // L.save_interval + 1) * L.save_interval
+            print("Saving Model..", flush=True)
+            save_engine(eng.learner, args.save_path, {"learn_steps": step, "actor_steps": eng.actor_steps})
+    torch.cuda.synchronize(device)
+    save_engine(eng.learner, args.save_path, {"learn_steps": eng.learn_steps, "actor_steps": eng.actor_steps})
+    if writer is not None:
+        writer.close()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
