@@ -191,6 +191,10 @@ class DQNLearner:
         self.pre_rows = []
         self.tree_rides_used = False  # the last traced trunk backward carried the tree riders
         self.draws_in_conv1 = False   # the last traced forward drew its batch inside conv1
+        # the drawn batch's frame ids of s, written by the folded draw beside (a, r, d) in
+        # self.a / self.r / self.d: the conv1 weight gradient and the loss read row b directly
+        self.batch_fid = torch.zeros(B, 4, dtype=torch.int32, device=dev)
+        self.batch_rows = False       # the last traced forward's draw wrote them
 
     @staticmethod
     def _stream() -> int:
@@ -262,11 +266,16 @@ class DQNLearner:
         forward launch -- the slots, IS weights and rows per_sample writes -- or None when the
         draw keeps its own launch (no fp32 HIP forward, private rows)."""
         rp = self.replay
+        self.batch_rows = False
         if not (self.cfg.draw_in_conv1 and self.hip_net and self.fp32 and self.rows is None):
             return None
         st = {} if rows is None else {"rows_stage": rows[0], "rows_dst": rp.trans_ptrs(),
                                       "rows_slot": rows[1].data_ptr(), "rows_prio": rows[2].data_ptr(),
                                       "rows_E": rows[1].numel()}
+        if self.hip.f32_batch_resolve() & 2:  # the draw also resolves the batch's compact rows
+            st.update(batch_fid=self.batch_fid.data_ptr(), batch_act=self.a.data_ptr(), batch_rew=self.r.data_ptr(),
+                      batch_done=self.d.data_ptr(), batch_src=rp.trans_ptrs())
+            self.batch_rows = True
         return self.hip.make_conv_sample(rp.tree, rp.filled.data_ptr(), self.beta.data_ptr(), rp.seed,
                                          self.step_counter.data_ptr(), self.idx.data_ptr(), self.w.data_ptr(),
                                          int(not rp.exact_mass), **st)
@@ -280,8 +289,13 @@ class DQNLearner:
             # the loss reads (a, r, d) straight out of the transition table.  The three passes
             # share each layer's launch (5 kernels, not 15).
             ids_s, ids_s2, jdx, tab = self._src
+            # the single-process fp32 learner's gradient pass leaves its ReLU sign bits for the
+            # input gradients (the N > 1 learners keep the fp32 masks)
+            bits = bool(self.fp32 and draw is not None and not self.dp_split)
             forward_multi([(self.net, rp.frames, self.ws_s, ids_s, jdx), (self.net, rp.frames, self.ws_s2, ids_s2, jdx),
-                           (self.tnet, rp.frames, self.ws_t, ids_s2, jdx)], draw=draw)
+                           (self.tnet, rp.frames, self.ws_t, ids_s2, jdx)], draw=draw, sign_bits=bits)
+            if draw is not None and self.batch_rows:  # (a, r, d) of row b: the draw's compact rows
+                tab, jdx = SimpleNamespace(action=self.a, reward=self.r, done=self.d), None
             q2t = self.ws_t.q
             m = self.model
             self.hip.dqn_heads_bwd(
@@ -331,13 +345,14 @@ class DQNLearner:
         sumsq = self.fin_partials if self.allreduce is None else None
         rides = self._tree_rides()
         self.tree_rides_used = rides is not None
+        fid = {"batch_fid": self.batch_fid} if self.draws_in_conv1 and self.batch_rows else {}
         if rides is not None:  # the tree write rides the backward launches: no fork / join
             n = self.net.trunk_backward(rp.frames, self.ws_s, ids_s, jdx, extra_jobs=[heads_job], sumsq=sumsq,
-                                        rides=rides)
+                                        rides=rides, **fid)
         else:
             after = self._fork_point()
             n = self.net.trunk_backward(rp.frames, self.ws_s, ids_s, jdx, extra_jobs=[heads_job], sumsq=sumsq,
-                                        after_first=after)
+                                        after_first=after, **fid)
         if self.allreduce is None:
             assert n <= self.fin_partials.numel()
             self.n_fin_partials = n

@@ -55,6 +55,14 @@ class F32Workspace:
             self.dy3 = torch.empty(B, FEAT, **f32)
             self.dy2 = torch.empty(B, 81, 64, **f32)
             self.dy1 = torch.empty(B, 400, 32, **f32)
+            # ReLU sign bits of a1 / a2 / a3 (one bit per activation, words of 32 channels): written
+            # by the conv forwards when this workspace is problem 0 of a ``sign_bits`` forward, read
+            # by the input gradients in place of the fp32 activations (``bits_valid``)
+            i32 = dict(dtype=torch.int32, device=device)
+            self.bits1 = torch.zeros(B, 400, **i32)
+            self.bits2 = torch.zeros(B, 81, 2, **i32)
+            self.bits3 = torch.zeros(B, P3, 2, **i32)
+        self.bits_valid = False
 
 
 class F32DuelingNet:
@@ -200,6 +208,12 @@ class F32DuelingNet:
 
     fc1_ride_ok = True  # the backward launches take priority-tree riders (ops/csrc/tree_dev.h)
 
+    @staticmethod
+    def _mask_bits(ws: F32Workspace, layer: int) -> int:
+        """Sign bits of the activation masking layer ``layer``'s input gradient (0: read the
+        fp32 activation -- the forward that filled ``ws`` wrote no bits)."""
+        return getattr(ws, f"bits{layer}").data_ptr() if getattr(ws, "bits_valid", False) else 0
+
     def _fc1_bwd(self, ws: F32Workspace, ride=None) -> list:
         """FC1 dgrad + weight gradient (one launch, + the tree-write rider ``ride``); returns
         the finalize jobs that complete the weight gradient (sum the slices + transpose to the
@@ -207,25 +221,31 @@ class F32DuelingNet:
         m = self.model
         ga, gv = m.advantage[0].weight.grad, m.value[0].weight.grad
         self.hip.f32_fc1_bwd_split(ws.dz.data_ptr(), ws.a3.data_ptr(), self.wfc1p.data_ptr(), ws.dy3.data_ptr(),
-                                   self._fc1_ws.data_ptr(), ws.B, self._s(), ride=ride)
+                                   self._fc1_ws.data_ptr(), ws.B, self._s(), ride=ride,
+                                   mask_bits=self._mask_bits(ws, 3))
         return [self.hip.f32_fc1_finalize_job(0, self._fc1_G, self._fc1_ws.data_ptr(), ga.data_ptr()),
                 self.hip.f32_fc1_finalize_job(1, self._fc1_G, self._fc1_ws.data_ptr(), gv.data_ptr())]
 
-    def _conv_chain(self, x, ws: F32Workspace, ids, idx, after_first=None, rides=(None, None)) -> list:
+    def _conv_chain(self, x, ws: F32Workspace, ids, idx, after_first=None, rides=(None, None),
+                    batch_fid: torch.Tensor | None = None) -> list:
         """conv3 .. conv1 backward (wgrad partials + masked dgrad per launch; ``rides``: the
-        tree-write riders of the conv3 / conv2 launches); returns the finalize jobs of the
-        three layers."""
+        tree-write riders of the conv3 / conv2 launches; ``batch_fid``: the batch's frame ids
+        [B][4] left by the draw, read by the conv1 weight gradient in place of ``ids[idx]``);
+        returns the finalize jobs of the three layers."""
         B = ws.B
         h, s, f = self.hip, self._s(), self.model.features
         xp, ip, jp = self._src(x, ids, idx, B)
         w1, w2, w3 = self._wgrad_wss
         h.f32_conv_bwd(3, ws.a2.data_ptr(), 0, 0, ws.dy3.data_ptr(), self.w3t.data_ptr(), ws.a2.data_ptr(),
-                       ws.dy2.data_ptr(), w3.data_ptr(), B, s, ride=rides[0])
+                       ws.dy2.data_ptr(), w3.data_ptr(), B, s, ride=rides[0], mask_bits=self._mask_bits(ws, 2))
         if after_first is not None:
             after_first()
         h.f32_conv_bwd(2, ws.a1.data_ptr(), 0, 0, ws.dy2.data_ptr(), self.w2t.data_ptr(), ws.a1.data_ptr(),
-                       ws.dy1.data_ptr(), w2.data_ptr(), B, s, ride=rides[1])
-        h.f32_conv_bwd(1, xp, ip, jp, ws.dy1.data_ptr(), 0, 0, 0, w1.data_ptr(), B, s)
+                       ws.dy1.data_ptr(), w2.data_ptr(), B, s, ride=rides[1], mask_bits=self._mask_bits(ws, 1))
+        if batch_fid is not None:
+            assert batch_fid.dtype == torch.int32 and tuple(batch_fid.shape) == (B, 4) and ids is not None
+        h.f32_conv_bwd(1, xp, ip, jp, ws.dy1.data_ptr(), 0, 0, 0, w1.data_ptr(), B, s,
+                       batch_fid=0 if batch_fid is None else batch_fid.data_ptr())
         return [h.f32_conv_finalize_job(k, B, wsp.data_ptr(), f[2 * k - 2].weight.grad.data_ptr(),
                                         f[2 * k - 2].bias.grad.data_ptr()) for k, wsp in ((3, w3), (2, w2), (1, w1))]
 
@@ -243,38 +263,47 @@ class F32DuelingNet:
 
     def trunk_backward(self, x: torch.Tensor, ws: F32Workspace, ids: torch.Tensor | None = None,
                        idx: torch.Tensor | None = None, extra_jobs=(), sumsq: torch.Tensor | None = None,
-                       after_first=None, rides=(None, None, None, None)) -> int:
+                       after_first=None, rides=(None, None, None, None),
+                       batch_fid: torch.Tensor | None = None) -> int:
         """FC1 + conv backward from ``ws.dz`` (fp32 dL/dz).  The conv weight-gradient
         partials (+ ``extra_jobs``) are reduced by ONE grad_finalize, which also writes the
         per-workgroup sum-of-squares partials of EVERY gradient into ``sumsq`` (fp64) when
         given; returns the partial count.  ``after_first()`` runs right after the first launch;
-        ``rides`` = the priority-tree riders of the FC1, conv3 and conv2 launches and the finalize."""
+        ``rides`` = the priority-tree riders of the FC1, conv3 and conv2 launches and the finalize;
+        ``batch_fid``: see :meth:`_conv_chain`."""
         self.enable_backward(ws.B)
         fc1_jobs = self._fc1_bwd(ws, ride=rides[0])
         if after_first is not None:
             after_first()
         h = self.hip
-        jobs = self._conv_chain(x, ws, ids, idx, rides=rides[1:3]) + list(extra_jobs) + fc1_jobs
+        jobs = self._conv_chain(x, ws, ids, idx, rides=rides[1:3], batch_fid=batch_fid) + list(extra_jobs) + fc1_jobs
         return h.grad_finalize(jobs, self._s(), 0 if sumsq is None else sumsq.data_ptr(), ride=rides[3])
 
 
-def forward_multi_f32(passes, act: tuple | None = None, draw=None) -> None:
+def forward_multi_f32(passes, act: tuple | None = None, draw=None, sign_bits: bool = False) -> None:
     """Up to 3 fp32 forward passes ``(net, x, ws, ids, idx)`` (common batch and action
     count; the nets may differ, e.g. online and target) with ONE launch per layer.  ``draw``
-    (``make_conv_sample``): the conv1 launch draws the PER rows that ``idx`` then holds."""
+    (``make_conv_sample``): the conv1 launch draws the PER rows that ``idx`` then holds.
+    ``sign_bits``: the conv launches also write the ReLU sign bits of the first pass (the
+    gradient pass; its workspace kept for the backward), which its input gradients then read
+    (``APEX_F32_BATCH_RESOLVE`` / ``f32_set_batch_resolve`` bit 0 turns them off)."""
     passes = list(passes)
     assert 1 <= len(passes) <= 3
     net0 = passes[0][0]
     B, A = passes[0][2].B, net0.A
     h, s = net0.hip, net0._s()
     c1, c2, c3, fc, hd = [], [], [], [], []
-    for net, x, ws, ids, idx in passes:
+    for k, (net, x, ws, ids, idx) in enumerate(passes):
         assert ws.B == B and net.A == A, "one launch per layer needs a common batch and action count"
+        # (f32_batch_resolve bit 0: one build runs both mask paths, tests/test_gpu_relu_bits.py)
+        ws.bits_valid = bits = bool(sign_bits and k == 0 and getattr(ws, "bits1", None) is not None
+                                    and h.f32_batch_resolve() & 1)
         m, f = net.model, net.model.features
         xp, ip, jp = net._src(x, ids, idx, B)
-        c1.append((xp, ip, jp, f[0].weight.data_ptr(), 0, f[0].bias.data_ptr(), ws.a1.data_ptr()))
-        c2.append((ws.a1.data_ptr(), 0, 0, net.w2p.data_ptr(), 0, f[2].bias.data_ptr(), ws.a2.data_ptr()))
-        c3.append((ws.a2.data_ptr(), 0, 0, net.w3p.data_ptr(), 0, f[4].bias.data_ptr(), ws.a3.data_ptr()))
+        b1, b2, b3 = ((ws.bits1.data_ptr(),), (ws.bits2.data_ptr(),), (ws.bits3.data_ptr(),)) if bits else ((),) * 3
+        c1.append((xp, ip, jp, f[0].weight.data_ptr(), 0, f[0].bias.data_ptr(), ws.a1.data_ptr()) + b1)
+        c2.append((ws.a1.data_ptr(), 0, 0, net.w2p.data_ptr(), 0, f[2].bias.data_ptr(), ws.a2.data_ptr()) + b2)
+        c3.append((ws.a2.data_ptr(), 0, 0, net.w3p.data_ptr(), 0, f[4].bias.data_ptr(), ws.a3.data_ptr()) + b3)
         fc.append((ws.a3.data_ptr(), 0, 0, net.wfc1p.data_ptr(), 0, 0, ws.z.data_ptr()))
         hd.append(net._heads_tuple(ws))
     h.f32_conv_fwd_multi(1, c1, B, s, draw=draw)

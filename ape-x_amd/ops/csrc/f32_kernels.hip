@@ -136,6 +136,26 @@ struct HasColsum<P, decltype((void)P::A_COLSUM, void())> {
   static constexpr bool value = P::A_COLSUM;
 };
 
+// ReLU sign bits (one bit per stored activation, words of 32 channels per row), both optional:
+//  * a forward policy may WRITE them (HasReluBits: want_bits(ctx) block-uniform, stored(a, c, n, v)
+//    = the activation its store() writes, bits_word(c, ml, nl0) = the word of tile row ml and
+//    columns nl0 .. nl0 + 31, nullptr for a row past M): per accumulator element one ballot of
+//    "stored > 0" is the words of rows (e, h = 0) and (e, h = 1); lane e of each half keeps its
+//    half's word and the 16 rows go out as ONE store of 32 lanes;
+//  * an input-gradient policy may READ them in place of the fp32 activation (HasMaskBits:
+//    use_bits(a) read by the launcher, mask_word(a, c, ml, nl0) = the word of tile row ml (clamped to the
+//    batch) and columns nl0 .. +31, store_keep(a, c, ml, n, v, keep)): lane r loads the word of
+//    wave-tile row r BEFORE the k loop (one VGPR per 32 x 32 block; the latency hides behind the
+//    loop), and element e of half h takes its row's word by v_readlane at a compile-time row.
+template <class P, class = void>
+struct HasReluBits : std::false_type {};
+template <class P>
+struct HasReluBits<P, decltype((void)P::RELU_BITS, void())> : std::true_type {};
+template <class P, class = void>
+struct HasMaskBits : std::false_type {};
+template <class P>
+struct HasMaskBits<P, decltype((void)P::MASK_BITS, void())> : std::true_type {};
+
 // The next k-block is loaded into registers while the current one computes (its LDS store
 // follows the MFMA block).  Policies may precompute a per-thread row state once (the k-invariant part of an operand
 // chunk's address: im2col divisions by the output width, sample / channel offsets) and load
@@ -299,12 +319,15 @@ __device__ __forceinline__ uint2 ds_tr16(const char* p) {
 // run past the operand's range (zeros, or other bytes of the same operand), the other loaders
 // get the k-block index clamped to the last one.  Same k order, same staged values, same MFMA
 // k-slots at every depth: bit-identical results (tests/test_gpu_f32_prefetch.py).
-template <class P, int SS, int D>
+// XB: the launch carries sign bits (a kernel of its own: with the hooks compiled into the plain
+// kernels behind a null-pointer test, those ran 1.3 % slower per step with every pointer null).
+template <class P, int SS, int D, bool XB = false>
 __device__ __forceinline__ void gemm_body(const typename P::Args& args, int block, float* lds,
                                           typename P::Smem& sm) {
   using G = Geo<P>;
   using GS = GeoS<P>;
   constexpr bool COLSUM = HasColsum<P>::value;
+  constexpr bool WBITS = XB && HasReluBits<P>::value, RBITS = XB && HasMaskBits<P>::value;
   static_assert(!COLSUM || (!P::A_KMAJ && 256 % G::RA == 0), "colsum needs MN-major A");
   typename P::Ctx ctx;
   P::decode(args, block, ctx, sm);
@@ -337,6 +360,15 @@ __device__ __forceinline__ void gemm_body(const typename P::Args& args, int bloc
       const int q = min(t + 256 * j, G::CB - 1);
       rowb[j] = P::row_b(args, ctx, q / G::RB, q % G::RB);
     }
+  }
+  // the sign-bit words of this lane's wave-tile row, in flight during the whole k loop
+  uint32_t mw[G::TM][G::TN] = {};
+  if constexpr (RBITS) {
+#pragma unroll
+    for (int mi = 0; mi < G::TM; ++mi)
+#pragma unroll
+      for (int ni = 0; ni < G::TN; ++ni)
+        mw[mi][ni] = P::mask_word(args, ctx, wm * G::WTM + mi * 32 + r, wn * G::WTN + ni * 32);
   }
 
   auto gload = [&](int kbr, auto S) {
@@ -636,15 +668,59 @@ __device__ __forceinline__ void gemm_body(const typename P::Args& args, int bloc
 #pragma unroll
     for (int ni = 0; ni < G::TN; ++ni) acc[mi][ni] += accx[mi][ni];
 
+  if constexpr (RBITS) {
+    {
+      // lane (r, h) tests bit r of the word of row (e, h): one mask per half, so each of the two
+      // scalar words meets a VGPR operand
+      const uint32_t bit0 = h ? 0u : 1u << r, bit1 = h ? 1u << r : 0u;
 #pragma unroll
-  for (int mi = 0; mi < G::TM; ++mi)
+      for (int mi = 0; mi < G::TM; ++mi)
 #pragma unroll
-    for (int ni = 0; ni < G::TN; ++ni)
+        for (int ni = 0; ni < G::TN; ++ni)
 #pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int row = (e & 3) + 8 * (e >> 2) + 4 * h;
-        P::store(args, ctx, wm * G::WTM + mi * 32 + row, wn * G::WTN + ni * 32 + r, acc[mi][ni][e]);
-      }
+          for (int e = 0; e < 16; ++e) {
+            const int row0 = (e & 3) + 8 * (e >> 2);
+            const uint32_t w0 = __builtin_amdgcn_readlane(mw[mi][ni], row0);
+            const uint32_t w1 = __builtin_amdgcn_readlane(mw[mi][ni], row0 + 4);
+            const bool keep = ((w0 & bit0) | (w1 & bit1)) != 0u;
+            P::store_keep(args, ctx, wm * G::WTM + mi * 32 + row0 + 4 * h, wn * G::WTN + ni * 32 + r, acc[mi][ni][e],
+                          keep);
+          }
+    }
+  } else {
+#pragma unroll
+    for (int mi = 0; mi < G::TM; ++mi)
+#pragma unroll
+      for (int ni = 0; ni < G::TN; ++ni)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int row = (e & 3) + 8 * (e >> 2) + 4 * h;
+          P::store(args, ctx, wm * G::WTM + mi * 32 + row, wn * G::WTN + ni * 32 + r, acc[mi][ni][e]);
+        }
+  }
+
+  if constexpr (WBITS) {
+    if (P::want_bits(ctx)) {  // block-uniform: every lane takes part in the ballots
+#pragma unroll
+      for (int mi = 0; mi < G::TM; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < G::TN; ++ni) {
+          uint32_t mine = 0u;
+#pragma unroll
+          for (int e = 0; e < 16; ++e) {
+            const float sv = P::stored(args, ctx, wn * G::WTN + ni * 32 + r, acc[mi][ni][e]);
+            const unsigned long long bal = __ballot(sv > 0.f);
+            const uint32_t wd = h ? (uint32_t)(bal >> 32) : (uint32_t)bal;  // this half's row (e, h)
+            mine = r == e ? wd : mine;
+          }
+          if (r < 16) {  // lane e of each half: row (e, h)
+            const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+            uint32_t* bp = P::bits_ptr(ctx, wm * G::WTM + mi * 32 + row, wn * G::WTN + ni * 32);
+            if (bp) *bp = mine;
+          }
+        }
+    }
+  }
 
   if constexpr (COLSUM) {
     if (P::want_colsum(ctx)) {  // block-uniform
@@ -679,19 +755,19 @@ struct BodyForm {
   static constexpr int value = SS == 3 ? 2 : SS;
 };
 
-template <class P, int SS, int D>
+template <class P, int SS, int D, bool XB = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SS == 3 || D > 1 ? 3 : 1))) void gemm_k(
     typename P::Args args) {
   __shared__ __attribute__((aligned(16))) float lds[LdsFloats<P, SS>::value];
   __shared__ typename P::Smem sm;
-  gemm_body<P, BodyForm<SS>::value, D>(args, xcd_chunk(blockIdx.x, gridDim.x), lds, sm);
+  gemm_body<P, BodyForm<SS>::value, D, XB>(args, xcd_chunk(blockIdx.x, gridDim.x), lds, sm);
 }
 
 // Two independent GEMMs in one launch: blocks [0, n1) run P1, the rest P2 (P1 first: the
 // longer per-block problem starts early).
 // r (stage > 0): the learner's priority-tree write riding the launch as extra workgroups
 // (tree_dev.h tree_ride: the leaves in block 0, a level's recompute past the GEMM tiles).
-template <class P1, class P2, int SS, int D>
+template <class P1, class P2, int SS, int D, bool XB = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SS == 3 || D > 1 ? 3 : 1))) void gemm2_k(
     typename P1::Args a1, typename P2::Args a2, int n1, TreeRide r) {
   __shared__ __attribute__((aligned(16))) float lds[MaxI<LdsFloats<P1, SS>::value, LdsFloats<P2, SS>::value>::value];
@@ -702,9 +778,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SS == 3 || 
   int b = blockIdx.x;
   if (r.stage && tree_ride(r, r.nhost, lds, &b)) return;  // (grid-uniform stage, block-uniform role)
   if (b < n1)
-    gemm_body<P1, BodyForm<SS>::value, D>(a1, b, lds, sm.s1);
+    gemm_body<P1, BodyForm<SS>::value, D, XB>(a1, b, lds, sm.s1);
   else
-    gemm_body<P2, BodyForm<SS>::value, D>(a2, b - n1, lds, sm.s2);
+    gemm_body<P2, BodyForm<SS>::value, D, XB>(a2, b - n1, lds, sm.s2);
 }
 
 __device__ __forceinline__ F32Prob pick(const F32Set& s, int i) {
@@ -770,9 +846,19 @@ struct Conv2FwdT {  // a2 = relu(conv(a1, W2) + b2); k = (ky, kx, ci) = tap * 32
   static __device__ f32x4 load_b_row(const Args&, const Ctx& c, const RowB& r, int kb) {
     return bld4(c.w, r.off + (uint32_t)(kb * BK * 4));
   }
-  static __device__ void store(const Args&, const Ctx& c, int ml, int n, float v) {
+  static __device__ float stored(const Args&, const Ctx& c, int n, float v) {
+    return fmaxf(v + c.p.bias[c.n0 + n], 0.f);
+  }
+  static __device__ void store(const Args& a, const Ctx& c, int ml, int n, float v) {
     const int m = c.m0 + ml;
-    if (m < c.M) c.p.out[(size_t)m * 64 + c.n0 + n] = fmaxf(v + c.p.bias[c.n0 + n], 0.f);
+    if (m < c.M) c.p.out[(size_t)m * 64 + c.n0 + n] = stored(a, c, n, v);
+  }
+  // sign bits [M][2]: word (n0 + nl0) / 32 of row m (gemm_body's HasReluBits epilogue)
+  static constexpr bool RELU_BITS = true;
+  static __device__ bool want_bits(const Ctx& c) { return c.p.relu_bits != nullptr; }
+  static __device__ uint32_t* bits_ptr(const Ctx& c, int ml, int nl0) {
+    const int m = c.m0 + ml;
+    return m < c.M ? c.p.relu_bits + (size_t)m * 2 + ((c.n0 + nl0) >> 5) : nullptr;
   }
 };
 
@@ -833,9 +919,19 @@ struct Conv3FwdT {  // a3 = relu(conv(a2, W3) + b3); k = tap * 64 + ci; w = w3p
   static __device__ f32x4 load_b_row(const Args&, const Ctx& c, const RowB& r, int kb) {
     return bld4(c.w, r.off + (uint32_t)(kb * BK * 4));
   }
-  static __device__ void store(const Args&, const Ctx& c, int ml, int n, float v) {
+  static __device__ float stored(const Args&, const Ctx& c, int n, float v) {
+    return fmaxf(v + c.p.bias[c.n0 + n], 0.f);
+  }
+  static __device__ void store(const Args& a, const Ctx& c, int ml, int n, float v) {
     const int m = c.m0 + ml;
-    if (m < c.M) c.p.out[(size_t)m * 64 + c.n0 + n] = fmaxf(v + c.p.bias[c.n0 + n], 0.f);
+    if (m < c.M) c.p.out[(size_t)m * 64 + c.n0 + n] = stored(a, c, n, v);
+  }
+  // sign bits [M][2]: word (n0 + nl0) / 32 of row m (gemm_body's HasReluBits epilogue)
+  static constexpr bool RELU_BITS = true;
+  static __device__ bool want_bits(const Ctx& c) { return c.p.relu_bits != nullptr; }
+  static __device__ uint32_t* bits_ptr(const Ctx& c, int ml, int nl0) {
+    const int m = c.m0 + ml;
+    return m < c.M ? c.p.relu_bits + (size_t)m * 2 + ((c.n0 + nl0) >> 5) : nullptr;
   }
 };
 
@@ -1016,6 +1112,8 @@ __device__ __forceinline__ int opaque_i(int x) {
 // cs.out_idx (the learner): the PER draw folded in -- wave k draws sample s0 + k's slot (the
 // per_sample_k descent, same arithmetic: identical slots and IS weights) and its 4 frame ids go
 // to LDS before the first frame load; workgroups past cs.nhost scatter the staged actor rows.
+// BITS: problem 0 also writes its ReLU sign bits (a kernel of its own, as for the GEMMs: XB).
+template <bool BITS>
 __global__ __launch_bounds__(256, 2) void f32_conv1_fwd_x3_k(F32Set set, ConvSample cs) {
   __shared__ __attribute__((aligned(16))) uint32_t xs[2 * kPlaneDw * 4];  // 4 planes of bf16
   __shared__ int fid[kC1xDrawMax][4];  // (the draw) frame ids of the workgroup's samples
@@ -1048,10 +1146,32 @@ __global__ __launch_bounds__(256, 2) void f32_conv1_fwd_x3_k(F32Set set, ConvSam
       const int se = staged_row_of(cs.rows, node, lane);
       const F32Prob pp = pick(set, prob);
       const int* ids = se < 0 ? pp.ids : (pp.ids == cs.rows.dst.s_ids ? cs.rows.st.s_ids : cs.rows.st.s2_ids);
-      if (lane < 4) fid[k][lane] = ids[4 * (se < 0 ? node : se) + lane];
+      const int srow = se < 0 ? node : se;
+      // lanes 0..3: the sample's frame ids; lanes 4..6 (problem 0, compact rows): the row's action /
+      // reward / done words (a staged slot: from its staging row, like the ids) -- issued together,
+      // ONE round trip ahead of the frame loads (loaded after the ids they cost a second one: +1.8 us)
+      const bool crow = prob == 0 && cs.batch_fid != nullptr;
+      uint32_t f = 0;
+      if (lane < 4) {
+        f = (uint32_t)ids[4 * srow + lane];
+      } else if (crow && lane < 7) {
+        const void* col = lane == 4 ? (const void*)(se < 0 ? cs.src_act : cs.rows.st.action)
+                                    : (lane == 5 ? (const void*)(se < 0 ? cs.src_rew : cs.rows.st.reward)
+                                                 : (const void*)(se < 0 ? cs.src_done : cs.rows.st.done));
+        f = static_cast<const uint32_t*>(col)[srow];
+      }
+      if (lane < 4) fid[k][lane] = (int)f;
       if (prob == 0 && lane == 0) {
         cs.out_idx[b] = node;
         cs.out_w[b] = per_is_weight(p, pmin, 1.f, cs.beta[0]);
+      }
+      if (crow) {  // the batch's compact rows
+        if (lane < 4) {
+          cs.batch_fid[4 * b + lane] = (int)f;
+        } else if (lane < 7) {
+          void* dst = lane == 4 ? (void*)cs.batch_act : (lane == 5 ? (void*)cs.batch_rew : (void*)cs.batch_done);
+          static_cast<uint32_t*>(dst)[b] = f;
+        }
       }
     }
     __syncthreads();
@@ -1071,6 +1191,9 @@ __global__ __launch_bounds__(256, 2) void f32_conv1_fwd_x3_k(F32Set set, ConvSam
     // roles swapped on the MFMA (A = the weight slice, B = the pixels: identical lane maps),
     // so lane (i, q) ends with channels 4q .. 4q+3 of pixel i -- one 16-byte store
     float* out = p.out + (size_t)b * 400 * 32 + nh * 16 + 4 * q;
+    // sign bits [B][400] words of 32 channels: this wave's 16 channels are half nh of a word
+    uint16_t* bits =
+        BITS && p.relu_bits ? reinterpret_cast<uint16_t*>(p.relu_bits + (size_t)b * 400) + nh : nullptr;
     float4 bias4;
     bias4.x = p.bias[nh * 16 + 4 * q];
     bias4.y = p.bias[nh * 16 + 4 * q + 1];
@@ -1091,7 +1214,7 @@ __global__ __launch_bounds__(256, 2) void f32_conv1_fwd_x3_k(F32Set set, ConvSam
         a[kb] = __builtin_bit_cast(bfx8, make_uint4(lo.x, lo.y, hi.x, hi.y));
       }
     };
-    auto tile_mfma = [&](int tile, const bfx8 (&a)[8]) {
+    auto tile_mfma = [&](int tile, const bfx8 (&a)[8], auto WB) {
       // three accumulators (hi / mid / lo products): no MFMA waits on its predecessor's result
       f32x4 ah = zero4(), am = zero4(), al = zero4();
 #pragma unroll
@@ -1106,22 +1229,43 @@ __global__ __launch_bounds__(256, 2) void f32_conv1_fwd_x3_k(F32Set set, ConvSam
       y.z = fmaxf(ah[2] + (am[2] + al[2]) + bias4.z, 0.f);
       y.w = fmaxf(ah[3] + (am[3] + al[3]) + bias4.w, 0.f);
       *reinterpret_cast<float4*>(out + (size_t)(tile * 16 + i) * 32) = y;
+      if constexpr (decltype(WB)::value) {
+        // the wave's 16 channels of pixel i from four ballots (bit 16 q + i of ballot j = channel
+        // 4 q + j): VALU only, no branch in the tile loop (the sample's whole loop is compiled twice,
+        // below), and the lane groups q = 1..3 store the same word to the same address
+        const unsigned long long b0 = __ballot(y.x > 0.f), b1 = __ballot(y.y > 0.f), b2 = __ballot(y.z > 0.f),
+                                 b3 = __ballot(y.w > 0.f);
+        auto lo = [&](unsigned long long b) { return ((uint32_t)b >> i) & 0x00010001u; };          // q = 0 | 1
+        auto hi = [&](unsigned long long b) { return ((uint32_t)(b >> 32) >> i) & 0x00010001u; };  // q = 2 | 3
+        const uint32_t T = lo(b0) | lo(b1) << 1 | lo(b2) << 2 | lo(b3) << 3;  // bit j: q = 0, bit 16 + j: q = 1
+        const uint32_t U = hi(b0) | hi(b1) << 1 | hi(b2) << 2 | hi(b3) << 3;  // bit j: q = 2, bit 16 + j: q = 3
+        const uint32_t nb = (T & 0xFu) | ((T >> 12) & 0xF0u) | ((U & 0xFu) << 8) | ((U >> 4) & 0xF000u);
+        bits[(tile * 16 + i) * 2] = (uint16_t)nb;
+      }
     };
     // ping-pong fragment buffers: the next tile's LDS reads are in flight during this tile's MFMAs.
     // Wave parity t0 owns tiles t0, t0 + 2, ...: 6 pairs (+ tile 24 for t0 = 0); every fragment
     // load is unconditional (the one past parity 1's last tile re-reads tile 24, unused), so the
     // buffers keep fixed registers (guarded loads + a mid-loop exit made the compiler copy them)
-    bfx8 fa[8], fb[8];
-    const int t0 = wave & 1;
-    frags(t0, fa);
-    for (int pr = 0; pr < 6; ++pr) {
-      const int tile = t0 + 4 * pr;
-      frags(tile + 2, fb);
-      tile_mfma(tile, fa);
-      frags(min(tile + 4, 24), fa);
-      tile_mfma(tile + 2, fb);
+    auto tiles = [&](auto WB) {
+      bfx8 fa[8], fb[8];
+      const int t0 = wave & 1;
+      frags(t0, fa);
+      for (int pr = 0; pr < 6; ++pr) {
+        const int tile = t0 + 4 * pr;
+        frags(tile + 2, fb);
+        tile_mfma(tile, fa, WB);
+        frags(min(tile + 4, 24), fa);
+        tile_mfma(tile + 2, fb, WB);
+      }
+      if (t0 == 0) tile_mfma(24, fa, WB);
+    };
+    if constexpr (BITS) {  // block-uniform, as a scalar branch: the sign bits are problem 0's
+      if (__builtin_amdgcn_readfirstlane(bits != nullptr)) tiles(std::true_type{});
+      else tiles(std::false_type{});
+    } else {
+      tiles(std::false_type{});
     }
-    if (t0 == 0) tile_mfma(24, fa);
   }
 }
 
@@ -1133,6 +1277,8 @@ struct BwdArgs {
   const float* dy;      // gradient w.r.t. the layer's (post-ReLU-masked) output
   const float* w;       // packed weights: wfc1p (FC1 dgrad), w3t / w2t (conv dgrad)
   const float* mask;    // post-ReLU activation of the layer below (dgrad ReLU backward)
+  const uint32_t* mask_bits;  // its sign bits (F32Prob::relu_bits layout): when set, `mask` is not read
+  const int* batch_fid; // conv1 wgrad: the batch's frame ids [B][4] (when set, ids / idx are not read)
   float* out;           // dgrad output | wgrad partials / FC1 advantage grad
   float* out2;          // wgrad bias partials | FC1 value grad
   int B;
@@ -1177,6 +1323,16 @@ struct Fc1Dgrad {  // dy3[b][k'] = (a3 > 0) * sum_n dz[b][n] wfc1p[n][k']
     if (b >= a.B) return;
     const size_t o = (size_t)b * 3136 + c.n0 + nl;
     a.out[o] = a.mask[o] > 0.f ? v : 0.f;
+  }
+  // sign bits of a3 [B][49][2]: the 64-wide n-tile is position n0 / 64, word nl0 / 32
+  static constexpr bool MASK_BITS = true;
+  static __host__ __device__ bool use_bits(const Args& a) { return a.mask_bits != nullptr; }
+  static __device__ uint32_t mask_word(const Args& a, const Ctx& c, int ml, int nl0) {
+    return a.mask_bits[(size_t)min(c.m0 + ml, a.B - 1) * 98 + ((c.n0 + nl0) >> 5)];
+  }
+  static __device__ void store_keep(const Args& a, const Ctx& c, int ml, int nl, float v, bool keep) {
+    const int b = c.m0 + ml;
+    if (b < a.B) a.out[(size_t)b * 3136 + c.n0 + nl] = keep ? v : 0.f;
   }
 };
 
@@ -1360,7 +1516,11 @@ __global__ __launch_bounds__(256 * S) void f32_conv1_wgrad_x3_k(BwdArgs a) {
     // (kept as offsets from the kernel-argument base: a pointer read back from LDS is a flat
     // pointer, and flat loads may alias the LDS stores below -- each waited out before its store)
     const uint8_t* fb = static_cast<const uint8_t*>(a.x);
-    if (t < S * 4) wplanes[t] = frame_plane(f, b0 + min(t >> 2, ns - 1), t & 3, kPlane) - fb;
+    // (a.batch_fid: the draw left the batch's frame ids in row order -- one load, no lookups)
+    if (t < S * 4) {
+      const int b = b0 + min(t >> 2, ns - 1);
+      wplanes[t] = a.batch_fid ? (int64_t)a.batch_fid[4 * b + (t & 3)] * kPlane : frame_plane(f, b, t & 3, kPlane) - fb;
+    }
     __syncthreads();
     uint4 v[kPer];
 #pragma unroll
@@ -1552,6 +1712,16 @@ struct Conv3DgradPT {  // dy2[b][pi][ci] = (a2 > 0) * sum_{valid taps, co} dy3[b
     const size_t o = ((size_t)b * 81 + c.pos) * 64 + c.n0 + n;
     a.out[o] = a.mask[o] > 0.f ? v : 0.f;
   }
+  // sign bits of a2 [B][81][2]
+  static constexpr bool MASK_BITS = true;
+  static __host__ __device__ bool use_bits(const Args& a) { return a.mask_bits != nullptr; }
+  static __device__ uint32_t mask_word(const Args& a, const Ctx& c, int ml, int nl0) {
+    return a.mask_bits[((size_t)min(c.b0 + ml, a.B - 1) * 81 + c.pos) * 2 + ((c.n0 + nl0) >> 5)];
+  }
+  static __device__ void store_keep(const Args& a, const Ctx& c, int ml, int n, float v, bool keep) {
+    const int b = c.b0 + ml;
+    if (b < a.B) a.out[((size_t)b * 81 + c.pos) * 64 + c.n0 + n] = keep ? v : 0.f;
+  }
 };
 
 // Under the register split BK 16 won (half the LDS: more workgroups per CU beside the
@@ -1621,6 +1791,19 @@ struct Conv2DgradPT {
     const int iy = 2 * c.jy + (c.cls >> 1), ix = 2 * c.jx + (c.cls & 1);
     const size_t o = ((size_t)b * 400 + iy * 20 + ix) * 32 + n;
     a.out[o] = a.mask[o] > 0.f ? v : 0.f;
+  }
+  // sign bits of a1 [B][400]: one word per pixel (32 channels = the n-tile)
+  static constexpr bool MASK_BITS = true;
+  static __host__ __device__ bool use_bits(const Args& a) { return a.mask_bits != nullptr; }
+  static __device__ uint32_t mask_word(const Args& a, const Ctx& c, int ml, int) {
+    const int iy = 2 * c.jy + (c.cls >> 1), ix = 2 * c.jx + (c.cls & 1);
+    return a.mask_bits[(size_t)min(c.b0 + ml, a.B - 1) * 400 + iy * 20 + ix];
+  }
+  static __device__ void store_keep(const Args& a, const Ctx& c, int ml, int n, float v, bool keep) {
+    const int b = c.b0 + ml;
+    if (b >= a.B) return;
+    const int iy = 2 * c.jy + (c.cls >> 1), ix = 2 * c.jx + (c.cls & 1);
+    a.out[((size_t)b * 400 + iy * 20 + ix) * 32 + n] = keep ? v : 0.f;
   }
 };
 using Conv2DgradP = Conv2DgradPT<16>;
@@ -1694,41 +1877,74 @@ int prefetch_mask() {
   }
   return g_prefetch;
 }
+// What is resolved once for the backward (kernels.h f32_set_batch_resolve): 1 = ReLU sign bits,
+// 2 = the drawn batch's compact rows; consulted by the callers that wire the pointers.  Whole step,
+// builds and masks alternated in separate processes on one box (profiles/backward_sign_bits.md):
+// mask 1 +1.9 % over the parent build, mask 3 +2.2 %, mask 2 alone -0.9 % (= this build at mask 0:
+// the compact rows gain nothing on their own), so they stay off by default.
+constexpr int kBatchResolveDefault = 1;
+int g_batch_resolve = -1;
+int batch_resolve_mask() {
+  if (g_batch_resolve < 0) {
+    const char* e = std::getenv("APEX_F32_BATCH_RESOLVE");
+    g_batch_resolve = e ? std::atoi(e) & 3 : kBatchResolveDefault;
+  }
+  return g_batch_resolve;
+}
 // cls: 0 = learner-sized forward, 1 = backward pair, 2 = small forward
 int prefetch_depth(int cls) { return std::min(3, 1 + ((prefetch_mask() >> (2 * cls)) & 3)); }
 
 // small: a launch below the learner's size (the actor's / evaluator's forward) -- bits 4-5 of the
 // mask, when set, give those launches a form of their own (form + 1; 0 = the forward form)
-template <class P, int D>
+template <class P, int D, bool XB>
 void launch1_d(const typename P::Args& a, int blocks, hipStream_t s, int form) {
   switch (form) {
-    case 1: gemm_k<P, 1, D><<<blocks, 256, 0, s>>>(a); break;
-    case 2: gemm_k<P, 2, D><<<blocks, 256, 0, s>>>(a); break;
-    case 3: gemm_k<P, 3, D><<<blocks, 256, 0, s>>>(a); break;
-    default: gemm_k<P, 0, D><<<blocks, 256, 0, s>>>(a);
+    case 1: gemm_k<P, 1, D, XB><<<blocks, 256, 0, s>>>(a); break;
+    case 2: gemm_k<P, 2, D, XB><<<blocks, 256, 0, s>>>(a); break;
+    case 3: gemm_k<P, 3, D, XB><<<blocks, 256, 0, s>>>(a); break;
+    default: gemm_k<P, 0, D, XB><<<blocks, 256, 0, s>>>(a);
   }
 }
-template <class P>
-void launch1(const typename P::Args& a, int blocks, hipStream_t s, bool small = false) {
-  if (blocks <= 0) return;
+template <class P, bool XB>
+void launch1_x(const typename P::Args& a, int blocks, hipStream_t s, bool small) {
   const int m = stage_split_mask();
   const int form = small && ((m >> 4) & 3) ? ((m >> 4) & 3) - 1 : m & 3;
   switch (prefetch_depth(small ? 2 : 0)) {
-    case 2: launch1_d<P, 2>(a, blocks, s, form); break;
-    case 3: launch1_d<P, 3>(a, blocks, s, form); break;
-    default: launch1_d<P, 1>(a, blocks, s, form);
+    case 2: launch1_d<P, 2, XB>(a, blocks, s, form); break;
+    case 3: launch1_d<P, 3, XB>(a, blocks, s, form); break;
+    default: launch1_d<P, 1, XB>(a, blocks, s, form);
+  }
+}
+// bits: the launch writes ReLU sign bits (policies with the hook: the kernels compiled with it)
+template <class P>
+void launch1(const typename P::Args& a, int blocks, hipStream_t s, bool small = false, bool bits = false) {
+  if (blocks <= 0) return;
+  if constexpr (HasReluBits<P>::value) {
+    if (bits) launch1_x<P, true>(a, blocks, s, small);
+    else launch1_x<P, false>(a, blocks, s, small);
+  } else {
+    launch1_x<P, false>(a, blocks, s, small);
   }
   LAUNCH_CHECK();
 }
 
-template <class P1, class P2, int D>
+template <class P1, class P2, int D, bool XB>
 void launch2_d(const typename P1::Args& a1, const typename P2::Args& a2, int n1, int nb, const TreeRide& r,
                hipStream_t s) {
   switch ((stage_split_mask() >> 2) & 3) {
-    case 1: gemm2_k<P1, P2, 1, D><<<nb, 256, 0, s>>>(a1, a2, n1, r); break;
-    case 2: gemm2_k<P1, P2, 2, D><<<nb, 256, 0, s>>>(a1, a2, n1, r); break;
-    case 3: gemm2_k<P1, P2, 3, D><<<nb, 256, 0, s>>>(a1, a2, n1, r); break;
-    default: gemm2_k<P1, P2, 0, D><<<nb, 256, 0, s>>>(a1, a2, n1, r);
+    case 1: gemm2_k<P1, P2, 1, D, XB><<<nb, 256, 0, s>>>(a1, a2, n1, r); break;
+    case 2: gemm2_k<P1, P2, 2, D, XB><<<nb, 256, 0, s>>>(a1, a2, n1, r); break;
+    case 3: gemm2_k<P1, P2, 3, D, XB><<<nb, 256, 0, s>>>(a1, a2, n1, r); break;
+    default: gemm2_k<P1, P2, 0, D, XB><<<nb, 256, 0, s>>>(a1, a2, n1, r);
+  }
+}
+template <class P1, class P2, bool XB>
+void launch2_x(const typename P1::Args& a1, const typename P2::Args& a2, int n1, int nb, const TreeRide& r,
+               hipStream_t s) {
+  switch (prefetch_depth(1)) {
+    case 2: launch2_d<P1, P2, 2, XB>(a1, a2, n1, nb, r, s); break;
+    case 3: launch2_d<P1, P2, 3, XB>(a1, a2, n1, nb, r, s); break;
+    default: launch2_d<P1, P2, 1, XB>(a1, a2, n1, nb, r, s);
   }
 }
 
@@ -1742,11 +1958,9 @@ void launch2(const typename P1::Args& a1, int n1, const typename P2::Args& a2, i
     r.nhost = n1 + n2;
   }
   const int nb = n1 + n2 + tree_ride_blocks(r);
-  switch (prefetch_depth(1)) {
-    case 2: launch2_d<P1, P2, 2>(a1, a2, n1, nb, r, s); break;
-    case 3: launch2_d<P1, P2, 3>(a1, a2, n1, nb, r, s); break;
-    default: launch2_d<P1, P2, 1>(a1, a2, n1, nb, r, s);
-  }
+  // the input gradient (P2) masks with sign bits: the kernels compiled with that hook
+  if (P2::use_bits(a2)) launch2_x<P1, P2, true>(a1, a2, n1, nb, r, s);
+  else launch2_x<P1, P2, false>(a1, a2, n1, nb, r, s);
   LAUNCH_CHECK();
 }
 
@@ -1759,7 +1973,7 @@ void check_set(const F32Set& set) {
 
 template <class P>
 void fwd_launch(const F32Set& set, hipStream_t s) {
-  launch1<P>(set, set.n * P::tiles(set.B), s, set.n * set.B < 1024);
+  launch1<P>(set, set.n * P::tiles(set.B), s, set.n * set.B < 1024, set.p[0].relu_bits != nullptr);
 }
 
 }  // namespace
@@ -1768,6 +1982,8 @@ void f32_set_stage_split(int mask) { g_stage_split = mask; }
 int f32_stage_split() { return stage_split_mask(); }
 void f32_set_prefetch(int mask) { g_prefetch = mask; }
 int f32_prefetch() { return prefetch_mask(); }
+void f32_set_batch_resolve(int mask) { g_batch_resolve = mask < 0 ? -1 : mask & 3; }
+int f32_batch_resolve() { return batch_resolve_mask(); }
 
 // ------------------------------------------------------------------ host launchers
 // Tiles (MI355X, measured): the learner's launches (2-3 passes of its batch: >= 1024 rows) on
@@ -1807,11 +2023,15 @@ void f32_conv_fwd_multi(int layer, const F32Set& set, hipStream_t s, int c1_grid
           throw std::invalid_argument("f32 conv1 draw: <= 8 samples per workgroup");
         if (!c.length || !c.beta || !c.counter || !c.out_w || set.p[0].idx != c.out_idx)
           throw std::invalid_argument("f32 conv1 draw: fill level, beta, counter, weights, and problem 0 reading idx");
+        if (c.batch_fid && (!c.batch_act || !c.batch_rew || !c.batch_done || !c.src_act || !c.src_rew || !c.src_done))
+          throw std::invalid_argument("f32 conv1 draw: the compact rows need all four outputs and the table columns");
         for (int k = 0; k < set.n; ++k)
           if (!set.p[k].ids || (c.rows.E > 0 && set.p[k].ids != c.rows.dst.s_ids && set.p[k].ids != c.rows.dst.s2_ids))
             throw std::invalid_argument("f32 conv1 draw: every problem reads the replay's frame-id tables");
       }
-      f32_conv1_fwd_x3_k<<<G + (c.out_idx ? (c.rows.E + 255) / 256 : 0), 256, 0, s>>>(set, c);
+      const int nb = G + (c.out_idx ? (c.rows.E + 255) / 256 : 0);
+      if (set.p[0].relu_bits) f32_conv1_fwd_x3_k<true><<<nb, 256, 0, s>>>(set, c);
+      else f32_conv1_fwd_x3_k<false><<<nb, 256, 0, s>>>(set, c);
       LAUNCH_CHECK();
       break;
     }
@@ -1859,13 +2079,14 @@ static void check_bwd_batch(int B) {
 }
 
 void f32_fc1_bwd_split(const float* dz, const float* a3, const float* wfc1p, float* dy3, float* ws, int B,
-                       hipStream_t s, const TreeRide* ride) {
+                       hipStream_t s, const TreeRide* ride, const uint32_t* mask_bits) {
   if (B <= 0) return;
   check_bwd_batch(B);
   BwdArgs d{};
   d.dy = dz;
   d.w = wfc1p;
   d.mask = a3;
+  d.mask_bits = mask_bits;
   d.out = dy3;
   d.B = B;
   BwdArgs w{};
@@ -1900,7 +2121,7 @@ size_t f32_wgrad_workspace_floats(int layer, int B, int target) {
 // wgrad + dgrad of conv layer 3 or 2 in one launch; layer 1: wgrad only (x = frames)
 void f32_conv_bwd(int layer, const void* x, const int* ids, const int* idx, const float* dy, const float* w,
                   const float* mask, float* dx, float* ws, int B, hipStream_t s, int target, int tile,
-                  const TreeRide* ride) {
+                  const TreeRide* ride, const uint32_t* mask_bits, const int* batch_fid) {
   if (B <= 0) return;
   check_bwd_batch(B);
   if (ride && ride->stage && layer == 1) throw std::invalid_argument("f32_conv_bwd: no tree rider on layer 1");
@@ -1916,10 +2137,12 @@ void f32_conv_bwd(int layer, const void* x, const int* ids, const int* idx, cons
   g.B = B;
   g.kbps = p.kbps;
   g.splits = p.splits;
+  g.batch_fid = layer == 1 ? batch_fid : nullptr;
   BwdArgs d{};
   d.dy = dy;
   d.w = w;
   d.mask = mask;
+  d.mask_bits = mask_bits;
   d.out = dx;
   d.B = B;
   // microbench knob (read once): APEX_F32_BWD_HALF=1 runs only the weight-gradient half of a conv

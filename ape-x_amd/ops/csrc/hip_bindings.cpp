@@ -482,15 +482,17 @@ PYBIND11_MODULE(_apex_hip, m) {
     pack_conv_wt(P<const float>(src), P<uint16_t>(dst), N, C, KH, KW, S(s));
   });
   // ---- fp32 (reference-precision) network kernels (f32_kernels.hip)
-  // a problem: (in, ids, idx, w, w2, bias, out)
+  // a problem: (in, ids, idx, w, w2, bias, out[, relu_bits])
   auto f32set = [](const std::vector<std::vector<uint64_t>>& probs, int B) {
     if (probs.empty() || probs.size() > (size_t)kMaxProbs) throw std::invalid_argument("1..3 problems");
     F32Set set{};
     for (size_t i = 0; i < probs.size(); ++i) {
       const auto& t = probs[i];
-      if (t.size() != 7) throw std::invalid_argument("f32 problem: 7 fields");
+      if (t.size() != 7 && t.size() != 8) throw std::invalid_argument("f32 problem: 7 or 8 fields");
       set.p[i] = F32Prob{P<const void>(t[0]), P<const int>(t[1]), P<const int>(t[2]), P<const float>(t[3]),
-                         P<const float>(t[4]), P<const float>(t[5]), P<float>(t[6])};
+                         P<const float>(t[4]), P<const float>(t[5]), P<float>(t[6]),
+                         t.size() == 8 ? P<uint32_t>(t[7]) : nullptr};
+      if (set.p[i].relu_bits && i != 0) throw std::invalid_argument("f32 problem: sign bits are problem 0's");
     }
     set.n = (int)probs.size();
     set.B = B;
@@ -509,7 +511,8 @@ PYBIND11_MODULE(_apex_hip, m) {
   m.def("make_conv_sample", [](const TreeHandle& t, uint64_t length_ptr, uint64_t beta_ptr, uint64_t seed,
                                uint64_t counter, uint64_t out_idx, uint64_t out_w, int exclude_last,
                                py::object rows_stage, py::object rows_dst, uint64_t rows_slot, uint64_t rows_prio,
-                               int rows_E) {
+                               int rows_E, uint64_t batch_fid, uint64_t batch_act, uint64_t batch_rew,
+                               uint64_t batch_done, py::object batch_src) {
     if (!length_ptr || !beta_ptr || !counter || !out_idx || !out_w)
       throw std::invalid_argument("make_conv_sample: fill level, beta, counter, idx and weight pointers");
     ConvSample c{};
@@ -526,10 +529,24 @@ PYBIND11_MODULE(_apex_hip, m) {
       c.rows = StagedRows{trans_table(rows_stage.cast<py::dict>()), trans_table(rows_dst.cast<py::dict>()),
                           P<const int>(rows_slot), P<const float>(rows_prio), rows_E};
     }
+    if (batch_fid) {  // the batch's compact rows; batch_src: the transition table they are taken from
+      if (!batch_act || !batch_rew || !batch_done || batch_src.is_none())
+        throw std::invalid_argument("make_conv_sample: compact rows need fid, act, rew, done and the table");
+      const TransTable src = trans_table(batch_src.cast<py::dict>());
+      c.batch_fid = P<int>(batch_fid);
+      c.batch_act = P<int>(batch_act);
+      c.batch_rew = P<float>(batch_rew);
+      c.batch_done = P<float>(batch_done);
+      c.src_act = src.action;
+      c.src_rew = src.reward;
+      c.src_done = src.done;
+    }
     return c;
   }, py::arg("t"), py::arg("length_ptr"), py::arg("beta_ptr"), py::arg("seed"), py::arg("counter"),
      py::arg("out_idx"), py::arg("out_w"), py::arg("exclude_last"), py::arg("rows_stage") = py::none(),
-     py::arg("rows_dst") = py::none(), py::arg("rows_slot") = 0, py::arg("rows_prio") = 0, py::arg("rows_E") = 0);
+     py::arg("rows_dst") = py::none(), py::arg("rows_slot") = 0, py::arg("rows_prio") = 0, py::arg("rows_E") = 0,
+     py::arg("batch_fid") = 0, py::arg("batch_act") = 0, py::arg("batch_rew") = 0, py::arg("batch_done") = 0,
+     py::arg("batch_src") = py::none());
   m.def("f32_fc1_fwd_multi", [f32set](const std::vector<std::vector<uint64_t>>& probs, int B, uint64_t s) {
     return f32_fc1_fwd_multi(f32set(probs, B), S(s));
   });
@@ -538,12 +555,14 @@ PYBIND11_MODULE(_apex_hip, m) {
   m.def("f32_stage_split", &f32_stage_split);
   m.def("f32_set_prefetch", &f32_set_prefetch);
   m.def("f32_prefetch", &f32_prefetch);
+  m.def("f32_set_batch_resolve", &f32_set_batch_resolve);
+  m.def("f32_batch_resolve", &f32_batch_resolve);
   m.def("f32_fc1_bwd_split", [](uint64_t dz, uint64_t a3, uint64_t wfc1p, uint64_t dy3, uint64_t ws, int B,
-                                uint64_t s, py::object ride) {
+                                uint64_t s, py::object ride, uint64_t mask_bits) {
     f32_fc1_bwd_split(P<const float>(dz), P<const float>(a3), P<const float>(wfc1p), P<float>(dy3), P<float>(ws), B,
-                      S(s), ride_of(ride));
+                      S(s), ride_of(ride), P<const uint32_t>(mask_bits));
   }, py::arg("dz"), py::arg("a3"), py::arg("wfc1p"), py::arg("dy3"), py::arg("ws"), py::arg("B"), py::arg("s"),
-     py::arg("ride") = py::none());
+     py::arg("ride") = py::none(), py::arg("mask_bits") = 0);
   m.def("f32_fc1_wgrad_splits", &f32_fc1_wgrad_splits);
   m.def("f32_fc1_wgrad_slices", &f32_fc1_wgrad_slices);
   m.def("f32_fc1_wgrad_workspace_floats", &f32_fc1_wgrad_workspace_floats);
@@ -555,12 +574,14 @@ PYBIND11_MODULE(_apex_hip, m) {
   m.def("f32_wgrad_workspace_floats", &f32_wgrad_workspace_floats, py::arg("layer"), py::arg("B"),
         py::arg("target") = 0);
   m.def("f32_conv_bwd", [](int layer, uint64_t x, uint64_t ids, uint64_t idx, uint64_t dy, uint64_t w, uint64_t mask,
-                           uint64_t dx, uint64_t ws, int B, uint64_t s, int target, int tile, py::object ride) {
+                           uint64_t dx, uint64_t ws, int B, uint64_t s, int target, int tile, py::object ride,
+                           uint64_t mask_bits, uint64_t batch_fid) {
     f32_conv_bwd(layer, P<const void>(x), P<const int>(ids), P<const int>(idx), P<const float>(dy), P<const float>(w),
-                 P<const float>(mask), P<float>(dx), P<float>(ws), B, S(s), target, tile, ride_of(ride));
+                 P<const float>(mask), P<float>(dx), P<float>(ws), B, S(s), target, tile, ride_of(ride),
+                 P<const uint32_t>(mask_bits), P<const int>(batch_fid));
   }, py::arg("layer"), py::arg("x"), py::arg("ids"), py::arg("idx"), py::arg("dy"), py::arg("w"), py::arg("mask"),
      py::arg("dx"), py::arg("ws"), py::arg("B"), py::arg("s"), py::arg("target") = 0, py::arg("tile") = 0,
-     py::arg("ride") = py::none());
+     py::arg("ride") = py::none(), py::arg("mask_bits") = 0, py::arg("batch_fid") = 0);
   m.def("f32_conv_finalize_job", [](int layer, int B, uint64_t ws, uint64_t grad, uint64_t bgrad, int target) {
     return f32_conv_finalize_job(layer, B, P<const float>(ws), P<float>(grad), P<float>(bgrad), target);
   }, py::arg("layer"), py::arg("B"), py::arg("ws"), py::arg("grad"), py::arg("bgrad"), py::arg("target") = 0);

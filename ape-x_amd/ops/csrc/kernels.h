@@ -390,6 +390,10 @@ struct F32Prob {
   const float* w2;    // unused
   const float* bias;
   float* out;         // activations (conv) | split-K partials [7][B][256] (FC1)
+  // optional (conv layers, problem 0 of the gradient pass): one bit per stored activation, set
+  // exactly when it is > 0, row-major words of 32 channels -- bits1 [B][400] (conv1),
+  // bits2 [B][81][2] (conv2), bits3 [B][49][2] (conv3): the ReLU masks of the input gradients
+  uint32_t* relu_bits;
 };
 struct F32Set {
   F32Prob p[kMaxProbs];
@@ -411,6 +415,16 @@ struct ConvSample {
   int exclude_last;
   StagedRows rows;
   int nhost;  // set by the launcher
+  // optional compact rows of the drawn batch (problem 0's drawing waves, staged rows resolved
+  // like the frame ids): [B][4] frame ids of s, [B] action / reward / done -- the conv1 weight
+  // gradient and the loss launch then read row b directly (no idx -> table lookups)
+  int* batch_fid;
+  int* batch_act;
+  float* batch_rew;
+  float* batch_done;
+  const int* src_act;  // the transition table's action / reward / done columns (rows not staged)
+  const float* src_rew;
+  const float* src_done;
 };
 void f32_conv_fwd_multi(int layer, const F32Set& set, hipStream_t s, int c1_grid = 0, int tile = 0,
                         const ConvSample* draw = nullptr);  // draw: layer 1 only
@@ -427,6 +441,13 @@ int f32_stage_split();
 // Bit-identical at every depth; read at launch (graphs keep the depth they captured).
 void f32_set_prefetch(int mask);
 int f32_prefetch();
+// What the draw / the forward of the gradient pass resolve once for the backward: mask = 1 (the
+// ReLU sign bits: written by the conv forwards, read by the input gradients in place of the fp32
+// activations) + 2 (the drawn batch's compact rows: frame ids, action, reward, done); unset reads
+// APEX_F32_BATCH_RESOLVE (default 1: the sign bits; profiles/backward_sign_bits.md).  The callers
+// consult it when they wire the pointers; every setting computes the same values.
+void f32_set_batch_resolve(int mask);
+int f32_batch_resolve();
 int f32_fc1_fwd_multi(const F32Set& set, hipStream_t s);  // returns the slab count
 // target: conv2 / conv3 weight-gradient workgroups (<= 0: the default); the workspace, the
 // launch and the finalize job of one gradient must use the same value
@@ -436,13 +457,17 @@ size_t f32_wgrad_workspace_floats(int layer, int B, int target = 0);
 int f32_fc1_wgrad_splits();
 int f32_fc1_wgrad_slices(int B);
 size_t f32_fc1_wgrad_workspace_floats();
+// mask_bits (optional): a3's sign bits (bits3) -- the fp32 a3 is then read only as the weight
+// gradient's operand
 void f32_fc1_bwd_split(const float* dz, const float* a3, const float* wfc1p, float* dy3, float* ws, int B,
-                       hipStream_t s, const TreeRide* ride = nullptr);
+                       hipStream_t s, const TreeRide* ride = nullptr, const uint32_t* mask_bits = nullptr);
 // conv backward: layers 3/2 = wgrad partials + dgrad (w = w3t / w2t, masked by `mask`) in
 // one launch, layer 1 = wgrad partials from the u8 frames (x/ids/idx as FrameSrc)
 void f32_conv_bwd(int layer, const void* x, const int* ids, const int* idx, const float* dy, const float* w,
                   const float* mask, float* dx, float* ws, int B, hipStream_t s, int target = 0, int tile = 0,
-                  const TreeRide* ride = nullptr);  // ride: layers 3 / 2 only
+                  const TreeRide* ride = nullptr,  // ride: layers 3 / 2 only
+                  const uint32_t* mask_bits = nullptr,  // layers 3 / 2: the sign bits of `mask` (read instead)
+                  const int* batch_fid = nullptr);      // layer 1: the batch's frame ids [B][4] (ids / idx unread)
 FinalizeJob f32_conv_finalize_job(int layer, int B, const float* ws, float* grad, float* bias_grad, int target = 0);
 // grad_finalize job that only adds sum(g^2) of g[0..n) to the norm partials
 FinalizeJob norm_only_job(const float* g, int n);

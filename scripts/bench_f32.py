@@ -8,7 +8,8 @@ three-term split; the percentage is of the 157.3 TF fp32 MFMA peak, for comparis
 us/launch and achieved TFLOP/s (157.3 TF = fp32 MFMA peak); ``--graph 0`` launches
 eagerly (for rocprofv3 --pmc, one dispatch per launch).  ``--prefetch D`` runs every GEMM at
 prefetch depth D (1..3 k-blocks of operand loads in flight), ``--stage-split MASK`` in the
-given GEMM forms (APEX_F32_STAGE_SPLIT's mask)."""
+given GEMM forms (APEX_F32_STAGE_SPLIT's mask), ``--sign-bits 1`` with the ReLU sign bits (the conv
+forwards write them for problem 0, the input gradients read them in place of the fp32 masks)."""
 import argparse
 import json
 import os
@@ -39,6 +40,7 @@ ap.add_argument("--wgrad-targets", default="", help="extra conv2/conv3 backward 
 ap.add_argument("--prefetch", type=int, default=0, choices=[0, 1, 2, 3],
                 help="GEMM prefetch depth of every launch class (0: the defaults / APEX_F32_PREFETCH)")
 ap.add_argument("--stage-split", type=int, default=-1, help="GEMM form mask (-1: the defaults)")
+ap.add_argument("--sign-bits", type=int, default=0, choices=[0, 1], help="ReLU sign bits written / read (see above)")
 a = ap.parse_args()
 dev = torch.device("cuda")
 hip = ops.hip()
@@ -67,23 +69,28 @@ def S() -> int:  # the CURRENT stream at launch time (graph capture runs on a si
 
 def set3(layer):
     out = []
-    for ws in wss:
+    for k, ws in enumerate(wss):
         if layer == 1:
-            out.append((frames.data_ptr(), ids.data_ptr(), idx.data_ptr(), f[0].weight.data_ptr(), 0,
-                        f[0].bias.data_ptr(), ws.a1.data_ptr()))
+            t = (frames.data_ptr(), ids.data_ptr(), idx.data_ptr(), f[0].weight.data_ptr(), 0, f[0].bias.data_ptr(),
+                 ws.a1.data_ptr())
         elif layer == 2:
-            out.append((ws.a1.data_ptr(), 0, 0, net.w2p.data_ptr(), 0, f[2].bias.data_ptr(), ws.a2.data_ptr()))
+            t = (ws.a1.data_ptr(), 0, 0, net.w2p.data_ptr(), 0, f[2].bias.data_ptr(), ws.a2.data_ptr())
         elif layer == 3:
-            out.append((ws.a2.data_ptr(), 0, 0, net.w3p.data_ptr(), 0, f[4].bias.data_ptr(), ws.a3.data_ptr()))
+            t = (ws.a2.data_ptr(), 0, 0, net.w3p.data_ptr(), 0, f[4].bias.data_ptr(), ws.a3.data_ptr())
         else:
-            out.append((ws.a3.data_ptr(), 0, 0, net.wfc1p.data_ptr(), 0, 0, ws.z.data_ptr()))
+            t = (ws.a3.data_ptr(), 0, 0, net.wfc1p.data_ptr(), 0, 0, ws.z.data_ptr())
+        if a.sign_bits and k == 0 and layer <= 3:  # problem 0 also writes its sign bits
+            t += (getattr(ws, f"bits{layer}").data_ptr(),)
+        out.append(t)
     return out
 
 
 from apex_amd.models.fused import forward_multi  # noqa: E402
 
-forward_multi([(net, frames, wss[0], ids, idx), (net, frames, wss[1], ids, idx), (net, frames, wss[2], ids, idx)])
+forward_multi([(net, frames, wss[0], ids, idx), (net, frames, wss[1], ids, idx), (net, frames, wss[2], ids, idx)],
+              sign_bits=bool(a.sign_bits))
 ws = wss[0]
+mb = (lambda L: getattr(ws, f"bits{L}").data_ptr()) if a.sign_bits else (lambda L: 0)  # noqa: E731
 ws.dz.normal_()
 ws.dz.mul_((ws.h > 0).float())
 w1, w2, w3 = net._wgrad_wss
@@ -94,13 +101,13 @@ cases = {
     "conv3_fwd": (lambda: hip.f32_conv_fwd_multi(3, set3(3), B, S()), 2 * P * 49 * 64 * 576),
     "fc1_fwd": (lambda: hip.f32_fc1_fwd_multi(set3(4), B, S()), 2 * P * 256 * 3136),
     "fc1_bwd": (lambda: hip.f32_fc1_bwd_split(ws.dz.data_ptr(), ws.a3.data_ptr(), net.wfc1p.data_ptr(),
-                                              ws.dy3.data_ptr(), net._fc1_ws.data_ptr(), B, S()),
+                                              ws.dy3.data_ptr(), net._fc1_ws.data_ptr(), B, S(), mask_bits=mb(3)),
                 2 * 2 * B * 256 * 3136),
     "conv3_bwd": (lambda: hip.f32_conv_bwd(3, ws.a2.data_ptr(), 0, 0, ws.dy3.data_ptr(), net.w3t.data_ptr(),
-                                           ws.a2.data_ptr(), ws.dy2.data_ptr(), w3.data_ptr(), B, S()),
+                                           ws.a2.data_ptr(), ws.dy2.data_ptr(), w3.data_ptr(), B, S(), mask_bits=mb(2)),
                   2 * 2 * B * 49 * 64 * 576),
     "conv2_bwd": (lambda: hip.f32_conv_bwd(2, ws.a1.data_ptr(), 0, 0, ws.dy2.data_ptr(), net.w2t.data_ptr(),
-                                           ws.a1.data_ptr(), ws.dy1.data_ptr(), w2.data_ptr(), B, S()),
+                                           ws.a1.data_ptr(), ws.dy1.data_ptr(), w2.data_ptr(), B, S(), mask_bits=mb(1)),
                   2 * 2 * B * 81 * 64 * 512),
     "finalize": (lambda: hip.grad_finalize(
         [hip.f32_conv_finalize_job(k, B, wsp.data_ptr(), f[2 * k - 2].weight.grad.data_ptr(),
