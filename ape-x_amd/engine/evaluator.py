@@ -14,8 +14,16 @@ the latest published weights (the engine's actor weights, as the reference evalu
 takes the learner's PUB stream); ``run(k)`` advances every env ``k`` steps on the
 caller's stream (a side stream in ``train.py``); ``poll()`` returns the episodes
 finished since the last poll (a host read of the [E, 4] episode log).
+
+``rollout(k)`` is ``run(k)`` in one launch (``atari_rollout``, fp32 HIP forward only): one
+workgroup per env runs forward -> action -> env step -> render ``k`` times and leaves every
+buffer as ``run(k)`` does, so the two may alternate.  It also fills ``ep_ring`` (the last
+``RING`` episodes per env; ``poll_ring()``), since a long chunk ends several episodes per env.
+:class:`AtariEvaluator` runs rollouts of a weight snapshot on a side stream beside training.
 """
 from __future__ import annotations
+
+import collections
 
 import torch
 
@@ -26,6 +34,9 @@ from .hbm_replay import FRAME_BYTES
 
 
 class GPUEvaluator:
+    RING = 16           # episodes per env kept by ``ep_ring``
+    MAX_ROLLOUT = 10000  # steps per ``atari_rollout`` launch
+
     def __init__(self, src_model: DuelingDQN, n_envs: int = 8, n_actions: int = 18, forward: str = "hip",
                  dtype: str = "fp32", device="cuda", seed: int = 0, episode_life: bool = True,
                  max_episode_steps: int = 50000, action_repeat: int = 4, epsilon: float = 0.0):
@@ -71,6 +82,9 @@ class GPUEvaluator:
         self.steps = 0
         self.max_episode_steps = int(max_episode_steps)
         self._graph, self._graph_steps = None, 0
+        # (return, length) of the last RING episodes per env: written by ``rollout`` only
+        self.ep_ring = torch.zeros(E, self.RING, 2, **f32)
+        self._ring_seen = torch.zeros(E)
 
     @staticmethod
     def _stream() -> int:
@@ -119,6 +133,46 @@ class GPUEvaluator:
         for _ in range(n_steps):
             self.step()
 
+    def _rollout_args(self) -> dict:
+        m, f, net = self.model, self.model.features, self.net
+        t = {"w1": f[0].weight, "b1": f[0].bias, "w2p": net.w2p, "b2": f[2].bias, "w3p": net.w3p, "b3": f[4].bias,
+             "wfc1p": net.wfc1p, "ba1": m.advantage[0].bias, "bv1": m.value[0].bias, "wa2": m.advantage[2].weight,
+             "ba2": m.advantage[2].bias, "wv2": m.value[2].weight, "bv2": m.value[2].bias, "eps": self.eps,
+             "counter": self.counter, "env_state": self.env_state, "hist": self.hist, "frames": self.frames,
+             "new_frame": self.new_frame, "ep_log": self.ep_log, "reward": self.reward, "done": self.done,
+             "actions": self.actions, "ep_ring": self.ep_ring}
+        d = {k: v.data_ptr() for k, v in t.items()}
+        d.update(env_seed=self.seed, act_seed=self.seed ^ 0xE7A1, ring_R=self.RING)
+        return d
+
+    def rollout(self, n_steps: int, trace: dict | None = None) -> None:
+        """``run(n_steps)`` as one ``atari_rollout`` launch per at most 10,000 steps on the current
+        stream, each followed by the stream-ordered counter advance.  ``trace``: ``q`` f32
+        [E, T, A], ``act`` i32 [E, T], ``rew`` / ``done`` f32 [E, T] for the first T steps."""
+        if self.forward_mode != "hip" or self.dtype != "fp32":
+            raise ValueError(f"rollout needs the fp32 HIP forward (forward='{self.forward_mode}', "
+                             f"dtype='{self.dtype}')")
+        n_steps = int(n_steps)
+        if n_steps < 1:
+            raise ValueError("rollout: n_steps >= 1")
+        args = self._rollout_args()
+        if trace is not None:
+            q, act = trace["q"], trace["act"]
+            assert q.dtype == torch.float32 and act.dtype == torch.int32 and q.is_contiguous()
+            assert q.shape[0] >= self.E and q.shape[2] == self.A and tuple(act.shape) == tuple(q.shape[:2])
+            args.update(trace_q=q.data_ptr(), trace_act=act.data_ptr(), trace_rew=trace["rew"].data_ptr(),
+                        trace_done=trace["done"].data_ptr(), trace_T=int(q.shape[1]))
+        left = n_steps
+        while left > 0:
+            k = min(left, self.MAX_ROLLOUT)
+            args["n_steps"] = k
+            self.hip.atari_rollout(self.hip.make_atari_rollout(self.params, args), self._stream())
+            self.counter.add_(k)
+            left -= k
+            for key in ("trace_q", "trace_act", "trace_rew", "trace_done", "trace_T"):
+                args.pop(key, None)  # the trace covers the first launch's first steps
+        self.steps += n_steps
+
     def capture(self, steps: int = 100) -> None:
         """Capture ``steps`` greedy steps as one hipGraph on the current stream (the
         evaluator's ~8 launches per step are host-bound when eager: a budget that finishes
@@ -149,3 +203,110 @@ class GPUEvaluator:
         self.episodes += int((log[:, 2] - self._seen).clamp_min(0).sum())
         self._seen = log[:, 2].clone()
         return out
+
+    @staticmethod
+    def ring_episodes(ring: torch.Tensor, counts: torch.Tensor, seen: torch.Tensor) -> list[tuple[float, float]]:
+        """The episodes ``seen[e] .. counts[e] - 1`` of every env still in its ring (the newest
+        ``R``), oldest first: episode i of env e is ring slot ``i % R``."""
+        R = ring.shape[1]
+        out = []
+        for e in range(ring.shape[0]):
+            c, s0 = int(counts[e]), int(seen[e])
+            for i in range(max(s0, c - R), c):
+                out.append((float(ring[e, i % R, 0]), float(ring[e, i % R, 1])))
+        return out
+
+    def poll_ring(self) -> list[tuple[float, float]]:
+        """Every episode finished since the last ``poll_ring`` (up to ``RING`` per env, oldest
+        first) from ``ep_ring``: episodes that ``rollout`` ended (stepwise steps do not fill it)."""
+        ring, counts = self.ep_ring.cpu(), self.ep_log[:, 2].cpu()
+        out = self.ring_episodes(ring, counts, self._ring_seen)
+        self._ring_seen = counts.clone()
+        self.episodes = int(counts.sum())
+        return out
+
+    # ---- the device side of AtariEvaluator
+    def snapshot(self, src_flat: torch.Tensor, src_net) -> None:
+        """Device copies of the source weights on the current stream: the flat parameters and
+        the forward arena."""
+        self.hip.copy_f32(self.flat.data_ptr(), src_flat.data_ptr(), self.flat.numel(), self._stream())
+        self.net.copy_packed_from(src_net)
+
+    def host_results(self) -> dict:
+        E = self.E
+        return {"ring": torch.zeros(E, self.RING, 2).pin_memory(), "counts": torch.zeros(E).pin_memory(),
+                "running": torch.zeros(E, 2).pin_memory()}
+
+    def copy_results(self, host: dict) -> None:
+        host["ring"].copy_(self.ep_ring, non_blocking=True)
+        host["counts"].copy_(self.ep_log[:, 2], non_blocking=True)
+        host["running"].copy_(self.env_state[:, 25:27], non_blocking=True)  # S_EPRET, S_EPLEN
+
+
+class AtariEvaluator:
+    """Greedy evaluation beside training.  ``launch()`` snapshots the source weights on the
+    current (training) stream into the evaluator's own copies and plays ``n_steps`` greedy
+    steps with ``GPUEvaluator.rollout`` on a side stream; the finished episodes and the running
+    (return, length) land in pinned host memory and ``poll()`` / ``wait()`` hand each result
+    over exactly once.  While a launch is in flight a further ``launch()`` does nothing (the
+    snapshot may still be read by the running kernel): evaluations conflate.  The training
+    stream never waits on the side stream; all launches are eager, between graph replays.
+
+    ``stream`` / ``event`` / ``stream_ctx`` default to ``torch.cuda``'s (host tests pass fakes)."""
+
+    def __init__(self, evaluator, stream=None, event=None, stream_ctx=None):
+        self.ev = evaluator
+        self.stream = torch.cuda.Stream(device=evaluator.device) if stream is None else stream
+        self._ctx = torch.cuda.stream if stream_ctx is None else stream_ctx
+        make = torch.cuda.Event if event is None else event
+        self.snapshot_taken, self.results_landed = make(), make()
+        self.host = evaluator.host_results()
+        self._seen = torch.zeros_like(self.host["counts"])
+        self._pending, self._tag = False, None
+        self._done = collections.deque()
+        self.launches = 0
+
+    def launch(self, src_flat, src_net, n_steps: int, tag=None) -> bool:
+        """Start one evaluation chunk of the source weights as they are at this point of the
+        current stream.  ``False`` (and nothing done) while the previous one has not landed."""
+        if self._pending:
+            if not self.results_landed.query():
+                return False
+            self._harvest()  # the pinned buffers are about to be reused
+        self.ev.snapshot(src_flat, src_net)
+        self.snapshot_taken.record()
+        with self._ctx(self.stream):
+            self.stream.wait_event(self.snapshot_taken)
+            self.ev.rollout(n_steps)
+            self.ev.copy_results(self.host)
+            self.results_landed.record()
+        self._pending, self._tag = True, tag
+        self.launches += 1
+        return True
+
+    def _harvest(self) -> None:
+        self._pending = False
+        h = self.host
+        counts = h["counts"].clone()
+        eps = GPUEvaluator.ring_episodes(h["ring"], counts, self._seen)
+        self._seen = counts
+        self._done.append({"tag": self._tag, "episodes": eps, "total_episodes": int(counts.sum()),
+                           "running_return": h["running"][:, 0].tolist(),
+                           "running_length": h["running"][:, 1].tolist()})
+
+    def poll(self) -> dict | None:
+        """The oldest landed result not yet handed over (each exactly once), or ``None``."""
+        if self._pending and self.results_landed.query():
+            self._harvest()
+        return self._done.popleft() if self._done else None
+
+    def wait(self) -> dict | None:
+        """As ``poll()``, but blocks until the launch in flight has landed: on the results event
+        only, never on the device.  ``None`` if nothing was launched."""
+        if self._done:
+            return self._done.popleft()
+        if not self._pending:
+            return None
+        self.results_landed.synchronize()
+        self._harvest()
+        return self._done.popleft()

@@ -940,6 +940,35 @@ PYBIND11_MODULE(_apex_hip, m) {
     return r;
   });
   m.def("aql_rollout", [](const AqlRollout& r, uint64_t s) { aql_rollout(r, S(s)); });
+  // n_steps greedy steps of every Atari evaluator env in one launch (atari_rollout_kernels.hip)
+  py::class_<AtariRollout>(m, "AtariRollout");
+  // d: w1, b1, w2p, b2, w3p, b3, wfc1p, ba1, bv1, wa2, ba2, wv2, bv2, n_steps, env_seed, act_seed, eps, counter,
+  // env_state, hist, frames, new_frame, ep_log, reward, done, actions [+ ep_ring, ring_R]
+  // [+ trace_q, trace_act, trace_rew, trace_done, trace_T]
+  m.def("make_atari_rollout", [](const VecEnvParams& p, py::dict d) {
+    auto opt = [&](const char* k) { return d.contains(k) ? d[k].cast<uint64_t>() : (uint64_t)0; };
+    AtariRollout r{};
+    r.p = p;
+    r.w1 = P<const float>(opt("w1")); r.b1 = P<const float>(opt("b1"));
+    r.w2p = P<const float>(opt("w2p")); r.b2 = P<const float>(opt("b2"));
+    r.w3p = P<const float>(opt("w3p")); r.b3 = P<const float>(opt("b3"));
+    r.wfc1p = P<const float>(opt("wfc1p"));
+    r.ba1 = P<const float>(opt("ba1")); r.bv1 = P<const float>(opt("bv1"));
+    r.wa2 = P<const float>(opt("wa2")); r.ba2 = P<const float>(opt("ba2"));
+    r.wv2 = P<const float>(opt("wv2")); r.bv2 = P<const float>(opt("bv2"));
+    r.n_steps = d["n_steps"].cast<int>();
+    r.env_seed = d["env_seed"].cast<uint64_t>(); r.act_seed = d["act_seed"].cast<uint64_t>();
+    r.eps = P<const float>(opt("eps")); r.counter = P<const int64_t>(opt("counter"));
+    r.env_state = P<float>(opt("env_state")); r.hist = P<int>(opt("hist")); r.frames = P<uint8_t>(opt("frames"));
+    r.new_frame = P<int>(opt("new_frame")); r.ep_log = P<float>(opt("ep_log"));
+    r.reward = P<float>(opt("reward")); r.done = P<float>(opt("done")); r.actions = P<int>(opt("actions"));
+    r.ep_ring = P<float>(opt("ep_ring")); r.ring_R = d.contains("ring_R") ? d["ring_R"].cast<int>() : 0;
+    r.trace_q = P<float>(opt("trace_q")); r.trace_act = P<int>(opt("trace_act"));
+    r.trace_rew = P<float>(opt("trace_rew")); r.trace_done = P<float>(opt("trace_done"));
+    r.trace_T = d.contains("trace_T") ? d["trace_T"].cast<int>() : 0;
+    return r;
+  });
+  m.def("atari_rollout", [](const AtariRollout& r, uint64_t s) { atari_rollout(r, S(s)); });
   // one env's acting frame of the single-process AQL trainer (aql_frame_kernels.hip)
   py::class_<AqlFrame>(m, "AqlFrame");
   m.def("make_aql_frame", [](const AQLNet& net, const AqlEnv& env, const AqlInsert& ins, const TreeHandle& tree,

@@ -124,6 +124,44 @@ void vec_env_step(float* state, const int* actions, uint64_t seed, const int64_t
 void select_actions(const float* q, int E, int A, const float* eps, uint64_t seed, const int64_t* counter,
                     int* actions, hipStream_t s);
 
+// ---- atari_rollout_kernels.hip
+// n_steps greedy steps of every evaluator env in one launch (one workgroup per env): per step
+// the fp32 Nature-CNN dueling forward on the env's own 4-frame stack, select_actions' rule and
+// draw at counter + k, vec_env_step's game logic and render (atari_env_dev.h) and
+// frame_hist_step's stack advance.  Every buffer is left as n_steps stepwise steps leave it;
+// the step counter is only read (advance it by n_steps with a stream-ordered op afterwards).
+// ep_ring (optional): slot ep_log[e][2] % ring_R of env e takes (return, length) at every
+// agent-level done.  The trace (all four pointers or none) covers the first trace_T steps.
+struct AtariRollout {
+  const float *w1, *b1;        // features.0 weight (32,4,8,8) / bias (master layout)
+  const float *w2p, *b2;       // conv2 weight (64,4,4,32) of the fp32 forward arena / bias
+  const float *w3p, *b3;       // conv3 weight (64,3,3,64) / bias
+  const float *wfc1p;          // (256,49,64): advantage.0 rows then value.0 rows
+  const float *ba1, *bv1;      // advantage.0 / value.0 bias [128]
+  const float *wa2, *ba2;      // advantage.2 [A][128] / [A]
+  const float *wv2, *bv2;      // value.2 [128] / [1]
+  VecEnvParams p;
+  int n_steps;
+  uint64_t env_seed, act_seed;
+  const float* eps;            // [E]
+  const int64_t* counter;      // step counter at launch (read only)
+  float* env_state;            // [E][32]
+  int* hist;                   // [E][4]
+  uint8_t* frames;             // [F][84*84]
+  int* new_frame;              // [E]
+  float* ep_log;               // [E][4]
+  float *reward, *done;        // [E]
+  int* actions;                // [E]
+  float* ep_ring;              // optional [E][ring_R][2]
+  int ring_R;
+  float* trace_q;              // optional [E][trace_T][A]
+  int* trace_act;              // optional [E][trace_T]
+  float* trace_rew;            // optional [E][trace_T]
+  float* trace_done;           // optional [E][trace_T]
+  int trace_T;
+};
+void atari_rollout(const AtariRollout& r, hipStream_t s);
+
 struct NStepParams {
   int E, A, n, C;   // envs, actions, n-step, transition capacity
   float gamma;

@@ -55,6 +55,11 @@ def parser():
                         "capped episode (max_episode_length steps) inside each log window of --bps_interval "
                         "learner steps (run as captured graphs of 100 steps; slows training wall-clock, not "
                         "its per-step dynamics)")
+    p.add_argument("--eval-mode", choices=["step", "rollout", "async"], default="step",
+                   help="step: stepwise greedy steps on a side stream (captured graphs of 100 steps); rollout: "
+                        "each chunk as one atari_rollout launch; async: one-launch chunks of a weight snapshot "
+                        "beside training, a chunk that would queue behind a running one is skipped (the "
+                        "one-launch modes need --forward hip --dtype fp32)")
     return p
 
 
@@ -221,9 +226,13 @@ def main(argv=None) -> int:
     if rank == 0:
         print(f"replay warm ({time.perf_counter() - t_fill:.1f}s); training from step {start}", flush=True)
 
-    evaluator = None
+    evaluator, async_eval = None, None
+    eval_mode = args.eval_mode
     if rank == 0 and args.eval_envs > 0:
-        from .engine.evaluator import GPUEvaluator
+        from .engine.evaluator import AtariEvaluator, GPUEvaluator
+
+        if eval_mode != "step" and (cfg.kernel.forward != "hip" or cfg.kernel.dtype != "fp32"):
+            raise SystemExit(f"--eval-mode {eval_mode} needs --forward hip --dtype fp32")
 
         src_model = eng.actor_model if hasattr(eng, "actor_model") else learner.model
         evaluator = GPUEvaluator(src_model, args.eval_envs, args.actions, forward=cfg.kernel.forward,
@@ -236,26 +245,58 @@ def main(argv=None) -> int:
             eval_steps = -(-int(cfg.env.max_episode_length) // chunks)
         else:
             eval_steps = int(args.eval_steps)
-        if cfg.kernel.use_graphs and eval_steps >= 100:
+        if eval_mode == "async":
+            async_eval = AtariEvaluator(evaluator)
+        if eval_mode == "step" and cfg.kernel.use_graphs and eval_steps >= 100:
             with torch.cuda.stream(eval_stream):
                 evaluator.capture(100)
             torch.cuda.synchronize(device)
         print(f"evaluator: {args.eval_envs} envs, {eval_steps} greedy steps per {args.eval_interval} learner steps "
-              f"(episode cap {int(cfg.env.max_episode_length)})", flush=True)
+              f"(episode cap {int(cfg.env.max_episode_length)}, mode {eval_mode})", flush=True)
+
+    def eval_source():
+        if hasattr(eng, "actor_flat"):
+            return eng.actor_flat, getattr(eng, "actor_net", None)
+        return learner.flat, getattr(learner, "net", None)
 
     def eval_chunk():
         """Latest published weights -> evaluator (ordered after the publish on the training
         stream, which in turn waits only for the copy), then greedy steps on the side stream."""
+        if async_eval is not None:  # snapshot on this stream, the chunk on its own; skipped while one runs
+            async_eval.launch(*eval_source(), eval_steps, tag=eng.learn_steps)
+            return
         cur = torch.cuda.current_stream(device)
         eval_stream.wait_stream(cur)
         with torch.cuda.stream(eval_stream):
-            if hasattr(eng, "actor_flat"):
-                evaluator.load(eng.actor_flat, getattr(eng, "actor_net", None))
-            else:
-                evaluator.load(learner.flat, getattr(learner, "net", None))
+            evaluator.load(*eval_source())
             ev_loaded.record(eval_stream)
-            evaluator.run(eval_steps)
+            if eval_mode == "rollout":
+                evaluator.rollout(eval_steps)
+            else:
+                evaluator.run(eval_steps)
         cur.wait_event(ev_loaded)
+
+    async_state = {"episodes": 0.0, "running": None}
+
+    def async_eval_line(line: dict, results) -> None:
+        """The ``evaluator/*`` tags from landed async chunks (``running_*``: the last one landed)."""
+        for res in results:
+            for r, n in res["episodes"]:
+                eval_rets.append(r)
+                eval_lens.append(n)
+            async_state["episodes"] = float(res["total_episodes"])
+            async_state["running"] = (res["running_return"], res["running_length"])
+        if eval_rets:
+            line["evaluator/episode_reward"] = sum(eval_rets) / len(eval_rets)
+            line["evaluator/episode_length"] = sum(eval_lens) / len(eval_lens)
+            line["evaluator/episodes"] = async_state["episodes"]
+            line["evaluator/capped_episodes"] = float(sum(n >= evaluator.max_episode_steps for n in eval_lens))
+            del eval_rets[:], eval_lens[:]
+        if async_state["running"] is not None:
+            line["evaluator/chunks"] = float(async_eval.launches)  # chunks started (the others were skipped)
+            rr, rl = async_state["running"]
+            line["evaluator/running_return"] = sum(rr) / len(rr)
+            line["evaluator/running_length"] = sum(rl) / len(rl)
 
     max_step = int(L.max_step)
     bps_every = max(1, L.bps_interval)
@@ -270,7 +311,10 @@ def main(argv=None) -> int:
         if evaluator is not None and step % max(1, args.eval_interval) == 0:
             eval_chunk()
         if learner is not None and step % bps_every == 0:
-            torch.cuda.synchronize(device)
+            if async_eval is not None:  # the evaluation chunk goes on beside the next steps
+                torch.cuda.current_stream(device).synchronize()
+            else:
+                torch.cuda.synchronize(device)
             now = time.perf_counter()
             dt_log = now - t_last
             sps = (step - step_last) / dt_log
@@ -289,8 +333,10 @@ def main(argv=None) -> int:
                         "learner/batches_per_sec": sps * (world if topology == "sharded" else 1),
                         "actor/frames_per_sec": (fps_measured if topology == "central"
                                                  else sps * frames_per_round)}
-                if evaluator is not None:
-                    for r, n in evaluator.poll():
+                if async_eval is not None:
+                    async_eval_line(line, iter(async_eval.poll, None))
+                elif evaluator is not None:
+                    for r, n in (evaluator.poll_ring() if eval_mode == "rollout" else evaluator.poll()):
                         eval_rets.append(r)
                         eval_lens.append(n)
                     if eval_rets:  # episodes finished since the last log line
@@ -319,6 +365,15 @@ def main(argv=None) -> int:
         if L.save_interval and step % L.save_interval == 0 and rank == 0 and learner is not None:
             print("Saving Model..", flush=True)
             save_engine(learner, args.save_path, {"learn_steps": step, "actor_steps": eng.actor_steps})
+    if async_eval is not None:  # the last evaluation is logged
+        line = {}
+        res = async_eval.wait()
+        async_eval_line(line, [res] if res is not None else [])
+        if line:
+            print(f"Step: {step} " + " ".join(f"{k}={v:.4g}" for k, v in line.items()), flush=True)
+            if writer is not None:
+                for k, v in line.items():
+                    writer.add_scalar(k, v, step)
     torch.cuda.synchronize(device)
     if rank == 0 and learner is not None:
         save_engine(learner, args.save_path, {"learn_steps": step, "actor_steps": eng.actor_steps})
