@@ -15,15 +15,26 @@ learner graph are shared with the GPU-env engine, unchanged.
 actor forward, copies the actions out, enqueues ``k`` learner steps, and only then steps the
 emulators on the host -- the GPU trains while the CPU emulates.
 
+Emulator worker processes live behind the vector-env protocol
+(:class:`apex_amd.envs.proc_vector.ProcRawAtariVector`); what this module adds for them is the
+device side of a pool.  A vector env that exposes ``staging`` (its shared ``[N, 2, H, W, 3]``
+block) is read in place: the shard registers the block with HIP and copies out of it with
+``memcpy_h2d_async`` on the engine's stream, so no host memcpy moves the pairs into a second
+pinned buffer.  A vector env that exposes ``banks`` and ``step_async`` / ``wait_bank`` is ingested
+bank by bank (``HostEnvConfig.ingest``): each worker's env range gets its own H2D copies and one
+ranged ``host_env_ingest_range`` launch as soon as that worker is done, while the other workers
+are still emulating.  A range launch writes exactly what the whole launch writes for its envs, so
+the banked, the whole and the in-process paths fill the ring and the replay identically.
+
 Out of scope here: double-banked env groups (stepping one half of the envs while the other
-half's forward runs), a device evaluator, and the multi-GPU topologies (``parallel/``,
-``engine/central.py``); worker processes / threads for the emulators live behind the vector-env
-protocol, not in this module.
+half's forward runs), a device evaluator for host envs, and the multi-GPU topologies
+(``parallel/``, ``engine/central.py``).
 """
 from __future__ import annotations
 
 import copy
 import time
+import weakref
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -40,6 +51,20 @@ from .learner import DQNLearner, LearnerConfig, forward_q
 
 OUT = 84          # the warp's output side (kHostEnvOut)
 TAP_WIDTH = 8     # weights per output index in the tap tables (kHostEnvTaps)
+INGEST_MODES = ("auto", "whole", "banked")
+
+
+def has_banks(vec) -> bool:
+    """Does ``vec`` offer the banked form (``banks``, ``step_async``, ``wait_bank``)?"""
+    return all(hasattr(vec, a) for a in ("banks", "step_async", "wait_bank"))
+
+
+def _unregister(hip, ptr: int, keep) -> None:
+    """Finalizer of a registered staging block (``keep`` holds the mapping until here)."""
+    try:
+        hip.host_unregister(ptr)
+    except RuntimeError:
+        pass
 
 
 # ---------------------------------------------------------------------------- tap tables
@@ -94,6 +119,15 @@ class Ingest:
                                  reward.data_ptr(), done.data_ptr(), new_frame.data_ptr(), hist.data_ptr(),
                                  acc.data_ptr(), ep_log.data_ptr(), torch.cuda.current_stream().cuda_stream)
 
+    def range(self, e0: int, n: int, raw, reward_in, done_in, frames, step_counter, reset: bool, reward, done,
+              new_frame, hist, acc, ep_log) -> None:
+        """The same launch over envs ``[e0, e0 + n)``; every tensor is the whole shard's."""
+        self.hip.host_env_ingest_range(raw.data_ptr(), reward_in.data_ptr(), done_in.data_ptr(), self.taps[0],
+                                       self.taps[1], frames.data_ptr(), self.params, step_counter.data_ptr(),
+                                       bool(reset), reward.data_ptr(), done.data_ptr(), new_frame.data_ptr(),
+                                       hist.data_ptr(), acc.data_ptr(), ep_log.data_ptr(), int(e0), int(n),
+                                       torch.cuda.current_stream().cuda_stream)
+
 
 # ---------------------------------------------------------------------------- shard
 class HostEnvShard:
@@ -104,7 +138,11 @@ class HostEnvShard:
 
     def __init__(self, replay, n_envs: int, n_actions: int, raw_shape, n_step: int = 3, gamma: float = 0.99,
                  eps_base: float = 0.4, eps_alpha: float = 7.0, actor_offset: int = 0, total_actors: int | None = None,
-                 seed: int = 0, mode: str = "reference", clip_rewards: bool = True):
+                 seed: int = 0, mode: str = "reference", clip_rewards: bool = True, staging=None,
+                 ingest: str = "auto"):
+        if ingest not in INGEST_MODES:
+            raise ValueError(f"ingest must be one of {INGEST_MODES}, got {ingest!r}")
+        self.ingest_mode = ingest
         self.replay = replay
         self.E, self.A, self.n = int(n_envs), int(n_actions), int(n_step)
         assert replay.n_envs == self.E, "replay slot layout is sized for this shard's env count"
@@ -148,8 +186,20 @@ class HostEnvShard:
         self.nstep = self.hip.make_nstep(E, A, n, replay.capacity, float(gamma), 0 if mode == "reference" else 1,
                                          st_ptrs, replay.trans_ptrs())
         # host staging (pinned: the copies below are truly asynchronous) and the device twins
-        self.raw_host = torch.zeros(E, 2, H, W, 3, dtype=torch.uint8).pin_memory()
-        self.raw_np = self.raw_host.numpy()
+        self._registered = None
+        if staging is None:
+            self.raw_host = torch.zeros(E, 2, H, W, 3, dtype=torch.uint8).pin_memory()
+            self.raw_np = self.raw_host.numpy()
+        else:
+            # the vector env's own shared block, registered with HIP and read in place
+            if tuple(staging.shape) != (E, 2, H, W, 3) or staging.dtype != np.uint8 or not staging.flags.c_contiguous:
+                raise ValueError(f"staging must be a contiguous uint8 {(E, 2, H, W, 3)} array")
+            self.raw_host = None
+            self.raw_np = staging
+            self.raw_ptr = int(staging.ctypes.data)
+            self.hip.host_register(self.raw_ptr, int(staging.nbytes))
+            self._registered = weakref.finalize(self, _unregister, self.hip, self.raw_ptr, staging)
+        self.pair_bytes = 2 * H * W * 3
         self.raw_dev = torch.zeros(E, 2, H, W, 3, dtype=torch.uint8, device=dev)
         self.reward_host = torch.zeros(E, dtype=torch.float32).pin_memory()
         self.done_host = torch.zeros(E, dtype=torch.float32).pin_memory()
@@ -157,18 +207,45 @@ class HostEnvShard:
         self.reward_in = torch.zeros(E, **f32)
         self.done_in = torch.zeros(E, **f32)
         self.event = torch.cuda.Event()
-        self.raw_bytes_per_step = self.raw_host.numel() + 8 * E
+        self.raw_bytes_per_step = self.raw_dev.numel() + 8 * E
 
     def _ingest(self, reset: bool) -> None:
         self.ingest(self.raw_dev, self.reward_in, self.done_in, self.replay.frames, self.step_counter, reset,
                     self.reward, self.done, self.new_frame, self.st["hist"], self.acc, self.ep_log)
 
+    def _banked(self, vec) -> bool:
+        """Ingest bank by bank?  ``auto`` says yes whenever ``vec`` offers banks."""
+        if self.ingest_mode == "whole" or self._registered is None:
+            return False
+        return has_banks(vec)
+
+    def _ship(self, e0: int, e1: int, reset: bool) -> None:
+        """Envs ``[e0, e1)`` of the registered staging block: their H2D copies (pairs; reward and
+        done slices on a step) and one ingest launch over the range, on the current stream."""
+        s = torch.cuda.current_stream().cuda_stream
+        off = e0 * self.pair_bytes
+        self.hip.memcpy_h2d_async(self.raw_dev.data_ptr() + off, self.raw_ptr + off, (e1 - e0) * self.pair_bytes, s)
+        if not reset:
+            self.reward_in[e0:e1].copy_(self.reward_host[e0:e1], non_blocking=True)
+            self.done_in[e0:e1].copy_(self.done_host[e0:e1], non_blocking=True)
+        if e0 == 0 and e1 == self.E:
+            self._ingest(reset)
+        else:
+            self.ingest.range(e0, e1 - e0, self.raw_dev, self.reward_in, self.done_in, self.replay.frames,
+                              self.step_counter, reset, self.reward, self.done, self.new_frame, self.st["hist"],
+                              self.acc, self.ep_log)
+
     def reset(self, vec) -> None:
         """Start every env; the start frames fill the stacks (``vec_env_reset``'s outputs).  The
-        copy out of the pinned buffer is ordered like a step's (see :meth:`finish`)."""
+        copy out of the pinned buffer is ordered like a step's (see :meth:`finish`).  With a
+        registered staging block the pairs take a step's path: per bank, or as one range."""
         vec.reset(self.raw_np)
-        self.raw_dev.copy_(self.raw_host, non_blocking=True)
-        self._ingest(True)
+        if self._registered is None:
+            self.raw_dev.copy_(self.raw_host, non_blocking=True)
+            self._ingest(True)
+            return
+        for e0, e1 in (vec.banks if self._banked(vec) else [(0, self.E)]):
+            self._ship(e0, e1, True)
 
     def observe(self) -> torch.Tensor:
         """Current stacked observations u8 [E,4,84,84] (gathered from the frame ring)."""
@@ -203,20 +280,51 @@ class HostEnvShard:
         t+1's forward on the same stream, and the host waits for the event recorded after that
         forward before it writes the pinned buffers again -- when the wait returns, every copy
         that read them has completed.  (The same holds for the pinned reward / done / actions
-        buffers, and for the copy :meth:`reset` starts.)"""
+        buffers, and for the copy :meth:`reset` starts.)
+
+        The invariant keeps holding with worker processes and a registered shared staging block:
+        the workers are told to step (``step_async``) only after the host has waited for the event
+        recorded after the next forward, and by then every copy that read the staging block has
+        completed.  Within a step, a bank's copy reads only that bank's env range, which its
+        worker has finished writing; it may run while the other workers still write their own,
+        disjoint ranges.  Banked ingest: for each bank, in completion order, its H2D copies and
+        one ranged ingest launch; ``nstep_emit`` and ``write_batch`` follow once all banks are in."""
         self.event.synchronize()
-        r, d = vec.step(self.actions_host.numpy(), self.raw_np)
-        self.reward_host.numpy()[:] = r
-        self.done_host.numpy()[:] = d
-        self.raw_dev.copy_(self.raw_host, non_blocking=True)
-        self.reward_in.copy_(self.reward_host, non_blocking=True)
-        self.done_in.copy_(self.done_host, non_blocking=True)
-        self._ingest(False)
+        if self._registered is None:
+            r, d = vec.step(self.actions_host.numpy(), self.raw_np)
+            self.reward_host.numpy()[:] = r
+            self.done_host.numpy()[:] = d
+            self.raw_dev.copy_(self.raw_host, non_blocking=True)
+            self.reward_in.copy_(self.reward_host, non_blocking=True)
+            self.done_in.copy_(self.done_host, non_blocking=True)
+            self._ingest(False)
+        elif self._banked(vec):
+            vec.step_async(self.actions_host.numpy())
+            rh, dh = self.reward_host.numpy(), self.done_host.numpy()
+            for _ in vec.banks:
+                b, r, d = vec.wait_bank()
+                e0, e1 = vec.banks[b]
+                rh[e0:e1] = r
+                dh[e0:e1] = d
+                self._ship(e0, e1, False)
+        else:
+            r, d = vec.step(self.actions_host.numpy(), self.raw_np)   # (out is the staging block: no copy)
+            self.reward_host.numpy()[:] = r
+            self.done_host.numpy()[:] = d
+            self._ship(0, self.E, False)
         s = torch.cuda.current_stream().cuda_stream
         self.hip.nstep_emit(self.nstep, self.q.data_ptr(), self.actions.data_ptr(), self.reward.data_ptr(),
                             self.done.data_ptr(), self.new_frame.data_ptr(), self.step_counter.data_ptr(),
                             self.slot.data_ptr(), self.prio.data_ptr(), s, False)
         self.replay.write_batch(pre=(self.slot, self.prio, self.replay.filled), bump=self.step_counter)
+
+    def close(self) -> None:
+        """Let go of a registered staging block: wait for the copies that read it, unregister
+        it, drop the view.  Call before the vector env unlinks the block; idempotent."""
+        if self._registered is not None and self._registered.alive:
+            torch.cuda.synchronize(self.device)
+            self._registered()
+        self.raw_np = None
 
     def step_host(self, vec) -> None:
         """Both halves back to back (``self.actions`` already chosen)."""
@@ -254,6 +362,10 @@ class HostEnvConfig:
     warmup_learner_steps: int = 3             # eager learner steps before the graph is captured
     exact_mass: bool = False
     seed: int = 1122
+    # how a vector env with worker banks is ingested: "banked" = per-bank copies + ranged launches in
+    # completion order, "whole" = wait for every bank, then one copy and one launch, "auto" = banked
+    # when the vector env offers banks.  The in-process vector (no banks) is not affected.
+    ingest: str = "auto"
     learner: LearnerConfig = field(default_factory=LearnerConfig)
 
 
@@ -262,6 +374,11 @@ class HostEnvEngine:
         k = cfg.learner_steps_per_actor_step
         if not isinstance(k, int) or isinstance(k, bool) or k < 0:
             raise ValueError("learner_steps_per_actor_step must be an int >= 0")
+        if cfg.ingest not in INGEST_MODES:
+            raise ValueError(f"ingest must be one of {INGEST_MODES}, got {cfg.ingest!r}")
+        staging = getattr(vec, "staging", None)
+        if cfg.ingest == "banked" and (staging is None or not has_banks(vec)):
+            raise ValueError("ingest='banked' needs a vector env with staging, banks, step_async and wait_bank")
         self.cfg = cfg
         self.vec = vec
         self.device = torch.device(device)
@@ -272,7 +389,9 @@ class HostEnvEngine:
         self.replay = HBMReplay(cfg.replay_capacity, E, lc.n_step, cfg.alpha, self.device, exact_mass=cfg.exact_mass,
                                 seed=cfg.seed)
         self.actor = HostEnvShard(self.replay, E, A, vec.raw_shape, lc.n_step, lc.gamma, cfg.eps_base, cfg.eps_alpha,
-                                  cfg.actor_offset, cfg.total_actors, cfg.seed, cfg.nstep_mode, cfg.clip_rewards)
+                                  cfg.actor_offset, cfg.total_actors, cfg.seed, cfg.nstep_mode, cfg.clip_rewards,
+                                  staging=staging, ingest=cfg.ingest)
+        self.ingest = "banked" if self.actor._banked(vec) else "whole"   # what "auto" resolved to
         model = model if model is not None else DuelingDQN.from_shapes((4, 84, 84), A)
         self.learner = DQNLearner(model, self.replay, lc)
         self.actor_model = copy.deepcopy(self.learner.model)
@@ -401,3 +520,11 @@ class HostEnvEngine:
     def save(self, path: str) -> str:
         """``torch.save(state_dict)`` with the reference keys (utils/checkpoint.py)."""
         return save_model(self.learner.model, path)
+
+    def close(self) -> None:
+        """Finish the queued work, release the staging block and close a vector env that has a
+        ``close`` (a worker pool: its processes stop, its shared block is unlinked).  Idempotent."""
+        self.actor.close()
+        close = getattr(self.vec, "close", None)
+        if close is not None:
+            close()

@@ -18,8 +18,10 @@ Differences from ``AtariPreprocess``:
 * ``step`` returns ``(reward [N] float64, done [N] bool)``; the reward is the raw, unclipped
   sum over the repeat window (clipping is the consumer's business).
 
-The vector-env protocol the engine relies on -- a process-pool implementation only has to
-provide the same five members:
+The vector-env protocol the engine relies on.  :class:`apex_amd.envs.proc_vector.ProcRawAtariVector`
+provides the same five members over worker processes (one ``RawAtariVector`` per worker), plus a
+shared ``staging`` block and a banked ``step_async`` / ``wait_bank`` form the engine uses when it
+finds them:
 
 ``__len__()``              number of envs
 ``raw_shape``              ``(H, W, 3)`` of one emulator frame

@@ -1155,4 +1155,14 @@ PYBIND11_MODULE(_apex_hip, m) {
   }, py::arg("raw"), py::arg("reward_in"), py::arg("done_in"), py::arg("rows"), py::arg("cols"), py::arg("frames"),
      py::arg("params"), py::arg("step"), py::arg("reset"), py::arg("reward"), py::arg("done"), py::arg("new_frame"),
      py::arg("hist"), py::arg("acc"), py::arg("ep_log"), py::arg("s"));
+  m.def("host_env_ingest_range", [](uint64_t raw, uint64_t reward_in, uint64_t done_in, const HostEnvTaps& rows,
+                                    const HostEnvTaps& cols, uint64_t frames, const HostEnvParams& p, uint64_t step,
+                                    bool reset, uint64_t reward, uint64_t done, uint64_t new_frame, uint64_t hist,
+                                    uint64_t acc, uint64_t ep_log, int e0, int n, uint64_t s) {
+    host_env_ingest_range(P<const uint8_t>(raw), P<const float>(reward_in), P<const float>(done_in), rows, cols,
+                          P<uint8_t>(frames), p, P<const int64_t>(step), reset, P<float>(reward), P<float>(done),
+                          P<int>(new_frame), P<int>(hist), P<float>(acc), P<float>(ep_log), e0, n, S(s));
+  }, py::arg("raw"), py::arg("reward_in"), py::arg("done_in"), py::arg("rows"), py::arg("cols"), py::arg("frames"),
+     py::arg("params"), py::arg("step"), py::arg("reset"), py::arg("reward"), py::arg("done"), py::arg("new_frame"),
+     py::arg("hist"), py::arg("acc"), py::arg("ep_log"), py::arg("e0"), py::arg("n"), py::arg("s"));
 }

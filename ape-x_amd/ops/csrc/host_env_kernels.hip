@@ -8,7 +8,10 @@
 // vec_env_step_k would have used, with the same reward / done / new_frame / ep_log outputs:
 // everything downstream (conv1 on the ring, nstep_emit, the tree, the learner) is shared.
 //
-// Grid (E, 84 / kBand): one workgroup warps kBand = 4 output rows h of one env.  It stages the
+// Grid (n, 84 / kBand) over the env range [e0, e0 + n): one workgroup warps kBand = 4 output rows h
+// of env e0 + blockIdx.x.  Slots, raw addressing, the bounds guard and the bookkeeping rows all use
+// the absolute env index over the whole shard's buffers, so a range launch writes exactly what the
+// whole launch (e0 = 0, n = E) writes for those envs and nothing else.  The workgroup stages the
 // input rows those need (two frames) into LDS with aligned 32-bit loads -- the band is one
 // contiguous byte range per frame -- runs the row pass over the band (grey formed on the
 // fly), then the column pass, and stores the 4 bytes of each output column w as one word:
@@ -33,10 +36,10 @@ inline int region_words(int H, int W) { return (band_rows(H) * W * 3 + 3 + 3) / 
 __global__ __launch_bounds__(256) void host_env_ingest_k(
     const uint8_t* __restrict__ raw, const float* __restrict__ reward_in, const float* __restrict__ done_in,
     HostEnvTaps rows, HostEnvTaps cols, uint8_t* __restrict__ frames, HostEnvParams p,
-    const int64_t* __restrict__ step_counter, int reset, int band, int reg_words, float* reward, float* done,
-    int* new_frame, int* hist, float* acc, float* ep_log) {
+    const int64_t* __restrict__ step_counter, int reset, int band, int reg_words, int e0, float* reward,
+    float* done, int* new_frame, int* hist, float* acc, float* ep_log) {
   extern __shared__ __align__(16) unsigned char smem[];
-  const int e = blockIdx.x, h0 = blockIdx.y * kBand, tid = threadIdx.x;
+  const int e = e0 + blockIdx.x, h0 = blockIdx.y * kBand, tid = threadIdx.x;
   const int H = p.H, W = p.W;
   const int64_t step = step_counter[0];
   const int slot = (int)(((step + (reset ? 0 : 1)) * (int64_t)p.E + e) % p.F);
@@ -145,24 +148,35 @@ __global__ __launch_bounds__(256) void host_env_ingest_k(
   }
 }
 
-void host_env_ingest(const uint8_t* raw, const float* reward_in, const float* done_in, const HostEnvTaps& rows,
-                     const HostEnvTaps& cols, uint8_t* frames, const HostEnvParams& p, const int64_t* step_counter,
-                     bool reset, float* reward, float* done, int* new_frame, int* hist, float* acc, float* ep_log,
-                     hipStream_t s) {
+void host_env_ingest_range(const uint8_t* raw, const float* reward_in, const float* done_in, const HostEnvTaps& rows,
+                           const HostEnvTaps& cols, uint8_t* frames, const HostEnvParams& p,
+                           const int64_t* step_counter, bool reset, float* reward, float* done, int* new_frame,
+                           int* hist, float* acc, float* ep_log, int e0, int n, hipStream_t s) {
   if (p.H < kOut || p.W < kOut) throw std::invalid_argument("host_env_ingest: the warp only shrinks (H, W >= 84)");
   if (rows.max_count > kTaps || cols.max_count > kTaps || rows.max_count < 1 || cols.max_count < 1)
     throw std::invalid_argument("host_env_ingest: tap count above the table width (" + std::to_string(kTaps) + ")");
   if (p.E <= 0 || p.F <= 0 || p.frame_bytes < kOut * kOut || p.frame_bytes % 4)
     throw std::invalid_argument("host_env_ingest: bad E / F / frame_bytes");
+  if (e0 < 0 || n < 1 || (int64_t)e0 + n > p.E)
+    throw std::invalid_argument("host_env_ingest: env range [" + std::to_string(e0) + ", " +
+                                std::to_string((int64_t)e0 + n) + ") outside [0, " + std::to_string(p.E) + ")");
   if ((reinterpret_cast<uintptr_t>(raw) | reinterpret_cast<uintptr_t>(frames)) & 3)
     throw std::invalid_argument("host_env_ingest: raw and frames must be 4-byte aligned");
   const int band = band_rows(p.H), rw = region_words(p.H, p.W);
   const size_t lds = (size_t)((2 * rw + 1) / 2) * 8 + (size_t)kBand * p.W * 8 + kOut * kBand;
   if (lds > (size_t)kMaxLds) throw std::invalid_argument("host_env_ingest: frame too large for the LDS stage");
-  host_env_ingest_k<<<dim3(p.E, kOut / kBand), 256, lds, s>>>(raw, reward_in, done_in, rows, cols, frames, p,
-                                                              step_counter, reset ? 1 : 0, band, rw, reward, done,
-                                                              new_frame, hist, acc, ep_log);
+  host_env_ingest_k<<<dim3(n, kOut / kBand), 256, lds, s>>>(raw, reward_in, done_in, rows, cols, frames, p,
+                                                            step_counter, reset ? 1 : 0, band, rw, e0, reward, done,
+                                                            new_frame, hist, acc, ep_log);
   LAUNCH_CHECK();
+}
+
+void host_env_ingest(const uint8_t* raw, const float* reward_in, const float* done_in, const HostEnvTaps& rows,
+                     const HostEnvTaps& cols, uint8_t* frames, const HostEnvParams& p, const int64_t* step_counter,
+                     bool reset, float* reward, float* done, int* new_frame, int* hist, float* acc, float* ep_log,
+                     hipStream_t s) {
+  host_env_ingest_range(raw, reward_in, done_in, rows, cols, frames, p, step_counter, reset, reward, done, new_frame,
+                        hist, acc, ep_log, 0, p.E, s);
 }
 
 }  // namespace apex

@@ -93,8 +93,17 @@ void register_ipc(py::module_& m) {
     if (n <= 0) return;
     hip_ok(hipMemcpy(P<void>(dst), P<const void>(src), (size_t)n, hipMemcpyDefault), "hipMemcpy");
   });
+  // host -> device, stream-ordered: the source is pinned or registered host memory (the host-env
+  // engine's shared staging block), so the copy is a DMA that does not block the caller
+  m.def("memcpy_h2d_async", [](uint64_t dst, uint64_t src, int64_t nbytes, uint64_t stream) {
+    if (nbytes < 0 || ((!dst || !src) && nbytes)) throw std::invalid_argument("memcpy_h2d_async: bad pointer or size");
+    if (nbytes == 0) return;
+    hip_ok(hipMemcpyAsync(P<void>(dst), P<const void>(src), (size_t)nbytes, hipMemcpyHostToDevice, S(stream)),
+           "hipMemcpyAsync(H2D)");
+  }, py::arg("dst"), py::arg("src"), py::arg("nbytes"), py::arg("stream"));
   // pin + map a host range (a /dev/shm control block) for GPU access; returns the device pointer
   m.def("host_register", [](uint64_t host, int64_t bytes) {
+    if (!host || bytes <= 0) throw std::invalid_argument("host_register: needs a pointer and bytes > 0");
     hip_ok(hipHostRegister(P<void>(host), (size_t)bytes, hipHostRegisterMapped | hipHostRegisterPortable),
            "hipHostRegister");
     void* d = nullptr;

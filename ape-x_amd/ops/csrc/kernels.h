@@ -940,6 +940,14 @@ void host_env_ingest(const uint8_t* raw, const float* reward_in, const float* do
                      const HostEnvTaps& cols, uint8_t* frames, const HostEnvParams& p, const int64_t* step_counter,
                      bool reset, float* reward, float* done, int* new_frame, int* hist, float* acc, float* ep_log,
                      hipStream_t s);
+// The same launch over the env range [e0, e0 + n) of the shard's buffers (all pointers are the whole
+// shard's; slots and rows keep their absolute env index): what host_env_ingest writes for those envs
+// and nothing else.  host_env_ingest is the range (0, E).  Throws std::invalid_argument for e0 < 0,
+// n < 1 or e0 + n > E before any launch.
+void host_env_ingest_range(const uint8_t* raw, const float* reward_in, const float* done_in, const HostEnvTaps& rows,
+                           const HostEnvTaps& cols, uint8_t* frames, const HostEnvParams& p,
+                           const int64_t* step_counter, bool reset, float* reward, float* done, int* new_frame,
+                           int* hist, float* acc, float* ep_log, int e0, int n, hipStream_t s);
 
 // ---- central-replay experience transport over HIP IPC (ipc_kernels.hip, parallel/ipc.py)
 struct IpcIngest {

@@ -9,9 +9,14 @@ into the HBM frame ring, and the replay, n-step batcher and fused learner are th
 engine's (``engine.host_env.HostEnvEngine``).  ``apex_amd.train`` remains the CLI of the
 GPU-resident envs.
 
+``--workers W`` steps the emulators in ``W`` worker processes (``envs.proc_vector.ProcRawAtariVector``:
+shared-memory staging that the GPU copies out of in place, per-worker ingest with ``--ingest
+banked``); the default 0 is the in-process vector.  Both compute the same run, bit for bit.
+
 Flags: the reference's (``--env``, ``--episode_life``, ``--clip_rewards``, ``--replay_buffer_size``,
 ``--threshold_size``, ``--batch_size``, intervals, ...) plus ``--envs``, ``--learner-steps`` (learner
-steps enqueued per env step), ``--max-step`` (learner steps, 0 = forever), ``--save-path``,
+steps enqueued per env step), ``--workers``, ``--worker-timeout`` (seconds a worker may stay silent),
+``--ingest {auto,whole,banked}``, ``--max-step`` (learner steps, 0 = forever), ``--save-path``,
 ``--resume`` (model + ``.train.pt`` sidecar, as ``apex_amd.train``) and ``--log-dir``.  Logged every
 ``--bps_interval`` learner steps: ``learner/loss``, ``learner/grad_norm``, ``learner/BPS``,
 ``actor/episode_reward`` (clipped return), ``actor/episode_length``, ``actor/episode_score``
@@ -22,8 +27,6 @@ from __future__ import annotations
 import sys
 import time
 
-import torch
-
 from .config import args_to_config, build_parser, preset
 
 
@@ -31,6 +34,12 @@ def parser():
     p = build_parser(preset("origin"), description="Ape-X DQN on MI355X over host gym-API Atari envs")
     p.add_argument("--envs", type=int, default=16, help="host emulators stepped per actor step")
     p.add_argument("--learner-steps", type=int, default=1, help="learner steps enqueued per env step (k >= 0)")
+    p.add_argument("--workers", type=int, default=0,
+                   help="emulator worker processes (0 = step the envs in this process)")
+    p.add_argument("--worker-timeout", type=float, default=60.0,
+                   help="seconds a worker may take for one step before the run is aborted")
+    p.add_argument("--ingest", choices=["auto", "whole", "banked"], default="auto",
+                   help="with --workers: ingest each worker's envs as they finish (banked) or all at once (whole)")
     p.add_argument("--save-path", default="model.pth")
     p.add_argument("--resume", default=None, help="model.pth (+ .train.pt sidecar) to resume from")
     p.add_argument("--log-dir", default=None, help="event-file directory (default runs/<time>-<env>-host)")
@@ -39,24 +48,46 @@ def parser():
 
 
 def main(argv=None) -> int:
+    import torch   # (not at module level: a worker process re-imports the main module, and stays torch-free)
+
     args = parser().parse_args(argv)
+    if args.workers < 0:
+        raise SystemExit("--workers must be >= 0")
     cfg = args_to_config(args)
     if not torch.cuda.is_available():
         raise SystemExit("apex_amd.train_host runs the GPU engine; use apex_amd.roles.* on CPU")
     device = torch.device("cuda", 0)
     torch.cuda.set_device(device)
 
-    from .engine.host_env import HostEnvConfig, HostEnvEngine
-    from .engine.learner import LearnerConfig
     from .envs.core import make
     from .envs.preprocess import PreprocessSpec
     from .envs.raw_vector import RawAtariVector
+
+    spec = PreprocessSpec.from_args(cfg.env)
+    if args.workers:
+        from .envs.proc_vector import ProcRawAtariVector
+
+        vec = ProcRawAtariVector(cfg.env.env, args.envs, spec, workers=args.workers, seed=cfg.seed,
+                                 timeout=args.worker_timeout)
+    else:
+        vec = RawAtariVector([make(cfg.env.env) for _ in range(args.envs)], spec)
+        vec.seed(cfg.seed)
+    try:
+        return _train(args, cfg, vec, spec, device)
+    finally:   # every exit path, exceptions included: stop the workers, unlink their shared block
+        close = getattr(vec, "close", None)
+        if close is not None:
+            close()
+
+
+def _train(args, cfg, vec, spec, device) -> int:
+    import torch
+
+    from .engine.host_env import HostEnvConfig, HostEnvEngine
+    from .engine.learner import LearnerConfig
     from .train import load_engine, save_engine
 
     L, R = cfg.learner, cfg.replay
-    spec = PreprocessSpec.from_args(cfg.env)
-    vec = RawAtariVector([make(cfg.env.env) for _ in range(args.envs)], spec)
-    vec.seed(cfg.seed)
     lc = LearnerConfig(batch_size=R.batch_size, n_step=cfg.n_steps, gamma=cfg.gamma, lr=L.lr, rms_alpha=L.rms_alpha,
                        rms_eps=L.rms_eps, centered=L.centered, max_norm=L.max_norm, lr_gamma=L.lr_gamma,
                        lr_step_size=L.lr_step_size, beta=R.beta, optimizer=L.optimizer, forward=cfg.kernel.forward,
@@ -67,15 +98,29 @@ def main(argv=None) -> int:
                          target_update_interval=L.target_update_interval, nstep_mode=cfg.actor.nstep_mode,
                          eps_base=cfg.actor.eps_base, eps_alpha=cfg.actor.eps_alpha,
                          clip_rewards=bool(cfg.env.clip_rewards), action_repeat=spec.skip,
-                         use_graphs=cfg.kernel.use_graphs, exact_mass=R.exact_mass, seed=cfg.seed, learner=lc)
+                         use_graphs=cfg.kernel.use_graphs, exact_mass=R.exact_mass, seed=cfg.seed,
+                         ingest=args.ingest if args.workers else "auto", learner=lc)
     eng = HostEnvEngine(ecfg, vec, device)
+    try:
+        return _loop(args, cfg, eng, device)
+    finally:
+        eng.close()   # unregisters the shared staging block, then closes the pool that owns it
+
+
+def _loop(args, cfg, eng, device) -> int:
+    import torch
+
+    from .train import load_engine, save_engine
+
+    L, vec = cfg.learner, eng.vec
     counters = {}
     if args.resume:
         counters = load_engine(eng.learner, args.resume)
         eng.publish_params()
     start = int(counters.get("learn_steps", 0))
     eng.learn_steps = start
-    print(f"{cfg.env.env}: {len(vec)} host envs, {vec.n_actions} actions, raw {vec.raw_shape}; "
+    where = f" in {args.workers} worker processes ({eng.ingest} ingest)" if args.workers else ""
+    print(f"{cfg.env.env}: {len(vec)} host envs{where}, {vec.n_actions} actions, raw {vec.raw_shape}; "
           f"training from step {start}", flush=True)
 
     writer = None

@@ -12,6 +12,9 @@
 ``--mode learn``    one learning run: ``--steps`` iterations, the actors' clipped return and unclipped
                     score over the run's last finished episodes against a random policy's
                     (``--k 0`` run of the same length, same seeds).
+
+``--workers W`` (modes host, engine, learn) steps the emulators in ``W`` worker processes
+(``ProcRawAtariVector``) and ``--ingest`` picks banked or whole ingest; 0 is the in-process vector.
 """
 import argparse
 import json
@@ -27,6 +30,10 @@ def _vec(a, raw=True):
     from apex_amd.envs.preprocess import AtariPreprocess, PreprocessSpec
     from apex_amd.envs.raw_vector import RawAtariVector
 
+    if raw and a.workers:
+        from apex_amd.envs.proc_vector import ProcRawAtariVector
+
+        return ProcRawAtariVector(a.env, a.envs, PreprocessSpec(), workers=a.workers, seed=a.seed)
     cls = RawAtariVector if raw else AtariPreprocess
     v = cls([make(a.env) for _ in range(a.envs)], PreprocessSpec())
     v.seed(a.seed)
@@ -41,7 +48,8 @@ def mode_host(a):
         v = _vec(a, raw)
         rng = np.random.default_rng(0)
         n_act = v.action_space.n
-        buf = np.zeros((a.envs, 2) + tuple(v.envs[0].observation_space.shape), np.uint8)
+        buf = v.staging if raw and a.workers else np.zeros((a.envs, 2) + tuple(v.envs[0].observation_space.shape),
+                                                           np.uint8)
         v.reset(buf) if raw else v.reset()
         acts = [rng.integers(0, n_act, a.envs) for _ in range(a.warmup + a.steps)]
         for t in range(a.warmup + a.steps):
@@ -55,6 +63,9 @@ def mode_host(a):
                     v.reset_one(int(i))
         dt = time.perf_counter() - t0
         out[name] = {"env_steps_per_s": a.steps * a.envs / dt, "ms_per_env_step": 1e3 * dt / (a.steps * a.envs)}
+        if hasattr(v, "close"):
+            v.close()
+    out["workers"] = a.workers
     out["raw_over_preprocess"] = out["raw_vector"]["env_steps_per_s"] / out["atari_preprocess"]["env_steps_per_s"]
     return out
 
@@ -97,7 +108,7 @@ def _engine(a, k, vec=None):
     from apex_amd.engine.learner import LearnerConfig
 
     cfg = HostEnvConfig(replay_capacity=a.capacity, threshold_size=a.threshold, learner_steps_per_actor_step=k,
-                        seed=a.seed, target_update_interval=a.target_interval,
+                        seed=a.seed, target_update_interval=a.target_interval, ingest=a.ingest,
                         learner=LearnerConfig(batch_size=a.batch, forward="hip", lr=a.lr, seed=a.seed))
     return HostEnvEngine(cfg, vec if vec is not None else _vec(a), "cuda:0")
 
@@ -109,9 +120,12 @@ def mode_engine(a):
         eng.iteration()
     l0 = eng.learn_steps
     dt = eng.run(a.steps)
-    return {"envs": a.envs, "k": a.k, "batch": a.batch, "iterations_per_s": a.steps / dt,
-            "env_steps_per_s": a.steps * a.envs / dt, "frames_per_s": a.steps * eng.frames_per_actor_step / dt,
-            "learner_steps_per_s": (eng.learn_steps - l0) / dt, "graph": eng._g_learn is not None}
+    res = {"envs": a.envs, "k": a.k, "batch": a.batch, "workers": a.workers, "ingest": eng.ingest,
+           "iterations_per_s": a.steps / dt,
+           "env_steps_per_s": a.steps * a.envs / dt, "frames_per_s": a.steps * eng.frames_per_actor_step / dt,
+           "learner_steps_per_s": (eng.learn_steps - l0) / dt, "graph": eng._g_learn is not None}
+    eng.close()
+    return res
 
 
 def mode_learner(a):
@@ -134,6 +148,7 @@ def mode_learner(a):
 
 def mode_learn(a):
     out = {"envs": a.envs, "iterations": a.steps, "batch": a.batch, "lr": a.lr, "threshold": a.threshold,
+           "workers": a.workers, "ingest": a.ingest,
            "target_interval": a.target_interval, "env": a.env}
     for name, k in (("random_policy", 0), ("learning", a.k)):
         eng = _engine(a, k)
@@ -150,6 +165,7 @@ def mode_learn(a):
                      "episodes": st["episodes"], "episode_reward_last": st.get("episode_reward"),
                      "episode_score_last": st.get("episode_score"), "episode_length_last": st.get("episode_length"),
                      "episode_reward_halfway": half.get("episode_reward"), "loss": st.get("loss")}
+        eng.close()
     return out
 
 
@@ -161,6 +177,8 @@ def main():
     ap.add_argument("--height", type=int, default=210)
     ap.add_argument("--width", type=int, default=160)
     ap.add_argument("--k", type=int, default=1)
+    ap.add_argument("--workers", type=int, default=0, help="emulator worker processes (0 = in process)")
+    ap.add_argument("--ingest", choices=["auto", "whole", "banked"], default="auto")
     ap.add_argument("--batch", type=int, default=512)
     ap.add_argument("--capacity", type=int, default=65536)
     ap.add_argument("--threshold", type=int, default=2048)
