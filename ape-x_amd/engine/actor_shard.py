@@ -18,56 +18,24 @@ from __future__ import annotations
 
 import torch
 
-from .. import ops
-from ..algo.schedules import actor_epsilon
 from .hbm_replay import HBMReplay
+from .shard import NStepShard
 
 ENV_STATE_STRIDE = 32
 
 
-class ActorShard:
+class ActorShard(NStepShard):
     def __init__(self, replay: HBMReplay, n_envs: int, n_actions: int, n_step: int = 3, gamma: float = 0.99,
                  eps_base: float = 0.4, eps_alpha: float = 7.0, actor_offset: int = 0, total_actors: int | None = None,
                  seed: int = 0, mode: str = "reference", clip_rewards: bool = True, episode_life: bool = True,
                  max_episode_steps: int = 50000, action_repeat: int = 4, staged: int = 0):
-        self.hip = ops.hip()
-        self.replay = replay
-        self.E, self.A, self.n = int(n_envs), int(n_actions), int(n_step)
-        assert replay.n_envs == self.E, "replay slot layout is sized for this shard's env count"
-        dev = replay.device
-        self.device = dev
-        self.seed = int(seed)
-        E, A, n = self.E, self.A, self.n
-        total = total_actors if total_actors is not None else E
-        ids = torch.arange(actor_offset, actor_offset + E, dtype=torch.float64)
-        self.eps = torch.as_tensor(actor_epsilon(ids.numpy(), total, eps_base, eps_alpha), dtype=torch.float32,
-                                   device=dev)
+        super().__init__(replay, n_envs, n_actions, n_step, gamma, eps_base, eps_alpha, actor_offset, total_actors,
+                         seed, mode)
+        E, A, dev = self.E, self.A, self.device
         i32 = dict(dtype=torch.int32, device=dev)
         f32 = dict(dtype=torch.float32, device=dev)
         self.env_state = torch.zeros(E, ENV_STATE_STRIDE, **f32)
-        self.new_frame = torch.zeros(E, **i32)
-        self.ep_log = torch.zeros(E, 4, **f32)
-        self.q = torch.zeros(E, A, **f32)
-        self.actions = torch.zeros(E, **i32)
-        self.reward = torch.zeros(E, **f32)
-        self.done = torch.zeros(E, **f32)
-        self.slot = torch.zeros(E, **i32)
-        self.prio = torch.zeros(E, **f32)
         self.obs = torch.zeros(E, 4, 84, 84, dtype=torch.uint8, device=dev)
-        self.step_counter = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.st = {
-            "win_ids": torch.zeros(E, n, 4, **i32), "win_a": torch.zeros(E, n, **i32),
-            "win_r": torch.zeros(E, n, **f32), "win_q": torch.zeros(E, n, A, **f32),
-            "win_meta": torch.zeros(E, 4, **i32), "hist": torch.zeros(E, 4, **i32),
-            "drain_ids": torch.zeros(E, n, 4, **i32), "drain_a": torch.zeros(E, n, **i32),
-            "drain_r": torch.zeros(E, n, **f32), "drain_q": torch.zeros(E, n, **f32),
-            "drain_meta": torch.zeros(E, 2, **i32), "drain_s2": torch.zeros(E, 4, **i32),
-        }
-        if mode not in ("reference", "textbook"):
-            raise ValueError("mode must be 'reference' or 'textbook'")
-        st_ptrs = {k: v.data_ptr() for k, v in self.st.items()}
-        nmode = 0 if mode == "reference" else 1
-        self.nstep = self.hip.make_nstep(E, A, n, replay.capacity, float(gamma), nmode, st_ptrs, replay.trans_ptrs())
         # staged mode (overlapped actor/learner streams): ``staged`` sets of [E] rows +
         # slots + priorities; the learner stream applies one half while the actor fills
         # the other
@@ -77,17 +45,12 @@ class ActorShard:
                            "action": torch.zeros(E, **i32), "reward": torch.zeros(E, **f32),
                            "done": torch.zeros(E, **f32)} for _ in range(self.staged)]
             self.stage_ptrs = [{k: v.data_ptr() for k, v in t.items()} for t in self.stage]
-            self.stage_nstep = [self.hip.make_nstep(E, A, n, replay.capacity, float(gamma), nmode, st_ptrs, sp,
-                                                    stage=1) for sp in self.stage_ptrs]
+            self.stage_nstep = [self.make_nstep(gamma, mode, sp, stage=1) for sp in self.stage_ptrs]
             self.stage_slot = [torch.zeros(E, **i32) for _ in range(self.staged)]
             self.stage_prio = [torch.zeros(E, **f32) for _ in range(self.staged)]
         self.env_params = self.hip.VecEnvParams(E, A, replay.frame_bytes, replay.frame_capacity, action_repeat,
                                                 int(clip_rewards), int(episode_life), int(max_episode_steps))
         self.reset()
-
-    @staticmethod
-    def _stream() -> int:
-        return torch.cuda.current_stream().cuda_stream
 
     def reset(self) -> None:
         self.hip.vec_env_reset(self.env_state.data_ptr(), self.seed, self.replay.frames.data_ptr(), self.env_params,
@@ -99,40 +62,27 @@ class ActorShard:
         self.replay.gather_frames(self.st["hist"], self.obs)
         return self.obs
 
-    def act_args(self) -> tuple:
-        """(eps, rng seed, step counter, actions) pointers for an inference kernel that
-        picks the actions itself (``heads_fwd_multi``'s eps-greedy epilogue: the same
-        draw as ``select_actions``); then call :meth:`act_and_step` with ``selected=True``."""
-        return (self.eps.data_ptr(), self.seed ^ 0x5E1EC7, self.step_counter.data_ptr(), self.actions.data_ptr())
-
     def act_and_step(self, q: torch.Tensor | None = None, parity: int | None = None, selected: bool = False,
                      tree: bool = True) -> None:
         """Given Q for the current observations (in ``self.q`` or ``q``), act, step the
         envs and push the emitted transitions into the replay (staged mode: into staging
         set ``parity``; :meth:`apply_staged` moves them into the replay).  ``selected``:
-        ``self.actions`` already holds this step's eps-greedy actions (see :meth:`act_args`).
-        ``tree=False``: rows only, no priority-tree write (a central actor rank's local mirror:
-        the priorities travel in its packet to rank 0's tree)."""
+        ``self.actions`` already holds this step's eps-greedy actions (picked by the forward
+        given :meth:`act_args`).  ``tree=False``: rows only, no priority-tree write (a central
+        actor rank's local mirror: the priorities travel in its packet to rank 0's tree)."""
         if q is not None and q.data_ptr() != self.q.data_ptr():
             self.q.copy_(q)
-        s = self._stream()
-        h = self.hip
-        E, A = self.E, self.A
         if not selected:
-            h.select_actions(self.q.data_ptr(), E, A, self.eps.data_ptr(), self.seed ^ 0x5E1EC7,
-                             self.step_counter.data_ptr(), self.actions.data_ptr(), s)
-        h.vec_env_step(self.env_state.data_ptr(), self.actions.data_ptr(), self.seed, self.step_counter.data_ptr(),
-                       self.replay.frames.data_ptr(), self.env_params, self.reward.data_ptr(), self.done.data_ptr(),
-                       self.new_frame.data_ptr(), self.ep_log.data_ptr(), s)
+            self.select()
+        self.hip.vec_env_step(self.env_state.data_ptr(), self.actions.data_ptr(), self.seed,
+                              self.step_counter.data_ptr(), self.replay.frames.data_ptr(), self.env_params,
+                              self.reward.data_ptr(), self.done.data_ptr(), self.new_frame.data_ptr(),
+                              self.ep_log.data_ptr(), self._stream())
         if parity is not None:
             assert 0 <= parity < self.staged, "staging set out of range"
-            h.nstep_emit(self.stage_nstep[parity], self.q.data_ptr(), self.actions.data_ptr(), self.reward.data_ptr(),
-                         self.done.data_ptr(), self.new_frame.data_ptr(), self.step_counter.data_ptr(),
-                         self.stage_slot[parity].data_ptr(), self.stage_prio[parity].data_ptr(), s, True)
+            self._emit(self.stage_nstep[parity], self.stage_slot[parity], self.stage_prio[parity], True)
             return  # the kernel advanced step_counter
-        h.nstep_emit(self.nstep, self.q.data_ptr(), self.actions.data_ptr(), self.reward.data_ptr(),
-                     self.done.data_ptr(), self.new_frame.data_ptr(), self.step_counter.data_ptr(),
-                     self.slot.data_ptr(), self.prio.data_ptr(), s, not tree)  # (no tree: the kernel bumps)
+        self._emit(self.nstep, self.slot, self.prio, not tree)  # (no tree: the kernel bumps)
         if tree:
             self.replay.write_batch(pre=(self.slot, self.prio, self.replay.filled), bump=self.step_counter)
 
@@ -164,7 +114,3 @@ class ActorShard:
         obs = self.observe()
         q = policy(obs)
         self.act_and_step(q)
-
-    def episode_stats(self) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        """(last episode return, last episode length, finished episode count) per env."""
-        return self.ep_log[:, 0], self.ep_log[:, 1], self.ep_log[:, 2]

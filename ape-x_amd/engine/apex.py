@@ -31,11 +31,11 @@ import torch
 from .. import ops
 from ..models.dqn import DuelingDQN
 from ..utils import trace
-from ..models.fused import make_hip_net, make_workspace
 from .actor_shard import ActorShard
+from .graphs import capture_graph, warm_up
 from .hbm_replay import HBMReplay
-from .learner import DQNLearner, LearnerConfig, forward_q
-
+from .learner import DQNLearner, LearnerConfig
+from .shard import ActorPolicy
 
 
 @dataclass
@@ -108,18 +108,10 @@ class ApexEngine:
 
             self._sharded = ShardedSampling(self.replay, force=force_collectives, comm=allreduce)
         self.learner = DQNLearner(model, self.replay, lc, allreduce=allreduce, sharded=self._sharded)
-        self.actor_model = copy.deepcopy(self.learner.model)
-        self.actor_model._flat = None
-        self.actor_flat = self.actor_model.flatten_parameters()
-        for p in self.actor_model.parameters():
-            p.requires_grad_(False)
-            p.grad = None
-        self.hip_net = lc.forward == "hip"
-        if self.hip_net:
-            # actors act at the learner's precision (the reference's actors are fp32 too)
-            self.actor_net = make_hip_net(self.actor_model, lc.dtype)
-            self.actor_ws = make_workspace(cfg.n_envs, cfg.n_actions, self.device, lc.dtype)
-            self.actor_ws.q = self.actor.q  # the heads kernel writes the actor's Q in place (no copy)
+        p = self.policy = ActorPolicy(copy.deepcopy(self.learner.model), cfg.n_envs, cfg.n_actions, self.device,
+                                      lc.forward, lc.dtype, self.actor.q)
+        self.actor_model, self.actor_flat, self.hip_net = p.model, p.flat, p.hip_net
+        self.actor_net, self.actor_ws = p.net, p.ws   # (None without the HIP forward)
         self.publish_params()
         self.learn_steps = 0
         self.actor_steps = 0
@@ -148,21 +140,12 @@ class ApexEngine:
     def publish_params(self) -> None:
         """Learner -> local actor weights (the on-GPU analogue of learner.py:169-170)."""
         trace.mark("apex.publish_params")
-        self.learner.copy_params_to(self.actor_flat)
-        if self.hip_net:
-            self.actor_net.copy_packed_from(self.learner.net)
+        self.policy.publish_from(self.learner)
 
     def _actor_body(self, stage: int | None = None):
-        if self.hip_net:  # conv1 reads the current stacks straight from the frame ring; the
-            # heads kernel writes Q into the actor's buffer and picks the eps-greedy actions
-            self.actor_net(self.replay.frames, self.actor_ws, self.actor.st["hist"], act=self.actor.act_args())
-            self.actor.act_and_step(None, stage, selected=True)
-            return
-        else:
-            obs = self.actor.observe()
-            with torch.no_grad():
-                q = forward_q(self.actor_model, obs, self.cfg.learner.dtype == "bf16")
-        self.actor.act_and_step(q, stage)
+        q = self.policy.forward(self.replay, self.actor)
+        # (q None: the HIP forward's heads kernel wrote Q in place and picked the actions)
+        self.actor.act_and_step(q, stage, selected=q is None)
 
     def _actor_half(self, half: int):
         """Actor steps into staging half ``half``."""
@@ -260,16 +243,6 @@ class ApexEngine:
         self._mass_pending = False
 
     # ------------------------------------------------------------------ graphs
-    @staticmethod
-    def _graph(fn, pool):
-        # thread_local capture: the process group's watchdog thread polls RCCL work events
-        # while we capture; in the default (global) mode that call invalidates the capture
-        # ("operation not permitted when stream is capturing", seen with --force-dp)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, pool=pool, capture_error_mode="thread_local"):
-            fn()
-        return g
-
     def capture(self, warmup_iters: int = 3, warm_replays: int = 0) -> None:
         """Warm up on a side stream, then capture actor and learner steps as hipGraphs.
         The warm-up iterations are real train steps and are counted as such.  Collectives
@@ -279,25 +252,20 @@ class ApexEngine:
         slower than steady state (clock / power ramp, scripts/diag/warmup_curve.py), so a
         caller that times a short window right after setup starts from the sustained state."""
         self._drain_mass()
-        s = torch.cuda.Stream(device=self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):
-            for _ in range(warmup_iters):  # full eager train steps (counters, publish/target cadence)
-                self.train_step()
-        torch.cuda.current_stream(self.device).wait_stream(s)
+        warm_up(self.device, self.train_step, warmup_iters)  # full eager train steps (counters, publish/target cadence)
         torch.cuda.synchronize(self.device)
         self._pool = torch.cuda.graph_pool_handle()
         if self.overlap:
             self._capture_overlap_graphs(torch.cuda.graph_pool_handle())  # actor graphs run concurrently:
         else:                                                           # never share their memory
             L = self.learner
-            self._g_actor = self._graph(self._actor_body, self._pool)
+            self._g_actor = capture_graph(self._actor_body, self._pool)
             if self._dp:
-                self._g_learn_a = self._graph(L.forward_phase, self._pool)
-                self._g_learn_a2 = self._graph(L.backward_phase, self._pool)
-                self._g_learn_b = self._graph(self._learn_b, self._pool)
+                self._g_learn_a = capture_graph(L.forward_phase, self._pool)
+                self._g_learn_a2 = capture_graph(L.backward_phase, self._pool)
+                self._g_learn_b = capture_graph(self._learn_b, self._pool)
             else:  # no host collective in between: one graph per step
-                self._g_learn_a = self._graph(lambda: (L.forward_phase(), self._learn_b()), self._pool)
+                self._g_learn_a = capture_graph(lambda: (L.forward_phase(), self._learn_b()), self._pool)
         self._captured = True
         torch.cuda.synchronize(self.device)
         if self.overlap:
@@ -317,8 +285,8 @@ class ApexEngine:
             try:
                 g_actor, g_dp = [], []
                 for h in (0, 1):
-                    g_actor.append(self._graph(lambda h=h: self._actor_half(h), apool))
-                    g_dp.append(self._graph(lambda h=h: self._dp_step_body(1 - h), self._pool))
+                    g_actor.append(capture_graph(lambda h=h: self._actor_half(h), apool))
+                    g_dp.append(capture_graph(lambda h=h: self._dp_step_body(1 - h), self._pool))
                 self._g_actor, self._g_dp = g_actor, g_dp
                 return
             except RuntimeError as e:  # RCCL capture unsupported here: the phase graphs instead
@@ -332,19 +300,19 @@ class ApexEngine:
             L = self.learner
             self._g_learn_front = []
             for h in (0, 1):
-                self._g_actor.append(self._graph(lambda h=h: self._actor_half(h), apool))
-                self._g_learn_front.append(self._graph(lambda h=h: self._learn_front(1 - h), self._pool))
-                self._g_learn_a.append(self._graph(lambda: (L.forward_phase(part="b"), self._learn_b()), self._pool))
+                self._g_actor.append(capture_graph(lambda h=h: self._actor_half(h), apool))
+                self._g_learn_front.append(capture_graph(lambda h=h: self._learn_front(1 - h), self._pool))
+                self._g_learn_a.append(capture_graph(lambda: (L.forward_phase(part="b"), self._learn_b()), self._pool))
             self._g_learn_b = None
             return
         for h in (0, 1):
-            self._g_actor.append(self._graph(lambda h=h: self._actor_half(h), apool))
+            self._g_actor.append(capture_graph(lambda h=h: self._actor_half(h), apool))
             if self._dp:
-                self._g_learn_a.append(self._graph(lambda h=h: self._learn_a(1 - h), self._pool))
-                self._g_learn_a2.append(self._graph(self.learner.backward_phase, self._pool))
+                self._g_learn_a.append(capture_graph(lambda h=h: self._learn_a(1 - h), self._pool))
+                self._g_learn_a2.append(capture_graph(self.learner.backward_phase, self._pool))
             else:
-                self._g_learn_a.append(self._graph(lambda h=h: (self._learn_a(1 - h), self._learn_b()), self._pool))
-        self._g_learn_b = self._graph(self._learn_b, self._pool) if self._dp else None
+                self._g_learn_a.append(capture_graph(lambda h=h: (self._learn_a(1 - h), self._learn_b()), self._pool))
+        self._g_learn_b = capture_graph(self._learn_b, self._pool) if self._dp else None
 
     def _mass_pending_ok(self) -> bool:
         """One-graph DP step: the shard masses must always arrive with the previous step's
@@ -410,11 +378,7 @@ class ApexEngine:
             self._learn(self._g_learn_a[h].replay, None, None, False)
         self.learn_steps += 1
         self.actor_steps += self.cfg.actor_steps_per_learner_step
-        if self.learn_steps % self.cfg.publish_param_interval == 0:
-            L.wait_event(self._ev_actor[h])  # the actor is not reading its weights
-            self.publish_params()
-        if self.learn_steps % self.cfg.target_update_interval == 0:
-            self.learner.sync_target()
+        self._after_learner_step(lambda: L.wait_event(self._ev_actor[h]))  # the actor is not reading its weights
         self._ev_learn.record(L)
         self._half ^= 1
 
@@ -436,14 +400,21 @@ class ApexEngine:
             self._g_learn_a[h].replay()
         self.learn_steps += 1
         self.actor_steps += self.cfg.actor_steps_per_learner_step
-        if self.learn_steps % self.cfg.publish_param_interval == 0:
-            L.wait_event(self._ev_actor[h])  # the actor is not reading its weights
-            self.publish_params()
-        if self.learn_steps % self.cfg.target_update_interval == 0:
-            self.learner.sync_target()
+        self._after_learner_step(lambda: L.wait_event(self._ev_actor[h]))  # the actor is not reading its weights
         self._half ^= 1
 
     # ------------------------------------------------------------------ steps
+    def _after_learner_step(self, before_publish=None) -> None:
+        """The reference cadences after ``learn_steps`` was advanced: publish the weights to the
+        actor (``before_publish()`` first: the overlap paths wait for the actor stream there)
+        and sync the target network."""
+        if self.learn_steps % self.cfg.publish_param_interval == 0:
+            if before_publish is not None:
+                before_publish()
+            self.publish_params()
+        if self.learn_steps % self.cfg.target_update_interval == 0:
+            self.learner.sync_target()
+
     def actor_step(self) -> None:
         self._drain_mass()
         if self._g_actor is not None:
@@ -460,10 +431,7 @@ class ApexEngine:
         else:
             self._learn(self._g_learn_a.replay, None, None, False)
         self.learn_steps += 1
-        if self.learn_steps % self.cfg.publish_param_interval == 0:
-            self.publish_params()
-        if self.learn_steps % self.cfg.target_update_interval == 0:
-            self.learner.sync_target()
+        self._after_learner_step()
 
     def fill(self, min_transitions: int | None = None) -> None:
         """Run actor steps until the replay holds ``threshold_size`` slots."""
@@ -498,10 +466,7 @@ class ApexEngine:
                 self._train_step_eager()
                 self.learn_steps += 1
                 self.actor_steps += self.cfg.actor_steps_per_learner_step
-                if self.learn_steps % self.cfg.publish_param_interval == 0:
-                    self.publish_params()
-                if self.learn_steps % self.cfg.target_update_interval == 0:
-                    self.learner.sync_target()
+                self._after_learner_step()
             return
         self.learner_step()
         for _ in range(self.cfg.actor_steps_per_learner_step):

@@ -38,7 +38,6 @@ import torch
 import torch.distributed as dist
 
 from ..models.dqn import DuelingDQN
-from ..models.fused import make_hip_net, make_workspace
 from .. import ops
 from ..parallel.experience import (META_COLS, STOP, ActorLink, Dropped, LearnerLinks, Region, apply_packets,
                                    engine_nonce, link_groups)
@@ -46,8 +45,10 @@ from ..parallel.ipc import IpcActorLink, IpcLearnerLinks, packet_bytes
 from ..roles.common import maybe_fault
 from .actor_shard import ActorShard
 from .apex import EngineConfig
+from .graphs import capture_graph
 from .hbm_replay import FRAME_BYTES, HBMReplay
 from .learner import DQNLearner
+from .shard import ActorPolicy
 
 
 def stage_packet(hip, replay: HBMReplay, actor: ActorShard, packet: torch.Tensor, E: int, initial: bool = False):
@@ -76,13 +77,8 @@ def build_actor_rank(cfg: EngineConfig, device, rank: int, R: int, C_r: int, F_r
                        actor_offset=(rank - 1) * E, total_actors=R * E, seed=cfg.seed + 7919 * rank,
                        mode=cfg.nstep_mode)
     model = (model if model is not None else DuelingDQN.from_shapes((4, 84, 84), cfg.n_actions)).to(device)
-    flat = model.flatten_parameters()
-    for p in model.parameters():
-        p.requires_grad_(False)
-    net = make_hip_net(model, lc.dtype)
-    ws = make_workspace(E, cfg.n_actions, device, lc.dtype)
-    ws.q = actor.q  # the heads kernel writes Q (and picks the actions) in place
-    return SimpleNamespace(replay=replay, actor=actor, model=model, flat=flat, net=net, ws=ws, E=E)
+    p = ActorPolicy(model, E, cfg.n_actions, device, "hip", lc.dtype, actor.q)  # (an actor rank acts with the HIP net)
+    return SimpleNamespace(replay=replay, actor=actor, model=model, flat=p.flat, net=p.net, ws=p.ws, E=E)
 
 
 def actor_rank_step(hip, a, packet: torch.Tensor) -> None:
@@ -419,16 +415,12 @@ class CentralApexEngine:
             self._learner_body()  # eager warm-up (a real step)
             self.learn_steps += 1
             torch.cuda.synchronize(self.device)
-            self._g_learn = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._g_learn, pool=pool, capture_error_mode="thread_local"):
-                self._learner_body()
+            self._g_learn = capture_graph(self._learner_body, pool)
         else:
             if not self.actor_step():  # eager warm-up (a real, pushed step)
                 return
             torch.cuda.synchronize(self.device)
-            self._g_actor = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._g_actor, pool=pool, capture_error_mode="thread_local"):
-                self._actor_body()
+            self._g_actor = capture_graph(self._actor_body, pool)
         torch.cuda.synchronize(self.device)
 
     def train_step(self) -> bool:

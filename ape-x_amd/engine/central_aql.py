@@ -51,6 +51,7 @@ import torch.distributed as dist
 from ..parallel.experience import META_COLS, STOP, ActorLink, Dropped, LearnerLinks, engine_nonce, link_groups
 from ..parallel.ipc import IpcActorLink, IpcLearnerLinks, aql_packet_floats, aql_packet_views
 from .aql import AQLEngine, AQLEngineConfig, target_sync_due
+from .graphs import capture_graph
 
 
 class CentralAQLEngine:
@@ -291,16 +292,12 @@ class CentralAQLEngine:
             self._learner_body()  # eager warm-up: a real iteration's work
             self._after_iteration()
             torch.cuda.synchronize(self.device)
-            self._g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._g, capture_error_mode="thread_local"):
-                self._learner_body()
+            self._g = capture_graph(self._learner_body)
         else:
             if not self.actor_step():  # eager warm-up (a real, pushed step)
                 return
             torch.cuda.synchronize(self.device)
-            self._g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._g, capture_error_mode="thread_local"):
-                self._actor_body()
+            self._g = capture_graph(self._actor_body)
         torch.cuda.synchronize(self.device)
 
     def sgd_steps(self) -> int:

@@ -32,7 +32,9 @@ from dataclasses import dataclass
 import torch
 
 from .. import ops
+from .graphs import capture_graph, warm_up
 from .hbm_replay import HBMReplay
+from .shard import ACT_SEED_XOR
 from .vector import MAX_BATCH, PARAM_KEYS, VecRolloutBuffers, env_spec, make_model, save_state_dict, vec_net
 
 MAX_ENVS = 8   # rows of one forward pass of a workgroup (vector_kernels.hip kRows)
@@ -118,7 +120,7 @@ class DQNFrameEngine:
         i64 = dict(dtype=torch.int64, device=dev)
         # ---- actor side
         self.env_seed = (cfg.seed * 0x2545F491 + 0xAC7) & 0xFFFFFFFFFFFF
-        self.act_seed = self.env_seed ^ 0x5E1EC7   # VectorActorShard's key of the action draw
+        self.act_seed = self.env_seed ^ ACT_SEED_XOR   # VectorActorShard's key of the action draw
         self.layout = h.vec_env_state_layout()
         self.env_state = torch.zeros(E, self.layout["STRIDE"], **f32)
         self.hist = torch.zeros(E, 4, **i32)
@@ -245,19 +247,12 @@ class DQNFrameEngine:
     def capture(self, warmup_iters: int = 3) -> None:
         """Run (real, counted) frames up to the first learning frame plus ``warmup_iters`` on a
         side stream, then capture the six launches of a learning frame as one hipGraph."""
-        from .apex import ApexEngine  # the shared thread_local capture helper
-
         if not self.learning:
             raise RuntimeError("capture() records a learning frame")
-        s = torch.cuda.Stream(device=self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):
-            for _ in range(max(self.first_learning_frame - self.frames, 0) + warmup_iters):
-                self.frame()
-        torch.cuda.current_stream(self.device).wait_stream(s)
+        warm_up(self.device, self.frame, max(self.first_learning_frame - self.frames, 0) + warmup_iters)
         torch.cuda.synchronize(self.device)
         self._pool = torch.cuda.graph_pool_handle()
-        self._graph = ApexEngine._graph(self._full_frame, self._pool)
+        self._graph = capture_graph(self._full_frame, self._pool)
         torch.cuda.synchronize(self.device)
 
     def run(self, n: int) -> float:

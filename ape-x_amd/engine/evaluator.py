@@ -30,6 +30,7 @@ import torch
 from .. import ops
 from ..models.dqn import DuelingDQN
 from .actor_shard import ENV_STATE_STRIDE
+from .graphs import capture_graph
 from .hbm_replay import FRAME_BYTES
 
 
@@ -179,10 +180,7 @@ class GPUEvaluator:
         capped episodes is thousands of steps per log window)."""
         self.step()  # (a real step: every kernel's first launch happens outside the capture)
         torch.cuda.synchronize(self.device)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            for _ in range(steps):
-                self.step()
+        g = capture_graph(lambda: [self.step() for _ in range(steps)])
         self.steps -= steps  # the captured steps did not run
         self._graph, self._graph_steps = g, int(steps)
 

@@ -41,13 +41,13 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..algo.schedules import actor_epsilon
 from ..envs.preprocess import area_weights
 from ..models.dqn import DuelingDQN
-from ..models.fused import make_hip_net, make_workspace
 from ..utils.checkpoint import save_model
+from .graphs import capture_graph, warm_up
 from .hbm_replay import HBMReplay
-from .learner import DQNLearner, LearnerConfig, forward_q
+from .learner import DQNLearner, LearnerConfig
+from .shard import ActorPolicy, NStepShard
 
 OUT = 84          # the warp's output side (kHostEnvOut)
 TAP_WIDTH = 8     # weights per output index in the tap tables (kHostEnvTaps)
@@ -130,11 +130,10 @@ class Ingest:
 
 
 # ---------------------------------------------------------------------------- shard
-class HostEnvShard:
-    """``ActorShard``'s interface (``st``, ``q``, ``actions``, ``reward``, ``done``, ``new_frame``,
-    ``slot``, ``prio``, ``ep_log``, ``step_counter``, ``eps``, ``act_args()``, ``observe()``,
-    ``episode_stats()``) over a host vector env.  ``ep_log`` column 3 is the episode's unclipped
-    score."""
+class HostEnvShard(NStepShard):
+    """``ActorShard``'s interface (the :class:`NStepShard` state, ``act_args()``, ``select()``,
+    ``observe()``, ``episode_stats()``) over a host vector env.  ``ep_log`` column 3 is the
+    episode's unclipped score."""
 
     def __init__(self, replay, n_envs: int, n_actions: int, raw_shape, n_step: int = 3, gamma: float = 0.99,
                  eps_base: float = 0.4, eps_alpha: float = 7.0, actor_offset: int = 0, total_actors: int | None = None,
@@ -143,48 +142,18 @@ class HostEnvShard:
         if ingest not in INGEST_MODES:
             raise ValueError(f"ingest must be one of {INGEST_MODES}, got {ingest!r}")
         self.ingest_mode = ingest
-        self.replay = replay
-        self.E, self.A, self.n = int(n_envs), int(n_actions), int(n_step)
-        assert replay.n_envs == self.E, "replay slot layout is sized for this shard's env count"
+        E = int(n_envs)
         H, W, C = (int(x) for x in raw_shape)
         if C != 3:
             raise ValueError("raw emulator frames must be RGB [H, W, 3]")
         dev = replay.device
-        self.device = dev
-        self.seed = int(seed)
-        E, A, n = self.E, self.A, self.n
+        # (first: bad geometry raises before the shard allocates anything on the device)
         self.ingest = Ingest(E, H, W, replay.frame_bytes, replay.frame_capacity, clip_rewards, dev)
-        self.hip = self.ingest.hip
-        total = total_actors if total_actors is not None else E
-        ids = torch.arange(actor_offset, actor_offset + E, dtype=torch.float64)
-        self.eps = torch.as_tensor(actor_epsilon(ids.numpy(), total, eps_base, eps_alpha), dtype=torch.float32,
-                                   device=dev)
-        i32 = dict(dtype=torch.int32, device=dev)
+        super().__init__(replay, E, n_actions, n_step, gamma, eps_base, eps_alpha, actor_offset, total_actors, seed,
+                         mode)
         f32 = dict(dtype=torch.float32, device=dev)
-        self.new_frame = torch.zeros(E, **i32)
-        self.ep_log = torch.zeros(E, 4, **f32)
         self.acc = torch.zeros(E, 4, **f32)      # running (return, raw return, length, -) per env
-        self.q = torch.zeros(E, A, **f32)
-        self.actions = torch.zeros(E, **i32)
-        self.reward = torch.zeros(E, **f32)
-        self.done = torch.zeros(E, **f32)
-        self.slot = torch.zeros(E, **i32)
-        self.prio = torch.zeros(E, **f32)
         self.obs = torch.zeros(E, 4, 84, 84, dtype=torch.uint8, device=dev)
-        self.step_counter = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.st = {
-            "win_ids": torch.zeros(E, n, 4, **i32), "win_a": torch.zeros(E, n, **i32),
-            "win_r": torch.zeros(E, n, **f32), "win_q": torch.zeros(E, n, A, **f32),
-            "win_meta": torch.zeros(E, 4, **i32), "hist": torch.zeros(E, 4, **i32),
-            "drain_ids": torch.zeros(E, n, 4, **i32), "drain_a": torch.zeros(E, n, **i32),
-            "drain_r": torch.zeros(E, n, **f32), "drain_q": torch.zeros(E, n, **f32),
-            "drain_meta": torch.zeros(E, 2, **i32), "drain_s2": torch.zeros(E, 4, **i32),
-        }
-        if mode not in ("reference", "textbook"):
-            raise ValueError("mode must be 'reference' or 'textbook'")
-        st_ptrs = {k: v.data_ptr() for k, v in self.st.items()}
-        self.nstep = self.hip.make_nstep(E, A, n, replay.capacity, float(gamma), 0 if mode == "reference" else 1,
-                                         st_ptrs, replay.trans_ptrs())
         # host staging (pinned: the copies below are truly asynchronous) and the device twins
         self._registered = None
         if staging is None:
@@ -252,20 +221,6 @@ class HostEnvShard:
         self.replay.gather_frames(self.st["hist"], self.obs)
         return self.obs
 
-    def act_args(self) -> tuple:
-        """(eps, rng seed, step counter, actions) pointers for the heads kernel's eps-greedy
-        epilogue -- ``ActorShard.act_args``."""
-        return (self.eps.data_ptr(), self.seed ^ 0x5E1EC7, self.step_counter.data_ptr(), self.actions.data_ptr())
-
-    def select(self, q: torch.Tensor | None = None) -> None:
-        """eps-greedy on ``self.q`` (or ``q``) with the standalone kernel: the same draw as the
-        heads epilogue (for a policy that does not pick the actions itself)."""
-        if q is not None and q.data_ptr() != self.q.data_ptr():
-            self.q.copy_(q)
-        self.hip.select_actions(self.q.data_ptr(), self.E, self.A, self.eps.data_ptr(), self.seed ^ 0x5E1EC7,
-                                self.step_counter.data_ptr(), self.actions.data_ptr(),
-                                torch.cuda.current_stream().cuda_stream)
-
     def begin(self) -> None:
         """After the forward picked ``self.actions``: start their copy to the host and mark the
         point the host has to wait for."""
@@ -312,10 +267,7 @@ class HostEnvShard:
             self.reward_host.numpy()[:] = r
             self.done_host.numpy()[:] = d
             self._ship(0, self.E, False)
-        s = torch.cuda.current_stream().cuda_stream
-        self.hip.nstep_emit(self.nstep, self.q.data_ptr(), self.actions.data_ptr(), self.reward.data_ptr(),
-                            self.done.data_ptr(), self.new_frame.data_ptr(), self.step_counter.data_ptr(),
-                            self.slot.data_ptr(), self.prio.data_ptr(), s, False)
+        self._emit(self.nstep, self.slot, self.prio, False)
         self.replay.write_batch(pre=(self.slot, self.prio, self.replay.filled), bump=self.step_counter)
 
     def close(self) -> None:
@@ -330,10 +282,6 @@ class HostEnvShard:
         """Both halves back to back (``self.actions`` already chosen)."""
         self.begin()
         self.finish(vec)
-
-    def episode_stats(self) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        """(last episode return, last episode length, finished episode count) per env."""
-        return self.ep_log[:, 0], self.ep_log[:, 1], self.ep_log[:, 2]
 
     def episode_scores(self) -> torch.Tensor:
         """Last episode's unclipped score per env (``ep_log`` column 3)."""
@@ -394,17 +342,10 @@ class HostEnvEngine:
         self.ingest = "banked" if self.actor._banked(vec) else "whole"   # what "auto" resolved to
         model = model if model is not None else DuelingDQN.from_shapes((4, 84, 84), A)
         self.learner = DQNLearner(model, self.replay, lc)
-        self.actor_model = copy.deepcopy(self.learner.model)
-        self.actor_model._flat = None
-        self.actor_flat = self.actor_model.flatten_parameters()
-        for p in self.actor_model.parameters():
-            p.requires_grad_(False)
-            p.grad = None
-        self.hip_net = lc.forward == "hip"
-        if self.hip_net:
-            self.actor_net = make_hip_net(self.actor_model, lc.dtype)
-            self.actor_ws = make_workspace(E, A, self.device, lc.dtype)
-            self.actor_ws.q = self.actor.q  # the heads kernel writes the actor's Q in place
+        p = self.policy = ActorPolicy(copy.deepcopy(self.learner.model), E, A, self.device, lc.forward, lc.dtype,
+                                      self.actor.q)
+        self.actor_model, self.actor_flat, self.hip_net = p.model, p.flat, p.hip_net
+        self.actor_net, self.actor_ws = p.net, p.ws   # (None without the HIP forward)
         self.publish_params()
         self.learn_steps = 0
         self.actor_steps = 0
@@ -415,18 +356,12 @@ class HostEnvEngine:
     # ------------------------------------------------------------------ bodies
     def publish_params(self) -> None:
         """Learner -> actor weights (``ApexEngine.publish_params``)."""
-        self.learner.copy_params_to(self.actor_flat)
-        if self.hip_net:
-            self.actor_net.copy_packed_from(self.learner.net)
+        self.policy.publish_from(self.learner)
 
     def _forward(self) -> None:
-        a = self.actor
-        if self.hip_net:  # conv1 reads the stacks from the ring; the heads kernel picks the actions
-            self.actor_net(self.replay.frames, self.actor_ws, a.st["hist"], act=a.act_args())
-            return
-        with torch.no_grad():
-            q = forward_q(self.actor_model, a.observe(), self.cfg.learner.dtype == "bf16")
-        a.select(q)
+        q = self.policy.forward(self.replay, self.actor)
+        if q is not None:  # (the HIP forward's heads kernel picked the actions itself)
+            self.actor.select(q)
 
     def _learn_body(self) -> None:
         self.learner.forward_phase()
@@ -452,21 +387,12 @@ class HostEnvEngine:
         if self._learning:
             return
         self._learning = True
-        cur = torch.cuda.current_stream(self.device)
-        s = torch.cuda.Stream(device=self.device)
-        s.wait_stream(cur)
-        with torch.cuda.stream(s):
-            for _ in range(self.cfg.warmup_learner_steps):
-                self._learner_step()
-        cur.wait_stream(s)
+        warm_up(self.device, self._learner_step, self.cfg.warmup_learner_steps)
         if not self.cfg.use_graphs:
             return
         torch.cuda.synchronize(self.device)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            self._learn_body()
         # (capture records, it does not run: the step counters are untouched)
-        self._g_learn = g
+        self._g_learn = capture_graph(self._learn_body)
 
     def held(self) -> int:
         """Transitions in the replay, from the host's own count (no device read)."""

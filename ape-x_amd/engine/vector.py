@@ -38,13 +38,13 @@ import collections
 import copy
 from dataclasses import dataclass
 
-import numpy as np
 import torch
 
 from .. import ops
-from ..algo.schedules import actor_epsilon
 from ..models.dqn import DuelingDQN
+from .graphs import capture_graph, warm_up
 from .hbm_replay import HBMReplay
+from .shard import NStepShard
 
 # env id -> (kind, obs_dim, n_actions, max_episode_steps); kind indexes the HIP env kernel
 VECTOR_ENVS = {
@@ -96,7 +96,7 @@ def vec_net(hip, model: DuelingDQN):
     return hip.make_vec_net(d)
 
 
-class VectorActorShard:
+class VectorActorShard(NStepShard):
     """E vectorised classic-control envs over an ``HBMReplay`` whose frames are observations
     (``frame_bytes = 4 * obs_dim``): same surface as :class:`ActorShard` (``reset``,
     ``act_and_step``, ``episode_stats``, the ``st`` dict of the n-step batcher)."""
@@ -105,59 +105,21 @@ class VectorActorShard:
                  eps_base: float = 0.4, eps_alpha: float = 7.0, actor_offset: int = 0,
                  total_actors: int | None = None, seed: int = 0, mode: str = "reference",
                  max_episode_steps: int | None = None):
-        self.hip = ops.hip()
-        self.replay = replay
         self.env_id = env_id
-        self.kind, self.obs_dim, self.A, limit = env_spec(env_id)
+        self.kind, self.obs_dim, n_actions, limit = env_spec(env_id)
         self.max_episode_steps = int(limit if max_episode_steps is None else max_episode_steps)
-        self.E, self.n = int(n_envs), int(n_step)
-        if replay.n_envs != self.E:
-            raise ValueError("replay slot layout is sized for this shard's env count")
         if replay.frame_bytes != 4 * self.obs_dim:
             raise ValueError(f"replay frame_bytes must be 4 * obs_dim = {4 * self.obs_dim}")
-        if mode not in ("reference", "textbook"):
-            raise ValueError("mode must be 'reference' or 'textbook'")
-        dev = replay.device
-        self.device = dev
-        self.seed = int(seed)
-        E, A, n = self.E, self.A, self.n
-        total = total_actors if total_actors is not None else E
-        ids = np.arange(actor_offset, actor_offset + E, dtype=np.float64)
-        self.eps = torch.as_tensor(np.atleast_1d(actor_epsilon(ids, total, eps_base, eps_alpha)), dtype=torch.float32,
-                                   device=dev)
-        i32 = dict(dtype=torch.int32, device=dev)
-        f32 = dict(dtype=torch.float32, device=dev)
+        super().__init__(replay, n_envs, n_actions, n_step, gamma, eps_base, eps_alpha, actor_offset, total_actors,
+                         seed, mode)
+        E = self.E
         self.layout = self.hip.vec_env_state_layout()
-        self.env_state = torch.zeros(E, self.layout["STRIDE"], **f32)
-        self.new_frame = torch.zeros(E, **i32)
-        self.ep_log = torch.zeros(E, 4, **f32)
-        self.q = torch.zeros(E, A, **f32)
-        self.actions = torch.zeros(E, **i32)
-        self.reward = torch.zeros(E, **f32)
-        self.done = torch.zeros(E, **f32)
-        self.slot = torch.zeros(E, **i32)
-        self.prio = torch.zeros(E, **f32)
-        self.step_counter = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.st = {
-            "win_ids": torch.zeros(E, n, 4, **i32), "win_a": torch.zeros(E, n, **i32),
-            "win_r": torch.zeros(E, n, **f32), "win_q": torch.zeros(E, n, A, **f32),
-            "win_meta": torch.zeros(E, 4, **i32), "hist": torch.zeros(E, 4, **i32),
-            "drain_ids": torch.zeros(E, n, 4, **i32), "drain_a": torch.zeros(E, n, **i32),
-            "drain_r": torch.zeros(E, n, **f32), "drain_q": torch.zeros(E, n, **f32),
-            "drain_meta": torch.zeros(E, 2, **i32), "drain_s2": torch.zeros(E, 4, **i32),
-        }
-        st_ptrs = {k: v.data_ptr() for k, v in self.st.items()}
-        self.nstep = self.hip.make_nstep(E, A, n, replay.capacity, float(gamma), 0 if mode == "reference" else 1,
-                                         st_ptrs, replay.trans_ptrs())
+        self.env_state = torch.zeros(E, self.layout["STRIDE"], dtype=torch.float32, device=self.device)
         self.ring = replay.frames.view(torch.float32)  # [F, obs_dim]
         self.env = self.hip.make_vec_env(self.kind, E, self.obs_dim, replay.frame_capacity, self.max_episode_steps,
                                          self.env_state.data_ptr(), self.ring.data_ptr(), self.seed)
         self._act = None
         self.reset()
-
-    @staticmethod
-    def _stream() -> int:
-        return torch.cuda.current_stream().cuda_stream
 
     def set_policy(self, model: DuelingDQN) -> None:
         """Act with ``model`` (its parameter storage is read in place by every later step)."""
@@ -165,7 +127,7 @@ class VectorActorShard:
             raise ValueError("policy shape does not match the env")
         self._policy = model
         self._act = self.hip.make_vec_act(vec_net(self.hip, model), self.ring.data_ptr(), self.st["hist"].data_ptr(),
-                                          self.E, self.eps.data_ptr(), self.seed ^ 0x5E1EC7,
+                                          self.E, self.eps.data_ptr(), self.act_seed,
                                           self.step_counter.data_ptr(), self.q.data_ptr(), self.actions.data_ptr())
 
     def reset(self) -> None:
@@ -190,19 +152,12 @@ class VectorActorShard:
     def act_and_step(self, selected: bool = False, tree: bool = True) -> None:
         """One actor step of all envs.  ``selected``: ``self.actions`` (and ``self.q``) already
         hold this step's actions and Q.  ``tree=False``: rows only, no priority-tree write."""
-        s, h = self._stream(), self.hip
         if not selected:
             self.act()
         self.env_step()
-        h.nstep_emit(self.nstep, self.q.data_ptr(), self.actions.data_ptr(), self.reward.data_ptr(),
-                     self.done.data_ptr(), self.new_frame.data_ptr(), self.step_counter.data_ptr(),
-                     self.slot.data_ptr(), self.prio.data_ptr(), s, True)  # (the kernel bumps the counter)
+        self._emit(self.nstep, self.slot, self.prio, True)  # (the kernel bumps the counter)
         if tree:  # unique ring-ordered slots: leaves and every level in one launch
             self.replay.write_priorities(self.slot, self.prio, dedup=False, bumps=((self.replay.filled, self.E),))
-
-    def episode_stats(self) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        """(last episode return, last episode length, finished episode count) per env."""
-        return self.ep_log[:, 0], self.ep_log[:, 1], self.ep_log[:, 2]
 
 
 @dataclass
@@ -440,18 +395,11 @@ class VectorApexEngine:
     def capture(self, warmup_iters: int = 3) -> None:
         """Warm up on a side stream (real, counted train steps), then capture the actor step
         and the learner step as hipGraphs."""
-        from .apex import ApexEngine  # the shared thread_local capture helper
-
-        s = torch.cuda.Stream(device=self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):
-            for _ in range(warmup_iters):
-                self.train_step()
-        torch.cuda.current_stream(self.device).wait_stream(s)
+        warm_up(self.device, self.train_step, warmup_iters)
         torch.cuda.synchronize(self.device)
         self._pool = torch.cuda.graph_pool_handle()
-        self._g_actor = ApexEngine._graph(self._actor_body, self._pool)
-        self._g_learn = ApexEngine._graph(self.learner.step, self._pool)
+        self._g_actor = capture_graph(self._actor_body, self._pool)
+        self._g_learn = capture_graph(self.learner.step, self._pool)
         torch.cuda.synchronize(self.device)
 
     def run(self, n_steps: int) -> float:

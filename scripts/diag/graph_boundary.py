@@ -23,6 +23,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     a = ap.parse_args()
     from apex_amd.engine.apex import ApexEngine, EngineConfig
+    from apex_amd.engine.graphs import capture_graph
     from apex_amd.engine.learner import LearnerConfig
 
     lc = LearnerConfig(batch_size=512, forward="hip", dtype="fp32")
@@ -40,7 +41,7 @@ def main():
     apool = torch.cuda.graph_pool_handle()
 
     def actor_graphs(fn):
-        return [eng._graph(lambda h=h: fn(h), apool) for h in (0, 1)]
+        return [capture_graph(lambda h=h: fn(h), apool) for h in (0, 1)]
 
     g_fwd = actor_graphs(lambda h: eng.actor_net(eng.replay.frames, eng.actor_ws, eng.actor.st["hist"],
                                                  act=eng.actor.act_args()))
@@ -51,7 +52,7 @@ def main():
     L = eng.learner
     fork, join = L._fork_point, L._tree_fork_end
     L._fork_point, L._tree_fork_end = (lambda: None), (lambda: None)
-    g_notree = [eng._graph(lambda h=h: (eng._learn_a(1 - h), eng._learn_b()), eng._pool) for h in (0, 1)]
+    g_notree = [capture_graph(lambda h=h: (eng._learn_a(1 - h), eng._learn_b()), eng._pool) for h in (0, 1)]
 
     # (h) timing probe only: the tree branch forked at the graph's start (it would write the
     # PREVIOUS step's priorities; here it races the sampling -- timing only) and joined after
@@ -64,7 +65,7 @@ def main():
         eng._learn_b()
         torch.cuda.current_stream().wait_stream(L.tree_stream)
 
-    g_rootfork = [eng._graph(lambda h=h: root_fork(h), eng._pool) for h in (0, 1)]
+    g_rootfork = [capture_graph(lambda h=h: root_fork(h), eng._pool) for h in (0, 1)]
     L._fork_point, L._tree_fork_end = fork, join
     torch.cuda.synchronize()
     eng._ev_learn.record(torch.cuda.current_stream())
