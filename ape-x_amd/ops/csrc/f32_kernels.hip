@@ -136,7 +136,11 @@ struct HasColsum<P, decltype((void)P::A_COLSUM, void())> {
   static constexpr bool value = P::A_COLSUM;
 };
 
-// ReLU sign bits (one bit per stored activation, words of 32 channels per row), both optional:
+// ReLU sign bits (one bit per stored activation, words of 32 channels per row), both optional
+// (the hooks as the element epilogue uses them; the row-owned epilogue, gemm_body<.., RW = true>,
+// needs only want_bits / bits_ptr / mask_word: a lane owns its row, so the word it loaded is its
+// own and the 16 bits of its half of a row come from its own registers, two halves joined by one
+// cross-half exchange):
 //  * a forward policy may WRITE them (HasReluBits: want_bits(ctx) block-uniform, stored(a, c, n, v)
 //    = the activation its store() writes, bits_word(c, ml, nl0) = the word of tile row ml and
 //    columns nl0 .. nl0 + 31, nullptr for a row past M): per accumulator element one ballot of
@@ -155,6 +159,19 @@ template <class P, class = void>
 struct HasMaskBits : std::false_type {};
 template <class P>
 struct HasMaskBits<P, decltype((void)P::MASK_BITS, void())> : std::true_type {};
+
+// Row-owned epilogue hooks (gemm_body<.., RW = true>): out_row(a, c, ml) = the address of tile row
+// ml, tile column 0 (nullptr for a row past the problem; rows are 16-byte aligned), optionally
+// fin4(a, c, nl, v) = the four values stored at tile columns nl .. nl + 3 (bias + ReLU).  A policy
+// whose store cannot always widen (ELEM_STORE: wide_rows(a) block-uniform) keeps store() too.
+template <class P, class = void>
+struct HasFin4 : std::false_type {};
+template <class P>
+struct HasFin4<P, decltype((void)P::FIN4, void())> : std::true_type {};
+template <class P, class = void>
+struct HasElemStore : std::false_type {};
+template <class P>
+struct HasElemStore<P, decltype((void)P::ELEM_STORE, void())> : std::true_type {};
 
 // The next k-block is loaded into registers while the current one computes (its LDS store
 // follows the MFMA block).  Policies may precompute a per-thread row state once (the k-invariant part of an operand
@@ -321,7 +338,9 @@ __device__ __forceinline__ uint2 ds_tr16(const char* p) {
 // k-slots at every depth: bit-identical results (tests/test_gpu_f32_prefetch.py).
 // XB: the launch carries sign bits (a kernel of its own: with the hooks compiled into the plain
 // kernels behind a null-pointer test, those ran 1.3 % slower per step with every pointer null).
-template <class P, int SS, int D, bool XB = false>
+// RW: the row-owned epilogue (operand roles swapped on the MFMA; APEX_F32_EPILOGUE picks per launch
+// class); false = the element epilogue.  Same products, same k order: bit-identical results.
+template <class P, int SS, int D, bool XB = false, bool RW = true>
 __device__ __forceinline__ void gemm_body(const typename P::Args& args, int block, float* lds,
                                           typename P::Smem& sm) {
   using G = Geo<P>;
@@ -514,6 +533,14 @@ __device__ __forceinline__ void gemm_body(const typename P::Args& args, int bloc
     }
     return f;
   };
+  // one product term.  RW (row-owned epilogue): the B fragment rides the MFMA's first operand and
+  // the A fragment its second, so the 32 x 32 block comes out transposed -- lane (r, h) holds
+  // row m = r and columns n = 4h + 8j + i in register 4j + i: four runs of four consecutive n.
+  // The products commute exactly and every k-slot is the same: bit-identical accumulators.
+  auto mm = [](bfx8 a, bfx8 b, f32x16 c) {
+    if constexpr (RW) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(b, a, c, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+  };
   auto compute = [&](int buf) {
     if constexpr (SS) {
       const char* As = reinterpret_cast<const char*>(lds) + buf * (GS::SA + GS::SB);
@@ -534,13 +561,13 @@ __device__ __forceinline__ void gemm_body(const typename P::Args& args, int bloc
 #pragma unroll
           for (int ni = 0; ni < G::TN; ++ni) {
             f32x16 x = accx[mi][ni];
-            x = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi].l, b[ni].h, x, 0, 0, 0);
-            x = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi].m, b[ni].m, x, 0, 0, 0);
-            x = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi].h, b[ni].l, x, 0, 0, 0);
-            x = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi].m, b[ni].h, x, 0, 0, 0);
-            x = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi].h, b[ni].m, x, 0, 0, 0);
+            x = mm(a[mi].l, b[ni].h, x);
+            x = mm(a[mi].m, b[ni].m, x);
+            x = mm(a[mi].h, b[ni].l, x);
+            x = mm(a[mi].m, b[ni].h, x);
+            x = mm(a[mi].h, b[ni].m, x);
             accx[mi][ni] = x;
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi].h, b[ni].h, acc[mi][ni], 0, 0, 0);
+            acc[mi][ni] = mm(a[mi].h, b[ni].h, acc[mi][ni]);
           }
       }
       return;
@@ -562,13 +589,13 @@ __device__ __forceinline__ void gemm_body(const typename P::Args& args, int bloc
 #pragma unroll
         for (int ni = 0; ni < G::TN; ++ni) {
           f32x16 x = accx[mi][ni];
-          x = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi].l, b[ni].h, x, 0, 0, 0);
-          x = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi].m, b[ni].m, x, 0, 0, 0);
-          x = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi].h, b[ni].l, x, 0, 0, 0);
-          x = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi].m, b[ni].h, x, 0, 0, 0);
-          x = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi].h, b[ni].m, x, 0, 0, 0);
+          x = mm(a[mi].l, b[ni].h, x);
+          x = mm(a[mi].m, b[ni].m, x);
+          x = mm(a[mi].h, b[ni].l, x);
+          x = mm(a[mi].m, b[ni].h, x);
+          x = mm(a[mi].h, b[ni].m, x);
           accx[mi][ni] = x;
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi].h, b[ni].h, acc[mi][ni], 0, 0, 0);
+          acc[mi][ni] = mm(a[mi].h, b[ni].h, acc[mi][ni]);
         }
     }
   };
@@ -668,58 +695,130 @@ __device__ __forceinline__ void gemm_body(const typename P::Args& args, int bloc
 #pragma unroll
     for (int ni = 0; ni < G::TN; ++ni) acc[mi][ni] += accx[mi][ni];
 
-  if constexpr (RBITS) {
-    {
-      // lane (r, h) tests bit r of the word of row (e, h): one mask per half, so each of the two
-      // scalar words meets a VGPR operand
-      const uint32_t bit0 = h ? 0u : 1u << r, bit1 = h ? 1u << r : 0u;
+  if constexpr (RW) {
+    // Row-owned epilogue: lane (r, h) holds row r of each 32 x 32 block, so the row predicate and
+    // the row's address are taken once per lane and block, the 16 values go out as four 16-byte
+    // stores, the ReLU-mask word the lane loaded before the k loop is the word of its OWN row, and
+    // the 16 sign bits of its half of a row come from its own registers.
+    bool wide = true;
+    if constexpr (HasElemStore<P>::value) wide = P::wide_rows(args);  // block-uniform
+    if (!wide) {
 #pragma unroll
       for (int mi = 0; mi < G::TM; ++mi)
 #pragma unroll
         for (int ni = 0; ni < G::TN; ++ni)
 #pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            const int row0 = (e & 3) + 8 * (e >> 2);
-            const uint32_t w0 = __builtin_amdgcn_readlane(mw[mi][ni], row0);
-            const uint32_t w1 = __builtin_amdgcn_readlane(mw[mi][ni], row0 + 4);
-            const bool keep = ((w0 & bit0) | (w1 & bit1)) != 0u;
-            P::store_keep(args, ctx, wm * G::WTM + mi * 32 + row0 + 4 * h, wn * G::WTN + ni * 32 + r, acc[mi][ni][e],
-                          keep);
-          }
-    }
-  } else {
+          for (int e = 0; e < 16; ++e)
+            P::store(args, ctx, wm * G::WTM + mi * 32 + r, wn * G::WTN + ni * 32 + 4 * h + 8 * (e >> 2) + (e & 3),
+                     acc[mi][ni][e]);
+    } else {
+      bool wbits = false;
+      if constexpr (WBITS) wbits = P::want_bits(ctx);  // block-uniform
 #pragma unroll
-    for (int mi = 0; mi < G::TM; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < G::TN; ++ni)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int row = (e & 3) + 8 * (e >> 2) + 4 * h;
-          P::store(args, ctx, wm * G::WTM + mi * 32 + row, wn * G::WTN + ni * 32 + r, acc[mi][ni][e]);
-        }
-  }
-
-  if constexpr (WBITS) {
-    if (P::want_bits(ctx)) {  // block-uniform: every lane takes part in the ballots
-#pragma unroll
-      for (int mi = 0; mi < G::TM; ++mi)
+      for (int mi = 0; mi < G::TM; ++mi) {
+        const int ml = wm * G::WTM + mi * 32 + r;
+        float* const orow = P::out_row(args, ctx, ml);  // nullptr: a row past the problem
 #pragma unroll
         for (int ni = 0; ni < G::TN; ++ni) {
-          uint32_t mine = 0u;
+          const int nl0 = wn * G::WTN + ni * 32 + 4 * h;
+          f32x4 v[4];
+          uint32_t half = 0u;  // bit 8j + i: value i of run j is > 0
 #pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            const float sv = P::stored(args, ctx, wn * G::WTN + ni * 32 + r, acc[mi][ni][e]);
-            const unsigned long long bal = __ballot(sv > 0.f);
-            const uint32_t wd = h ? (uint32_t)(bal >> 32) : (uint32_t)bal;  // this half's row (e, h)
-            mine = r == e ? wd : mine;
+          for (int j = 0; j < 4; ++j) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[j][i] = acc[mi][ni][4 * j + i];
+            if constexpr (HasFin4<P>::value) v[j] = P::fin4(args, ctx, nl0 + 8 * j, v[j]);
+            if constexpr (WBITS) {
+#pragma unroll
+              for (int i = 0; i < 4; ++i) half |= v[j][i] > 0.f ? 1u << (8 * j + i) : 0u;
+            }
           }
-          if (r < 16) {  // lane e of each half: row (e, h)
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-            uint32_t* bp = P::bits_ptr(ctx, wm * G::WTM + mi * 32 + row, wn * G::WTN + ni * 32);
-            if (bp) *bp = mine;
+          if constexpr (RBITS) {
+            const uint32_t kw = mw[mi][ni] >> (4 * h);  // bit 8j + i: column 4h + 8j + i of this row
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+              for (int i = 0; i < 4; ++i) v[j][i] = (kw >> (8 * j + i)) & 1u ? v[j][i] : 0.f;
+          }
+          if (orow) {
+            if constexpr (HasMaskBits<P>::value && !RBITS) {  // the fp32 activation at the output's offsets
+              const float* mrow = args.mask + (orow - args.out);
+#pragma unroll
+              for (int j = 0; j < 4; ++j) {
+                const f32x4 mk = ld4(mrow + nl0 + 8 * j);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) v[j][i] = mk[i] > 0.f ? v[j][i] : 0.f;
+              }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(orow + nl0 + 8 * j) = v[j];
+          }
+          if constexpr (WBITS) {
+            if (wbits) {  // the halves of a row's word sit in lanes r and r + 32: one exchange, one store
+              const uint32_t mine = half << (4 * h);
+              const uint32_t word = mine | (uint32_t)__shfl_xor((int)mine, 32);
+              uint32_t* bp = P::bits_ptr(ctx, ml, wn * G::WTN + ni * 32);
+              if (h == 0 && bp) *bp = word;
+            }
           }
         }
+      }
     }
+  } else {
+    if constexpr (RBITS) {
+      {
+        // lane (r, h) tests bit r of the word of row (e, h): one mask per half, so each of the two
+        // scalar words meets a VGPR operand
+        const uint32_t bit0 = h ? 0u : 1u << r, bit1 = h ? 1u << r : 0u;
+  #pragma unroll
+        for (int mi = 0; mi < G::TM; ++mi)
+  #pragma unroll
+          for (int ni = 0; ni < G::TN; ++ni)
+  #pragma unroll
+            for (int e = 0; e < 16; ++e) {
+              const int row0 = (e & 3) + 8 * (e >> 2);
+              const uint32_t w0 = __builtin_amdgcn_readlane(mw[mi][ni], row0);
+              const uint32_t w1 = __builtin_amdgcn_readlane(mw[mi][ni], row0 + 4);
+              const bool keep = ((w0 & bit0) | (w1 & bit1)) != 0u;
+              P::store_keep(args, ctx, wm * G::WTM + mi * 32 + row0 + 4 * h, wn * G::WTN + ni * 32 + r, acc[mi][ni][e],
+                            keep);
+            }
+      }
+    } else {
+  #pragma unroll
+      for (int mi = 0; mi < G::TM; ++mi)
+  #pragma unroll
+        for (int ni = 0; ni < G::TN; ++ni)
+  #pragma unroll
+          for (int e = 0; e < 16; ++e) {
+            const int row = (e & 3) + 8 * (e >> 2) + 4 * h;
+            P::store(args, ctx, wm * G::WTM + mi * 32 + row, wn * G::WTN + ni * 32 + r, acc[mi][ni][e]);
+          }
+    }
+
+    if constexpr (WBITS) {
+      if (P::want_bits(ctx)) {  // block-uniform: every lane takes part in the ballots
+  #pragma unroll
+        for (int mi = 0; mi < G::TM; ++mi)
+  #pragma unroll
+          for (int ni = 0; ni < G::TN; ++ni) {
+            uint32_t mine = 0u;
+  #pragma unroll
+            for (int e = 0; e < 16; ++e) {
+              const float sv = P::stored(args, ctx, wn * G::WTN + ni * 32 + r, acc[mi][ni][e]);
+              const unsigned long long bal = __ballot(sv > 0.f);
+              const uint32_t wd = h ? (uint32_t)(bal >> 32) : (uint32_t)bal;  // this half's row (e, h)
+              mine = r == e ? wd : mine;
+            }
+            if (r < 16) {  // lane e of each half: row (e, h)
+              const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+              uint32_t* bp = P::bits_ptr(ctx, wm * G::WTM + mi * 32 + row, wn * G::WTN + ni * 32);
+              if (bp) *bp = mine;
+            }
+          }
+      }
+    }
+
   }
 
   if constexpr (COLSUM) {
@@ -755,19 +854,19 @@ struct BodyForm {
   static constexpr int value = SS == 3 ? 2 : SS;
 };
 
-template <class P, int SS, int D, bool XB = false>
+template <class P, int SS, int D, bool XB = false, bool RW = true>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SS == 3 || D > 1 ? 3 : 1))) void gemm_k(
     typename P::Args args) {
   __shared__ __attribute__((aligned(16))) float lds[LdsFloats<P, SS>::value];
   __shared__ typename P::Smem sm;
-  gemm_body<P, BodyForm<SS>::value, D, XB>(args, xcd_chunk(blockIdx.x, gridDim.x), lds, sm);
+  gemm_body<P, BodyForm<SS>::value, D, XB, RW>(args, xcd_chunk(blockIdx.x, gridDim.x), lds, sm);
 }
 
 // Two independent GEMMs in one launch: blocks [0, n1) run P1, the rest P2 (P1 first: the
 // longer per-block problem starts early).
 // r (stage > 0): the learner's priority-tree write riding the launch as extra workgroups
 // (tree_dev.h tree_ride: the leaves in block 0, a level's recompute past the GEMM tiles).
-template <class P1, class P2, int SS, int D, bool XB = false>
+template <class P1, class P2, int SS, int D, bool XB = false, bool RW = true>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SS == 3 || D > 1 ? 3 : 1))) void gemm2_k(
     typename P1::Args a1, typename P2::Args a2, int n1, TreeRide r) {
   __shared__ __attribute__((aligned(16))) float lds[MaxI<LdsFloats<P1, SS>::value, LdsFloats<P2, SS>::value>::value];
@@ -778,9 +877,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SS == 3 || 
   int b = blockIdx.x;
   if (r.stage && tree_ride(r, r.nhost, lds, &b)) return;  // (grid-uniform stage, block-uniform role)
   if (b < n1)
-    gemm_body<P1, BodyForm<SS>::value, D, XB>(a1, b, lds, sm.s1);
+    gemm_body<P1, BodyForm<SS>::value, D, XB, RW>(a1, b, lds, sm.s1);
   else
-    gemm_body<P2, BodyForm<SS>::value, D, XB>(a2, b - n1, lds, sm.s2);
+    gemm_body<P2, BodyForm<SS>::value, D, XB, RW>(a2, b - n1, lds, sm.s2);
 }
 
 __device__ __forceinline__ F32Prob pick(const F32Set& s, int i) {
@@ -852,6 +951,15 @@ struct Conv2FwdT {  // a2 = relu(conv(a1, W2) + b2); k = (ky, kx, ci) = tap * 32
   static __device__ void store(const Args& a, const Ctx& c, int ml, int n, float v) {
     const int m = c.m0 + ml;
     if (m < c.M) c.p.out[(size_t)m * 64 + c.n0 + n] = stored(a, c, n, v);
+  }
+  static constexpr bool FIN4 = true;
+  static __device__ float* out_row(const Args&, const Ctx& c, int ml) {
+    const int m = c.m0 + ml;
+    return m < c.M ? c.p.out + (size_t)m * 64 + c.n0 : nullptr;
+  }
+  static __device__ f32x4 fin4(const Args&, const Ctx& c, int n, f32x4 v) {
+    const f32x4 b = ld4(c.p.bias + c.n0 + n);
+    return f32x4{fmaxf(v[0] + b[0], 0.f), fmaxf(v[1] + b[1], 0.f), fmaxf(v[2] + b[2], 0.f), fmaxf(v[3] + b[3], 0.f)};
   }
   // sign bits [M][2]: word (n0 + nl0) / 32 of row m (gemm_body's HasReluBits epilogue)
   static constexpr bool RELU_BITS = true;
@@ -926,6 +1034,15 @@ struct Conv3FwdT {  // a3 = relu(conv(a2, W3) + b3); k = tap * 64 + ci; w = w3p
     const int m = c.m0 + ml;
     if (m < c.M) c.p.out[(size_t)m * 64 + c.n0 + n] = stored(a, c, n, v);
   }
+  static constexpr bool FIN4 = true;
+  static __device__ float* out_row(const Args&, const Ctx& c, int ml) {
+    const int m = c.m0 + ml;
+    return m < c.M ? c.p.out + (size_t)m * 64 + c.n0 : nullptr;
+  }
+  static __device__ f32x4 fin4(const Args&, const Ctx& c, int n, f32x4 v) {
+    const f32x4 b = ld4(c.p.bias + c.n0 + n);
+    return f32x4{fmaxf(v[0] + b[0], 0.f), fmaxf(v[1] + b[1], 0.f), fmaxf(v[2] + b[2], 0.f), fmaxf(v[3] + b[3], 0.f)};
+  }
   // sign bits [M][2]: word (n0 + nl0) / 32 of row m (gemm_body's HasReluBits epilogue)
   static constexpr bool RELU_BITS = true;
   static __device__ bool want_bits(const Ctx& c) { return c.p.relu_bits != nullptr; }
@@ -976,6 +1093,10 @@ struct Fc1FwdT {  // z[s][b][n] = sum_{k' in split s} a3[b][k'] wfc1p[n][k'], k'
   static __device__ void store(const Args&, const Ctx& c, int ml, int nl, float v) {
     const int b = c.m0 + ml;
     if (b < c.B) c.p.out[((size_t)c.split * c.B + b) * 256 + c.n0 + nl] = v;
+  }
+  static __device__ float* out_row(const Args&, const Ctx& c, int ml) {
+    const int b = c.m0 + ml;
+    return b < c.B ? c.p.out + ((size_t)c.split * c.B + b) * 256 + c.n0 : nullptr;
   }
   // row states: the chunk's k-invariant byte offsets (rows past the batch: past the range, zeros)
   using RowA = BufRow;
@@ -1334,6 +1455,10 @@ struct Fc1Dgrad {  // dy3[b][k'] = (a3 > 0) * sum_n dz[b][n] wfc1p[n][k']
     const int b = c.m0 + ml;
     if (b < a.B) a.out[(size_t)b * 3136 + c.n0 + nl] = keep ? v : 0.f;
   }
+  static __device__ float* out_row(const Args& a, const Ctx& c, int ml) {
+    const int b = c.m0 + ml;
+    return b < a.B ? a.out + (size_t)b * 3136 + c.n0 : nullptr;
+  }
 };
 
 struct Fc1Wgrad {  // dW[n][k'] = sum_b dz[b][n] a3[b][k'], stored to the reference [n][c*49 + p]
@@ -1387,6 +1512,12 @@ struct Fc1Wgrad {  // dW[n][k'] = sum_b dz[b][n] a3[b][k'], stored to the refere
     const int ref = (k & 63) * 49 + (k >> 6);
     if (n < 128) a.out[n * 3136 + ref] = v;
     else a.out2[(n - 128) * 3136 + ref] = v;
+  }
+  // the in-place reference layout (stride 49 between channels) cannot take 16-byte stores
+  static constexpr bool ELEM_STORE = true;
+  static __device__ bool wide_rows(const Args& a) { return a.splits > 0; }
+  static __device__ float* out_row(const Args& a, const Ctx& c, int ml) {
+    return a.out + ((size_t)c.split * 256 + c.m0 + ml) * 3136 + c.n0;
   }
 };
 
@@ -1442,6 +1573,9 @@ struct ConvWgrad {
   }
   static __device__ void store(const Args& a, const Ctx& c, int m, int nl, float v) {
     a.out[((size_t)c.split * 64 + m) * N + c.n0 + nl] = v;
+  }
+  static __device__ float* out_row(const Args& a, const Ctx& c, int m) {
+    return a.out + ((size_t)c.split * 64 + m) * N + c.n0;
   }
   static __device__ bool want_colsum(const Ctx& c) { return c.n0 == 0; }
   static __device__ void store_colsum(const Args& a, const Ctx& c, int m, float v) {
@@ -1722,6 +1856,10 @@ struct Conv3DgradPT {  // dy2[b][pi][ci] = (a2 > 0) * sum_{valid taps, co} dy3[b
     const int b = c.b0 + ml;
     if (b < a.B) a.out[((size_t)b * 81 + c.pos) * 64 + c.n0 + n] = keep ? v : 0.f;
   }
+  static __device__ float* out_row(const Args& a, const Ctx& c, int ml) {
+    const int b = c.b0 + ml;
+    return b < a.B ? a.out + ((size_t)b * 81 + c.pos) * 64 + c.n0 : nullptr;
+  }
 };
 
 // Under the register split BK 16 won (half the LDS: more workgroups per CU beside the
@@ -1804,6 +1942,11 @@ struct Conv2DgradPT {
     if (b >= a.B) return;
     const int iy = 2 * c.jy + (c.cls >> 1), ix = 2 * c.jx + (c.cls & 1);
     a.out[((size_t)b * 400 + iy * 20 + ix) * 32 + n] = keep ? v : 0.f;
+  }
+  static __device__ float* out_row(const Args& a, const Ctx& c, int ml) {
+    const int b = c.b0 + ml;
+    const int iy = 2 * c.jy + (c.cls >> 1), ix = 2 * c.jx + (c.cls & 1);
+    return b < a.B ? a.out + ((size_t)b * 400 + iy * 20 + ix) * 32 : nullptr;
   }
 };
 using Conv2DgradP = Conv2DgradPT<16>;
@@ -1891,39 +2034,78 @@ int batch_resolve_mask() {
   }
   return g_batch_resolve;
 }
+// Epilogue of the GEMM bodies per launch class, read at launch time (a captured graph keeps the
+// one it was captured with): bit 0 = the learner-sized forward launches, bit 1 = the backward
+// pairs, bit 2 = the forward launches below the learner's size; a set bit = the row-owned
+// epilogue (operand roles swapped on the MFMA, 16-byte stores), a clear one = the element
+// epilogue (one dword per lane and store).  Bit-identical results (tests/test_gpu_f32_epilogue.py).
+// A class's DEFAULT epilogue is built for every form and depth, its other one only for the forms
+// the defaults run (forward: 0 and 3, backward pairs: 3) at depth 1 -- asking for it elsewhere
+// throws.  Whole step on one box, builds and masks alternated in separate processes
+// (profiles/epilogue_rows.md): the learner-sized forward gains 3.7 % (conv2 forward 59.8 -> 53.9 us);
+// the backward pairs lose (conv2 pair 45.6 -> 47.3 us per launch, step -0.2 %: 32 rows x 32 bytes
+// per store instruction against 2 rows x 128) and the small launches stay inside the noise.
+constexpr int kEpilogueDefault = 1;
+int g_epilogue = -1;
+int epilogue_mask() {
+  if (g_epilogue < 0) {
+    const char* e = std::getenv("APEX_F32_EPILOGUE");
+    g_epilogue = e ? std::atoi(e) & 7 : kEpilogueDefault;
+  }
+  return g_epilogue;
+}
 // cls: 0 = learner-sized forward, 1 = backward pair, 2 = small forward
+bool row_epilogue(int cls) { return (epilogue_mask() >> cls) & 1; }
+constexpr bool row_epilogue_default(int cls) { return (kEpilogueDefault >> cls) & 1; }
 int prefetch_depth(int cls) { return std::min(3, 1 + ((prefetch_mask() >> (2 * cls)) & 3)); }
 
-// small: a launch below the learner's size (the actor's / evaluator's forward) -- bits 4-5 of the
-// mask, when set, give those launches a form of their own (form + 1; 0 = the forward form)
-template <class P, int D, bool XB>
-void launch1_d(const typename P::Args& a, int blocks, hipStream_t s, int form) {
+template <class P, int D, bool XB, bool RW>
+void launch1_f(const typename P::Args& a, int blocks, hipStream_t s, int form) {
   switch (form) {
-    case 1: gemm_k<P, 1, D, XB><<<blocks, 256, 0, s>>>(a); break;
-    case 2: gemm_k<P, 2, D, XB><<<blocks, 256, 0, s>>>(a); break;
-    case 3: gemm_k<P, 3, D, XB><<<blocks, 256, 0, s>>>(a); break;
-    default: gemm_k<P, 0, D, XB><<<blocks, 256, 0, s>>>(a);
+    case 1: gemm_k<P, 1, D, XB, RW><<<blocks, 256, 0, s>>>(a); break;
+    case 2: gemm_k<P, 2, D, XB, RW><<<blocks, 256, 0, s>>>(a); break;
+    case 3: gemm_k<P, 3, D, XB, RW><<<blocks, 256, 0, s>>>(a); break;
+    default: gemm_k<P, 0, D, XB, RW><<<blocks, 256, 0, s>>>(a);
   }
 }
-template <class P, bool XB>
-void launch1_x(const typename P::Args& a, int blocks, hipStream_t s, bool small) {
+// CLS 0: a learner-sized forward launch; CLS 2: a launch below the learner's size (the actor's /
+// evaluator's forward) -- bits 4-5 of the form mask, when set, give those launches a form of their
+// own (form + 1; 0 = the forward form)
+template <class P, int CLS, int D, bool XB>
+void launch1_d(const typename P::Args& a, int blocks, hipStream_t s, int form) {
+  constexpr bool DEF = row_epilogue_default(CLS);
+  if (row_epilogue(CLS) == DEF) return launch1_f<P, D, XB, DEF>(a, blocks, s, form);
+  if constexpr (D == 1) {
+    if (form == 0) {
+      gemm_k<P, 0, 1, XB, !DEF><<<blocks, 256, 0, s>>>(a);
+      return;
+    }
+    if (form == 3) {
+      gemm_k<P, 3, 1, XB, !DEF><<<blocks, 256, 0, s>>>(a);
+      return;
+    }
+  }
+  throw std::invalid_argument("f32: a forward class's non-default epilogue is built for forms 0 and 3 at prefetch depth 1");
+}
+template <class P, int CLS, bool XB>
+void launch1_x(const typename P::Args& a, int blocks, hipStream_t s) {
   const int m = stage_split_mask();
-  const int form = small && ((m >> 4) & 3) ? ((m >> 4) & 3) - 1 : m & 3;
-  switch (prefetch_depth(small ? 2 : 0)) {
-    case 2: launch1_d<P, 2, XB>(a, blocks, s, form); break;
-    case 3: launch1_d<P, 3, XB>(a, blocks, s, form); break;
-    default: launch1_d<P, 1, XB>(a, blocks, s, form);
+  const int form = CLS == 2 && ((m >> 4) & 3) ? ((m >> 4) & 3) - 1 : m & 3;
+  switch (prefetch_depth(CLS)) {
+    case 2: launch1_d<P, CLS, 2, XB>(a, blocks, s, form); break;
+    case 3: launch1_d<P, CLS, 3, XB>(a, blocks, s, form); break;
+    default: launch1_d<P, CLS, 1, XB>(a, blocks, s, form);
   }
 }
 // bits: the launch writes ReLU sign bits (policies with the hook: the kernels compiled with it)
-template <class P>
-void launch1(const typename P::Args& a, int blocks, hipStream_t s, bool small = false, bool bits = false) {
+template <class P, int CLS>
+void launch1(const typename P::Args& a, int blocks, hipStream_t s, bool bits = false) {
   if (blocks <= 0) return;
   if constexpr (HasReluBits<P>::value) {
-    if (bits) launch1_x<P, true>(a, blocks, s, small);
-    else launch1_x<P, false>(a, blocks, s, small);
+    if (bits) launch1_x<P, CLS, true>(a, blocks, s);
+    else launch1_x<P, CLS, false>(a, blocks, s);
   } else {
-    launch1_x<P, false>(a, blocks, s, small);
+    launch1_x<P, CLS, false>(a, blocks, s);
   }
   LAUNCH_CHECK();
 }
@@ -1931,11 +2113,22 @@ void launch1(const typename P::Args& a, int blocks, hipStream_t s, bool small = 
 template <class P1, class P2, int D, bool XB>
 void launch2_d(const typename P1::Args& a1, const typename P2::Args& a2, int n1, int nb, const TreeRide& r,
                hipStream_t s) {
-  switch ((stage_split_mask() >> 2) & 3) {
-    case 1: gemm2_k<P1, P2, 1, D, XB><<<nb, 256, 0, s>>>(a1, a2, n1, r); break;
-    case 2: gemm2_k<P1, P2, 2, D, XB><<<nb, 256, 0, s>>>(a1, a2, n1, r); break;
-    case 3: gemm2_k<P1, P2, 3, D, XB><<<nb, 256, 0, s>>>(a1, a2, n1, r); break;
-    default: gemm2_k<P1, P2, 0, D, XB><<<nb, 256, 0, s>>>(a1, a2, n1, r);
+  constexpr bool DEF = row_epilogue_default(1);
+  const int form = (stage_split_mask() >> 2) & 3;
+  if (row_epilogue(1) != DEF) {
+    if constexpr (D == 1) {
+      if (form == 3) {
+        gemm2_k<P1, P2, 3, 1, XB, !DEF><<<nb, 256, 0, s>>>(a1, a2, n1, r);
+        return;
+      }
+    }
+    throw std::invalid_argument("f32: the backward pairs' non-default epilogue is built for form 3 at prefetch depth 1");
+  }
+  switch (form) {
+    case 1: gemm2_k<P1, P2, 1, D, XB, DEF><<<nb, 256, 0, s>>>(a1, a2, n1, r); break;
+    case 2: gemm2_k<P1, P2, 2, D, XB, DEF><<<nb, 256, 0, s>>>(a1, a2, n1, r); break;
+    case 3: gemm2_k<P1, P2, 3, D, XB, DEF><<<nb, 256, 0, s>>>(a1, a2, n1, r); break;
+    default: gemm2_k<P1, P2, 0, D, XB, DEF><<<nb, 256, 0, s>>>(a1, a2, n1, r);
   }
 }
 template <class P1, class P2, bool XB>
@@ -1971,9 +2164,10 @@ void check_set(const F32Set& set) {
     throw std::invalid_argument("f32: batch too large for 32-bit operand offsets");
 }
 
-template <class P>
+// CLS: 0 = a learner-sized launch (>= 1024 rows of samples), 2 = a small one
+template <class P, int CLS>
 void fwd_launch(const F32Set& set, hipStream_t s) {
-  launch1<P>(set, set.n * P::tiles(set.B), s, set.n * set.B < 1024, set.p[0].relu_bits != nullptr);
+  launch1<P, CLS>(set, set.n * P::tiles(set.B), s, set.p[0].relu_bits != nullptr);
 }
 
 }  // namespace
@@ -1982,6 +2176,8 @@ void f32_set_stage_split(int mask) { g_stage_split = mask; }
 int f32_stage_split() { return stage_split_mask(); }
 void f32_set_prefetch(int mask) { g_prefetch = mask; }
 int f32_prefetch() { return prefetch_mask(); }
+void f32_set_epilogue(int mask) { g_epilogue = mask < 0 ? -1 : mask & 7; }
+int f32_epilogue() { return epilogue_mask(); }
 void f32_set_batch_resolve(int mask) { g_batch_resolve = mask < 0 ? -1 : mask & 3; }
 int f32_batch_resolve() { return batch_resolve_mask(); }
 
@@ -2038,18 +2234,18 @@ void f32_conv_fwd_multi(int layer, const F32Set& set, hipStream_t s, int c1_grid
     case 2:  // learner: 128 x 64 tiles at BK 32 (64 x 32 per wave): on the split-bf16 MFMA 66.6-67.5 us
              // vs 73-79 for 64 x 64 (under fp32 MFMA 64 x 64 had won) and 76-88 for 256 x 64 (64 x 64
              // per wave: one wave per SIMD); whole step 2456-2466 vs 2193-2200 steps/s for 256 x 64
-      if (learner_sized(set) && tile == 1) fwd_launch<Conv2FwdT<64, 64, 32, 2>>(set, s);
-      else if (learner_sized(set) && tile == 2) fwd_launch<Conv2FwdT<128, 64, 32, 4>>(set, s);
-      else if (learner_sized(set)) fwd_launch<Conv2FwdT<128, 64, 32, 2>>(set, s);
-      else fwd_launch<Conv2FwdT<128, 32, 32, 4>>(set, s);  // (the actor: 128 x 64 / 64 x 64 measured no better)
+      if (learner_sized(set) && tile == 1) fwd_launch<Conv2FwdT<64, 64, 32, 2>, 0>(set, s);
+      else if (learner_sized(set) && tile == 2) fwd_launch<Conv2FwdT<128, 64, 32, 4>, 0>(set, s);
+      else if (learner_sized(set)) fwd_launch<Conv2FwdT<128, 64, 32, 2>, 0>(set, s);
+      else fwd_launch<Conv2FwdT<128, 32, 32, 4>, 2>(set, s);  // (the actor: 128 x 64 / 64 x 64 measured no better)
       break;
     case 3:  // learner: 64 x 64 (46.7-46.8 us vs 80.6-84.5 for 256 x 64)
-      if (learner_sized(set) && tile == 2) fwd_launch<Conv3FwdT<128, 64, 32, 2>>(set, s);
-      else if (learner_sized(set) && tile == 3) fwd_launch<Conv3FwdT<128, 32, 32, 4>>(set, s);
-      else if (learner_sized(set)) fwd_launch<Conv3FwdT<64, 64, 32, 2>>(set, s);
+      if (learner_sized(set) && tile == 2) fwd_launch<Conv3FwdT<128, 64, 32, 2>, 0>(set, s);
+      else if (learner_sized(set) && tile == 3) fwd_launch<Conv3FwdT<128, 32, 32, 4>, 0>(set, s);
+      else if (learner_sized(set)) fwd_launch<Conv3FwdT<64, 64, 32, 2>, 0>(set, s);
       // the actor: 128 x 64 tiles (98 workgroups for 256 envs beside the learner's forward):
       // 2622.6 vs 2564.0 learner steps/s for 128 x 32 (196), 64 x 64 (196) 2558.2 (one box)
-      else fwd_launch<Conv3FwdT<128, 64, 32, 2>>(set, s);
+      else fwd_launch<Conv3FwdT<128, 64, 32, 2>, 2>(set, s);
       break;
     default: throw std::invalid_argument("f32_conv_fwd_multi: layer must be 1, 2 or 3");
   }
@@ -2059,7 +2255,8 @@ int f32_fc1_splits() { return kFcSplits; }
 
 int f32_fc1_fwd_multi(const F32Set& set, hipStream_t s) {
   check_set(set);
-  fwd_launch<Fc1FwdT<64, 64, 32, 2>>(set, s);
+  if (learner_sized(set)) fwd_launch<Fc1FwdT<64, 64, 32, 2>, 0>(set, s);
+  else fwd_launch<Fc1FwdT<64, 64, 32, 2>, 2>(set, s);
   return kFcSplits;
 }
 

@@ -555,6 +555,8 @@ PYBIND11_MODULE(_apex_hip, m) {
   m.def("f32_stage_split", &f32_stage_split);
   m.def("f32_set_prefetch", &f32_set_prefetch);
   m.def("f32_prefetch", &f32_prefetch);
+  m.def("f32_set_epilogue", &f32_set_epilogue);
+  m.def("f32_epilogue", &f32_epilogue);
   m.def("f32_set_batch_resolve", &f32_set_batch_resolve);
   m.def("f32_batch_resolve", &f32_batch_resolve);
   m.def("f32_fc1_bwd_split", [](uint64_t dz, uint64_t a3, uint64_t wfc1p, uint64_t dy3, uint64_t ws, int B,

@@ -479,6 +479,13 @@ int f32_stage_split();
 // Bit-identical at every depth; read at launch (graphs keep the depth they captured).
 void f32_set_prefetch(int mask);
 int f32_prefetch();
+// GEMM epilogue per launch class: bit 0 = learner-sized forward, bit 1 = backward pairs, bit 2 =
+// small forward; set = the row-owned epilogue (16-byte stores), clear = the element epilogue;
+// unset (< 0) reads APEX_F32_EPILOGUE (default 1: profiles/epilogue_rows.md).  A class's
+// non-default epilogue exists for the default forms at prefetch depth 1 only (a launch throws
+// elsewhere).  Bit-identical results; read at launch (graphs keep the epilogue they captured).
+void f32_set_epilogue(int mask);
+int f32_epilogue();
 // What the draw / the forward of the gradient pass resolve once for the backward: mask = 1 (the
 // ReLU sign bits: written by the conv forwards, read by the input gradients in place of the fp32
 // activations) + 2 (the drawn batch's compact rows: frame ids, action, reward, done); unset reads

@@ -11,6 +11,8 @@ A variant is a comma-separated list of overrides ('-' = the defaults):
                  + 4 x (D - 1) of the backward pairs + 16 x (D - 1) of the actor's small launches
   br=MASK        APEX_F32_BATCH_RESOLVE: 1 = ReLU sign bits for the input gradients + 2 = the drawn
                  batch's compact rows (default 1; 0 = the fp32 masks and the idx lookups)
+  ep=MASK        APEX_F32_EPILOGUE: 1 = row-owned GEMM epilogue of the learner-sized forward + 2 = of
+                 the backward pairs + 4 = of the small forward launches (default 1)
   env:NAME=VAL   any other environment variable
   arg:--flag[=VAL]  a bench.py flag (e.g. arg:--actor-at=loss)
 e.g. ``python scripts/ab/apex_engine_ab.py - ss=4 ss=8 ss=8,arg:--actor-at=loss``.
@@ -40,6 +42,8 @@ def run(variant: str, steps: int, warmup: int, timeout: float) -> float:
             env["APEX_F32_PREFETCH"] = item[3:]
         elif item.startswith("br="):
             env["APEX_F32_BATCH_RESOLVE"] = item[3:]
+        elif item.startswith("ep="):
+            env["APEX_F32_EPILOGUE"] = item[3:]
         elif item.startswith("env:"):
             k, v = item[4:].split("=", 1)
             env[k] = v

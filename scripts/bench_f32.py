@@ -8,7 +8,8 @@ three-term split; the percentage is of the 157.3 TF fp32 MFMA peak, for comparis
 us/launch and achieved TFLOP/s (157.3 TF = fp32 MFMA peak); ``--graph 0`` launches
 eagerly (for rocprofv3 --pmc, one dispatch per launch).  ``--prefetch D`` runs every GEMM at
 prefetch depth D (1..3 k-blocks of operand loads in flight), ``--stage-split MASK`` in the
-given GEMM forms (APEX_F32_STAGE_SPLIT's mask), ``--sign-bits 1`` with the ReLU sign bits (the conv
+given GEMM forms (APEX_F32_STAGE_SPLIT's mask), ``--epilogue MASK`` with the row-owned (set bit) or
+element epilogue per launch class (APEX_F32_EPILOGUE's mask), ``--sign-bits 1`` with the ReLU sign bits (the conv
 forwards write them for problem 0, the input gradients read them in place of the fp32 masks)."""
 import argparse
 import json
@@ -40,6 +41,7 @@ ap.add_argument("--wgrad-targets", default="", help="extra conv2/conv3 backward 
 ap.add_argument("--prefetch", type=int, default=0, choices=[0, 1, 2, 3],
                 help="GEMM prefetch depth of every launch class (0: the defaults / APEX_F32_PREFETCH)")
 ap.add_argument("--stage-split", type=int, default=-1, help="GEMM form mask (-1: the defaults)")
+ap.add_argument("--epilogue", type=int, default=-1, help="GEMM epilogue mask (-1: the defaults)")
 ap.add_argument("--sign-bits", type=int, default=0, choices=[0, 1], help="ReLU sign bits written / read (see above)")
 a = ap.parse_args()
 dev = torch.device("cuda")
@@ -48,6 +50,8 @@ if a.prefetch:
     hip.f32_set_prefetch((a.prefetch - 1) * (1 + 4 + 16))
 if a.stage_split >= 0:
     hip.f32_set_stage_split(a.stage_split)
+if a.epilogue >= 0:
+    hip.f32_set_epilogue(a.epilogue)
 B, A = a.B, 18
 m = DuelingDQN.from_shapes((4, 84, 84), A).to(dev)
 m.flatten_parameters()
