@@ -56,6 +56,7 @@ from .. import envs, ops
 from ..algo.schedules import actor_epsilon
 from ..models.aql import AQL
 from ..models.aql_fused import FusedAQL
+from .evaluation import GreedyRollouts, RolloutBuffers, RolloutEvaluation
 from .hbm_replay import tree_level_sizes
 
 ENV_KINDS = {"BipedalWalker-v3": 0, "CartPole-v0": 1, "CartPole-v1": 1, "Pendulum-v0": 2, "Pendulum-v1": 2}
@@ -492,7 +493,7 @@ class AQLLearner:
                 "steps": int(self.step_ctr.item())}
 
 
-class AQLEngine:
+class AQLEngine(GreedyRollouts):
     """Actors + replay + learner of AQL_dis on one GPU (see module docstring)."""
 
     def __init__(self, cfg: AQLEngineConfig, device: str | torch.device = "cuda"):
@@ -622,7 +623,6 @@ class AQLEngine:
         self.eval_limit = int(getattr(self.host_env, "_max_episode_steps", None) or 10_000)
         self.eval_net = self.learner.fused_on._net(noisy=False)
         self._eval = None
-        self._rollout = None
 
     @staticmethod
     def _s() -> int:
@@ -824,10 +824,6 @@ class AQLEngine:
         return self.E
 
     # ------------------------------------------------------------------ evaluation
-    def _eval_seed(self, seed: int | None) -> int:
-        sd = (self.cfg.seed * 7919 + 0xE7A1 + self.learner_steps) if seed is None else int(seed)
-        return sd & 0xFFFFFFFFFFFF
-
     def evaluate(self, episodes: int = 10, seed: int | None = None, max_episode_steps: int | None = None) -> list[float]:
         """Greedy returns of ``episodes`` episodes, one env each, with the ONLINE network in eval
         mode (NoisyNet means: the reference's ``q.eval()`` evaluation branch), stepwise: per env
@@ -893,29 +889,20 @@ class AQLEngine:
                 break
         return ret.tolist()
 
-    def rollout_evaluate(self, episodes: int = 10, seed: int | None = None,
-                         max_episode_steps: int | None = None) -> list[float]:
-        """``evaluate()`` in one launch: ``aql_rollout`` plays the ``episodes`` greedy episodes
-        from reset to their first done inside one kernel on the current stream, then one
-        read-back.  Same contract, same default seed and, for the same seed, the same floats.
-        The online weights are read in place (the caller's stream order protects them)."""
-        n = int(episodes)
-        limit = int(self.eval_limit if max_episode_steps is None else max_episode_steps)
-        if self._rollout is None or self._rollout.n != n:
-            self._rollout = AQLRolloutBuffers(self, self.eval_net, n)
-        self._rollout.launch(self._eval_seed(seed), limit)
-        return self._rollout.returns.tolist()
+    # ---- GreedyRollouts: ``rollout_evaluate()`` is ``evaluate()`` in one ``aql_rollout`` launch
+    _eval_steps = property(lambda self: self.learner_steps)
+    _eval_limit = property(lambda self: self.eval_limit)
+
+    def _make_rollout(self, n: int) -> AQLRolloutBuffers:
+        return AQLRolloutBuffers(self, self.eval_net, n)
 
 
-class AQLRolloutBuffers:
+class AQLRolloutBuffers(RolloutBuffers):
     """Device outputs of ``aql_rollout`` for ``n`` episodes of one net handle + the launch."""
 
     def __init__(self, engine: AQLEngine, net, n: int):
-        self.engine, self.hip, self.net, self.n = engine, engine.hip, net, int(n)
-        dev = engine.device
-        self.returns = torch.zeros(self.n, dtype=torch.float32, device=dev)
-        self.lengths = torch.zeros(self.n, dtype=torch.int32, device=dev)
-        self.ended = torch.zeros(self.n, dtype=torch.int32, device=dev)
+        super().__init__(n, engine.device)
+        self.engine, self.hip, self.net = engine, engine.hip, net
 
     def descriptor(self, seed: int, max_steps: int, trace: dict | None = None, **over) -> dict:
         """The launch's arguments: seeds as ``AQLEngine.evaluate`` derives them from the env
@@ -938,78 +925,26 @@ class AQLRolloutBuffers:
                              torch.cuda.current_stream().cuda_stream)
 
 
-class AQLEvaluator:
-    """Greedy evaluation beside training: ``launch()`` snapshots the online flat parameters on
-    the training stream (``copy_f32``; no noise buffers -- evaluation uses the NoisyNet means)
-    and plays the episodes with ``aql_rollout`` on a side stream; training goes on in place and
-    ``poll()`` / ``wait()`` hand the result over once it has landed in pinned host memory.
-    While a launch is in flight a further ``launch()`` does nothing (the snapshot may still be
-    read by the running kernel): evaluations conflate, as the reference's evaluator does.
-    All launches are eager, issued between graph replays; no captured graph gains a node."""
+class AQLEvaluator(RolloutEvaluation):
+    """Greedy evaluation beside training (:class:`~apex_amd.engine.evaluation.SideStreamEvaluation`):
+    ``launch()`` snapshots the online flat parameters on the training stream (``copy_f32``; no
+    noise buffers -- evaluation uses the NoisyNet means) and plays the episodes with
+    ``aql_rollout`` on a side stream; a result holds their ``returns``, ``lengths`` and ``ended``
+    flags."""
 
-    def __init__(self, engine: AQLEngine, episodes: int = 10, max_episode_steps: int | None = None):
-        self.engine = engine
-        self.hip, self.device = engine.hip, engine.device
-        self.n = int(episodes)
-        self.limit = int(engine.eval_limit if max_episode_steps is None else max_episode_steps)
-        cfg = engine.cfg
+    def __init__(self, engine: AQLEngine, episodes: int = 10, max_episode_steps: int | None = None, **side):
+        self.hip, self.n = engine.hip, int(episodes)
+        cfg, dev = engine.cfg, engine.device
         self.model = AQL(env=engine.host_env, propose_sample=cfg.propose_sample, uniform_sample=cfg.uniform_sample,
-                         action_var=cfg.action_var, device=self.device).to(self.device)   # the snapshot
+                         action_var=cfg.action_var, device=dev).to(dev)   # the snapshot
         for p in self.model.parameters():
             p.requires_grad_(False)
         self.flat = flatten_module_params(self.model)
         assert self.flat.numel() == engine.learner.P
         self.fused = FusedAQL(self.model)
-        self.stream = torch.cuda.Stream(device=self.device)
-        self.ro = AQLRolloutBuffers(engine, self.fused._net(noisy=False), self.n)
-        self.host = {"returns": torch.zeros(self.n, dtype=torch.float32).pin_memory(),
-                     "lengths": torch.zeros(self.n, dtype=torch.int32).pin_memory(),
-                     "ended": torch.zeros(self.n, dtype=torch.int32).pin_memory()}
-        self.snapshot_taken = torch.cuda.Event()
-        self.results_landed = torch.cuda.Event()
-        self._pending = False   # a launch whose result is still on its way to the host
-        self._tag = None
-        self._done = collections.deque()   # landed results not yet handed over
+        ro = AQLRolloutBuffers(engine, self.fused._net(noisy=False), self.n)
+        super().__init__(engine, ro, engine.eval_limit if max_episode_steps is None else max_episode_steps, **side)
 
-    def launch(self, seed: int | None = None, tag=None) -> bool:
-        """Start one evaluation of the online weights as they are at this point of the current
-        stream.  ``False`` (and nothing done) while the previous one has not landed."""
-        if self._pending:
-            if not self.results_landed.query():
-                return False
-            self._harvest()  # the pinned buffers are about to be reused
-        eng = self.engine
-        sd = eng._eval_seed(seed)
-        self.hip.copy_f32(self.flat.data_ptr(), eng.learner.flat.data_ptr(), eng.learner.P,
-                          torch.cuda.current_stream().cuda_stream)
-        self.snapshot_taken.record()
-        with torch.cuda.stream(self.stream):
-            self.stream.wait_event(self.snapshot_taken)
-            self.ro.launch(sd, self.limit)
-            for k, hbuf in self.host.items():
-                hbuf.copy_(getattr(self.ro, k), non_blocking=True)
-            self.results_landed.record()
-        self._pending, self._tag = True, tag
-        return True
-
-    def _harvest(self) -> None:
-        self._pending = False
-        self._done.append({"tag": self._tag, "returns": self.host["returns"].tolist(),
-                           "lengths": self.host["lengths"].tolist(), "ended": self.host["ended"].tolist()})
-
-    def poll(self) -> dict | None:
-        """The oldest finished evaluation not yet handed over (each exactly once), or ``None``."""
-        if self._pending and self.results_landed.query():
-            self._harvest()
-        return self._done.popleft() if self._done else None
-
-    def wait(self) -> dict | None:
-        """As ``poll()``, but blocks until the launch in flight has landed: on the results event
-        only, never on the device.  ``None`` if nothing was launched."""
-        if self._done:
-            return self._done.popleft()
-        if not self._pending:
-            return None
-        self.results_landed.synchronize()
-        self._harvest()
-        return self._done.popleft()
+    def _snapshot(self) -> None:
+        L = self.engine.learner
+        self.hip.copy_f32(self.flat.data_ptr(), L.flat.data_ptr(), L.P, torch.cuda.current_stream().cuda_stream)

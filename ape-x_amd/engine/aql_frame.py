@@ -49,7 +49,8 @@ from .. import envs, ops
 from ..algo.schedules import cosine_lr
 from ..models.aql import AQL
 from ..utils.checkpoint import save_model, save_train_state
-from .aql import ENV_KINDS, AQLEngine, AQLEngineConfig, AQLLearner, AQLReplay, AQLRolloutBuffers
+from .aql import ENV_KINDS, AQLEngine, AQLEngineConfig, AQLLearner, AQLReplay
+from .evaluation import GreedyRollouts
 
 MAX_T = 1024           # candidates per state (aql_frame / aql_rollout: one LDS row)
 MAX_CAND_FLOATS = 4608  # T * (adim + 1): the candidate set and its Q row in LDS
@@ -142,7 +143,7 @@ class AQLFrameConfig:
                                exact_mass=self.exact_mass, fused=self.fused, seed=self.seed)
 
 
-class AQLFrameEngine:
+class AQLFrameEngine(GreedyRollouts):
     """``AQL.py`` on one GPU: ``frame()`` is one loop iteration of the reference trainer."""
 
     def __init__(self, cfg: AQLFrameConfig, device: str | torch.device = "cuda"):
@@ -237,7 +238,6 @@ class AQLFrameEngine:
         self._ep_read = 0
         self.eval_limit = int(getattr(self.host_env, "_max_episode_steps", None) or 10_000)
         self._eval = None
-        self._rollout = None
         h.aql_env_reset(self.env, self._s())
 
     @staticmethod
@@ -408,24 +408,13 @@ class AQLFrameEngine:
         return save_model(self.model, path)
 
     # ------------------------------------------------------------------ evaluation
-    def _eval_seed(self, seed: int | None) -> int:
-        sd = (self.cfg.seed * 7919 + 0xE7A1 + self.learn_steps) if seed is None else int(seed)
-        return sd & 0xFFFFFFFFFFFF
-
     # the stepwise greedy evaluator of the GPU AQL engine (eval-mode online net, an evaluation
-    # shard of its own): it only touches the attributes this engine shares with AQLEngine
+    # shard of its own) and its rollout buffers on the online net's eval handle: they only touch
+    # the attributes this engine shares with AQLEngine
     evaluate = AQLEngine.evaluate
-
-    def rollout_evaluate(self, episodes: int = 10, seed: int | None = None,
-                         max_episode_steps: int | None = None) -> list[float]:
-        """``evaluate()`` in one ``aql_rollout`` launch on the online net's eval handle: same
-        contract, same default seed and, for the same seed, the same floats."""
-        n = int(episodes)
-        limit = int(self.eval_limit if max_episode_steps is None else max_episode_steps)
-        if self._rollout is None or self._rollout.n != n:
-            self._rollout = AQLRolloutBuffers(self, self.eval_net, n)
-        self._rollout.launch(self._eval_seed(seed), limit)
-        return self._rollout.returns.tolist()
+    _eval_steps = property(lambda self: self.learn_steps)
+    _eval_limit = AQLEngine._eval_limit
+    _make_rollout = AQLEngine._make_rollout
 
 
 def host_epsilons(seed: int, n: int, eps_hi: float = 0.5, eps_lo: float = 0.05, eps_p: float = 0.1,

@@ -32,6 +32,7 @@ from dataclasses import dataclass
 import torch
 
 from .. import ops
+from .evaluation import GreedyRollouts
 from .graphs import capture_graph, warm_up
 from .hbm_replay import HBMReplay
 from .shard import ACT_SEED_XOR
@@ -89,7 +90,7 @@ class DQNEngineConfig:
         return self.batch_size // self.n_envs
 
 
-class DQNFrameEngine:
+class DQNFrameEngine(GreedyRollouts):
     """``DQN.py`` on one GPU: ``frame()`` is one loop iteration of the reference trainer."""
 
     def __init__(self, cfg: DQNEngineConfig, device: str | torch.device = "cuda"):
@@ -185,7 +186,6 @@ class DQNFrameEngine:
         self.frames = 0         # host mirror of ``t``
         self.learn_steps = 0
         self._graph = None
-        self._rollout = None
         h.vec_classic_reset(self.env, self.t.data_ptr(), self.new_frame.data_ptr(), self.hist.data_ptr(),
                             self.ep_log.data_ptr(), self._stream())
 
@@ -284,19 +284,11 @@ class DQNFrameEngine:
         """Reference-format ``state_dict`` of the online network."""
         return save_state_dict(self.model, path)
 
-    def _eval_seed(self, seed: int | None) -> int:
-        sd = (self.cfg.seed * 7919 + 0xE7A1 + self.frames) if seed is None else int(seed)
-        return sd & 0xFFFFFFFFFFFF
+    # ---- GreedyRollouts: ``rollout_evaluate()`` is one ``vec_rollout`` launch + one read-back
+    _eval_steps = property(lambda self: self.frames)
+    _eval_limit = property(lambda self: self.limit)
 
-    def rollout_evaluate(self, episodes: int = 10, seed: int | None = None,
-                         max_episode_steps: int | None = None) -> list[float]:
-        """Greedy returns of ``episodes`` episodes of the online weights: one ``vec_rollout``
-        launch on the current stream + one read-back.  Nothing is written to the replay."""
-        n = int(episodes)
-        limit = int(self.limit if max_episode_steps is None else max_episode_steps)
-        if self._rollout is None or self._rollout.n != n:
-            self._rollout = VecRolloutBuffers(self.hip, self.net, self.kind, self.obs_dim, n, self.device)
-        self._rollout.launch(self._eval_seed(seed), limit)
-        return self._rollout.returns.tolist()
+    def _make_rollout(self, n: int) -> VecRolloutBuffers:
+        return VecRolloutBuffers(self.hip, self.net, self.kind, self.obs_dim, n, self.device)
 
-    evaluate = rollout_evaluate
+    evaluate = GreedyRollouts.rollout_evaluate

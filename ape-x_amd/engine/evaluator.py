@@ -23,13 +23,12 @@ buffer as ``run(k)`` does, so the two may alternate.  It also fills ``ep_ring`` 
 """
 from __future__ import annotations
 
-import collections
-
 import torch
 
 from .. import ops
 from ..models.dqn import DuelingDQN
 from .actor_shard import ENV_STATE_STRIDE
+from .evaluation import SideStreamEvaluation
 from .graphs import capture_graph
 from .hbm_replay import FRAME_BYTES
 
@@ -241,70 +240,31 @@ class GPUEvaluator:
         host["running"].copy_(self.env_state[:, 25:27], non_blocking=True)  # S_EPRET, S_EPLEN
 
 
-class AtariEvaluator:
-    """Greedy evaluation beside training.  ``launch()`` snapshots the source weights on the
-    current (training) stream into the evaluator's own copies and plays ``n_steps`` greedy
-    steps with ``GPUEvaluator.rollout`` on a side stream; the finished episodes and the running
-    (return, length) land in pinned host memory and ``poll()`` / ``wait()`` hand each result
-    over exactly once.  While a launch is in flight a further ``launch()`` does nothing (the
-    snapshot may still be read by the running kernel): evaluations conflate.  The training
-    stream never waits on the side stream; all launches are eager, between graph replays.
-
-    ``stream`` / ``event`` / ``stream_ctx`` default to ``torch.cuda``'s (host tests pass fakes)."""
+class AtariEvaluator(SideStreamEvaluation):
+    """Greedy evaluation beside training (:class:`SideStreamEvaluation`).  ``launch()`` snapshots
+    the source weights into the evaluator's own copies and plays ``n_steps`` greedy steps with
+    ``GPUEvaluator.rollout`` on the side stream; a result holds the episodes finished since the
+    previous one and the running (return, length) of every env."""
 
     def __init__(self, evaluator, stream=None, event=None, stream_ctx=None):
+        super().__init__(evaluator.device, stream, event, stream_ctx)
         self.ev = evaluator
-        self.stream = torch.cuda.Stream(device=evaluator.device) if stream is None else stream
-        self._ctx = torch.cuda.stream if stream_ctx is None else stream_ctx
-        make = torch.cuda.Event if event is None else event
-        self.snapshot_taken, self.results_landed = make(), make()
         self.host = evaluator.host_results()
         self._seen = torch.zeros_like(self.host["counts"])
-        self._pending, self._tag = False, None
-        self._done = collections.deque()
-        self.launches = 0
 
     def launch(self, src_flat, src_net, n_steps: int, tag=None) -> bool:
         """Start one evaluation chunk of the source weights as they are at this point of the
         current stream.  ``False`` (and nothing done) while the previous one has not landed."""
-        if self._pending:
-            if not self.results_landed.query():
-                return False
-            self._harvest()  # the pinned buffers are about to be reused
-        self.ev.snapshot(src_flat, src_net)
-        self.snapshot_taken.record()
-        with self._ctx(self.stream):
-            self.stream.wait_event(self.snapshot_taken)
+        def play():
             self.ev.rollout(n_steps)
             self.ev.copy_results(self.host)
-            self.results_landed.record()
-        self._pending, self._tag = True, tag
-        self.launches += 1
-        return True
 
-    def _harvest(self) -> None:
-        self._pending = False
+        return self._launch(tag, lambda: self.ev.snapshot(src_flat, src_net), play)
+
+    def _result(self) -> dict:
         h = self.host
         counts = h["counts"].clone()
         eps = GPUEvaluator.ring_episodes(h["ring"], counts, self._seen)
         self._seen = counts
-        self._done.append({"tag": self._tag, "episodes": eps, "total_episodes": int(counts.sum()),
-                           "running_return": h["running"][:, 0].tolist(),
-                           "running_length": h["running"][:, 1].tolist()})
-
-    def poll(self) -> dict | None:
-        """The oldest landed result not yet handed over (each exactly once), or ``None``."""
-        if self._pending and self.results_landed.query():
-            self._harvest()
-        return self._done.popleft() if self._done else None
-
-    def wait(self) -> dict | None:
-        """As ``poll()``, but blocks until the launch in flight has landed: on the results event
-        only, never on the device.  ``None`` if nothing was launched."""
-        if self._done:
-            return self._done.popleft()
-        if not self._pending:
-            return None
-        self.results_landed.synchronize()
-        self._harvest()
-        return self._done.popleft()
+        return {"episodes": eps, "total_episodes": int(counts.sum()),
+                "running_return": h["running"][:, 0].tolist(), "running_length": h["running"][:, 1].tolist()}

@@ -34,7 +34,6 @@ engine's and are not offered here.
 """
 from __future__ import annotations
 
-import collections
 import copy
 from dataclasses import dataclass
 
@@ -42,6 +41,7 @@ import torch
 
 from .. import ops
 from ..models.dqn import DuelingDQN
+from .evaluation import GreedyRollouts, RolloutBuffers, RolloutEvaluation
 from .graphs import capture_graph, warm_up
 from .hbm_replay import HBMReplay
 from .shard import NStepShard
@@ -326,7 +326,7 @@ class MLPDQNLearner:
         return {"loss": float(self.loss.item()), "grad_norm_l2": n[0], "grad_norm": ref, "clip": n[2], "lr": n[3]}
 
 
-class VectorApexEngine:
+class VectorApexEngine(GreedyRollouts):
     """Actor shard + observation-ring replay + MLP learner on one GPU."""
 
     def __init__(self, cfg: VectorEngineConfig, device: str | torch.device = "cuda"):
@@ -349,7 +349,6 @@ class VectorApexEngine:
         self.actor_steps = 0
         self._g_actor = self._g_learn = None
         self._eval = None
-        self._rollout = None
 
     # ------------------------------------------------------------------ phases
     def publish_params(self) -> None:
@@ -441,9 +440,8 @@ class VectorApexEngine:
                                        ev["actions"].data_ptr())
             self._eval = ev
         ev = self._eval
-        sd = (self.cfg.seed * 7919 + 0xE7A1 + self.learn_steps) if seed is None else int(seed)
         env = h.make_vec_env(self.kind, n, self.obs_dim, ev["ring"].shape[0], self.limit, ev["state"].data_ptr(),
-                             ev["ring"].data_ptr(), sd & 0xFFFFFFFFFFFF)
+                             ev["ring"].data_ptr(), self._eval_seed(seed))
         s = torch.cuda.current_stream().cuda_stream
         ev["counter"].zero_()
         h.vec_classic_reset(env, ev["counter"].data_ptr(), ev["new_frame"].data_ptr(), ev["hist"].data_ptr(),
@@ -463,34 +461,20 @@ class VectorApexEngine:
                 break
         return first.tolist()
 
-    def _eval_seed(self, seed: int | None) -> int:
-        sd = (self.cfg.seed * 7919 + 0xE7A1 + self.learn_steps) if seed is None else int(seed)
-        return sd & 0xFFFFFFFFFFFF
+    # ---- GreedyRollouts: ``rollout_evaluate()`` is ``evaluate()`` in one ``vec_rollout`` launch
+    _eval_steps = property(lambda self: self.learn_steps)
+    _eval_limit = property(lambda self: self.limit)
 
-    def rollout_evaluate(self, episodes: int = 10, seed: int | None = None,
-                         max_episode_steps: int | None = None) -> list[float]:
-        """``evaluate()`` in one launch: ``vec_rollout`` plays the ``episodes`` greedy episodes
-        from reset to their first done inside one kernel on the current stream, then one
-        read-back.  Same contract, same default seed and, for the same seed, the same returns
-        bit for bit.  The online weights are read in place (the caller's stream order protects
-        them, as in ``evaluate()``)."""
-        n = int(episodes)
-        limit = int(self.limit if max_episode_steps is None else max_episode_steps)
-        if self._rollout is None or self._rollout.n != n:
-            self._rollout = VecRolloutBuffers(self.hip, self.learner.net, self.kind, self.obs_dim, n, self.device)
-        ro = self._rollout
-        ro.launch(self._eval_seed(seed), limit)
-        return ro.returns.tolist()
+    def _make_rollout(self, n: int) -> VecRolloutBuffers:
+        return VecRolloutBuffers(self.hip, self.learner.net, self.kind, self.obs_dim, n, self.device)
 
 
-class VecRolloutBuffers:
+class VecRolloutBuffers(RolloutBuffers):
     """Device outputs of ``vec_rollout`` for ``n`` episodes of one net + the launch."""
 
     def __init__(self, hip, net, kind: int, obs_dim: int, n: int, device):
-        self.hip, self.net, self.kind, self.obs_dim, self.n = hip, net, int(kind), int(obs_dim), int(n)
-        self.returns = torch.zeros(self.n, dtype=torch.float32, device=device)
-        self.lengths = torch.zeros(self.n, dtype=torch.int32, device=device)
-        self.ended = torch.zeros(self.n, dtype=torch.int32, device=device)
+        super().__init__(n, device)
+        self.hip, self.net, self.kind, self.obs_dim = hip, net, int(kind), int(obs_dim)
 
     def launch(self, seed: int, max_steps: int, trace: dict | None = None) -> None:
         """One ``vec_rollout`` launch on the current stream.  ``trace``: the tensors
@@ -503,75 +487,23 @@ class VecRolloutBuffers:
         self.hip.vec_rollout(self.hip.make_vec_rollout(self.net, d), torch.cuda.current_stream().cuda_stream)
 
 
-class VectorEvaluator:
-    """Greedy evaluation beside training: ``launch()`` snapshots the online weights on the
-    training stream and plays the episodes with ``vec_rollout`` on a side stream; training goes
-    on in place and ``poll()`` / ``wait()`` hand the result over once it has landed in pinned
-    host memory.  While a launch is in flight a further ``launch()`` does nothing (its
-    snapshot buffer may still be read by the running kernel): evaluations conflate, as the
-    reference's evaluator process does.  All launches are eager, issued between graph replays;
-    no captured graph gains a branch."""
+class VectorEvaluator(RolloutEvaluation):
+    """Greedy evaluation beside training (:class:`~apex_amd.engine.evaluation.SideStreamEvaluation`):
+    ``launch()`` snapshots the online weights on the training stream (``copy_f32``) and plays the
+    episodes with ``vec_rollout`` on a side stream; a result holds their ``returns``, ``lengths``
+    and ``ended`` flags."""
 
-    def __init__(self, engine: VectorApexEngine, episodes: int = 10, max_episode_steps: int | None = None):
-        self.engine = engine
-        self.hip, self.device = engine.hip, engine.device
-        self.n = int(episodes)
-        self.limit = int(engine.limit if max_episode_steps is None else max_episode_steps)
+    def __init__(self, engine: VectorApexEngine, episodes: int = 10, max_episode_steps: int | None = None,
+                 **side):
+        self.hip, self.n = engine.hip, int(episodes)
         self.model = copy.deepcopy(engine.learner.model)   # the snapshot
         self.model._flat = None
         self.flat = self.model.flatten_parameters()
         for p in self.model.parameters():
             p.requires_grad_(False)
-        self.stream = torch.cuda.Stream(device=self.device)
-        self.ro = VecRolloutBuffers(self.hip, vec_net(self.hip, self.model), engine.kind, engine.obs_dim, self.n,
-                                    self.device)
-        self.host = {"returns": torch.zeros(self.n, dtype=torch.float32).pin_memory(),
-                     "lengths": torch.zeros(self.n, dtype=torch.int32).pin_memory(),
-                     "ended": torch.zeros(self.n, dtype=torch.int32).pin_memory()}
-        self.snapshot_taken = torch.cuda.Event()
-        self.results_landed = torch.cuda.Event()
-        self._pending = False   # a launch whose result is still on its way to the host
-        self._tag = None
-        self._done = collections.deque()   # landed results not yet handed over
+        ro = VecRolloutBuffers(self.hip, vec_net(self.hip, self.model), engine.kind, engine.obs_dim, self.n,
+                               engine.device)
+        super().__init__(engine, ro, engine.limit if max_episode_steps is None else max_episode_steps, **side)
 
-    def launch(self, seed: int | None = None, tag=None) -> bool:
-        """Start one evaluation of the online weights as they are at this point of the current
-        stream.  ``False`` (and nothing done) while the previous one has not landed."""
-        if self._pending:
-            if not self.results_landed.query():
-                return False
-            self._harvest()  # the pinned buffers are about to be reused
-        eng = self.engine
-        sd = eng._eval_seed(seed)
-        eng.learner.copy_params_to(self.flat)
-        self.snapshot_taken.record()
-        with torch.cuda.stream(self.stream):
-            self.stream.wait_event(self.snapshot_taken)
-            self.ro.launch(sd, self.limit)
-            for k, h in self.host.items():
-                h.copy_(getattr(self.ro, k), non_blocking=True)
-            self.results_landed.record()
-        self._pending, self._tag = True, tag
-        return True
-
-    def _harvest(self) -> None:
-        self._pending = False
-        self._done.append({"tag": self._tag, "returns": self.host["returns"].tolist(),
-                           "lengths": self.host["lengths"].tolist(), "ended": self.host["ended"].tolist()})
-
-    def poll(self) -> dict | None:
-        """The oldest finished evaluation not yet handed over (each exactly once), or ``None``."""
-        if self._pending and self.results_landed.query():
-            self._harvest()
-        return self._done.popleft() if self._done else None
-
-    def wait(self) -> dict | None:
-        """As ``poll()``, but blocks until the launch in flight has landed: on the results event
-        only, never on the device.  ``None`` if nothing was launched."""
-        if self._done:
-            return self._done.popleft()
-        if not self._pending:
-            return None
-        self.results_landed.synchronize()
-        self._harvest()
-        return self._done.popleft()
+    def _snapshot(self) -> None:
+        self.engine.learner.copy_params_to(self.flat)

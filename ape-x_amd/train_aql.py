@@ -363,10 +363,8 @@ def _loop(a, eng: AQLEngine, iterate, envs_per_iter: int, episodes, start: int, 
                     writer.add_scalar("evaluator/episode_reward", r, eng.learner_steps)
                 last["greedy_mean_return"] = float(np.mean(ret))
             if asyn is not None:
-                res = None  # the newest evaluation that has landed (last iteration: wait out the one in flight)
-                while (r := asyn.wait() if final else asyn.poll()) is not None:
-                    res = r
-                if res is not None:
+                # the newest evaluation that has landed (last iteration: wait out the one in flight)
+                if (res := asyn.latest(block=final)) is not None:
                     _report_async(res, last, writer, eng)
             print(json.dumps(last), flush=True)
             if jl:

@@ -125,10 +125,8 @@ def train(a) -> dict:
                 g = eng.rollout_evaluate(a.eval_episodes) if mode == "rollout" else eng.evaluate(a.eval_episodes)
                 last["greedy_mean_return"] = sum(g) / len(g)
             if asyn is not None:
-                res = None  # the newest evaluation that has landed (after the last step: the final one)
-                while (r := asyn.wait() if final else asyn.poll()) is not None:
-                    res = r
-                if res is not None:
+                # the newest evaluation that has landed (after the last step: the final one)
+                if (res := asyn.latest(block=final)) is not None:
                     last["greedy_mean_return"] = sum(res["returns"]) / len(res["returns"])
                     last["greedy_step"] = res["tag"]
             print(json.dumps(last), flush=True)
