@@ -26,9 +26,11 @@ ranged ``host_env_ingest_range`` launch as soon as that worker is done, while th
 are still emulating.  A range launch writes exactly what the whole launch writes for its envs, so
 the banked, the whole and the in-process paths fill the ring and the replay identically.
 
+Greedy evaluation on further host emulators beside training (the reference's ``eval.py``) is
+:mod:`apex_amd.engine.host_eval`; it shares :class:`Ingest` and touches nothing here.
+
 Out of scope here: double-banked env groups (stepping one half of the envs while the other
-half's forward runs), a device evaluator for host envs, and the multi-GPU topologies
-(``parallel/``, ``engine/central.py``).
+half's forward runs) and the multi-GPU topologies (``parallel/``, ``engine/central.py``).
 """
 from __future__ import annotations
 

@@ -16,10 +16,14 @@ Banked form: ``step_async(actions)`` starts one agent step on every worker and
 ``wait_bank() -> (b, reward[e0:e1], done[e0:e1])`` hands back each bank exactly once per step, in
 completion order (the slices are views of the shared block, valid until the next step starts) --
 a consumer can ship bank ``b`` to the GPU while the other workers are still emulating.
+``poll_bank()`` is ``wait_bank()`` with a zero wait: the next finished bank, or ``None`` at once
+while every pending worker is still stepping (same exactly-once bookkeeping, same failure handling).
+``max_episode_steps`` is handed to every worker's ``RawAtariVector`` (0 = no cap).
 
 Failure handling: no wait is unbounded.  A worker that raises, exits or stays silent past
 ``timeout`` seconds makes the call raise ``RuntimeError`` naming the worker and its env range (an
-exception in the child arrives with its traceback text); the pool is then broken, every later
+exception in the child arrives with its traceback text; of several failed workers the lowest-numbered
+one is named, whatever the order their failures arrived in); the pool is then broken, every later
 call raises, and ``close()`` still returns.  ``close()`` is idempotent, runs from ``__exit__`` and
 from a finalizer, stops the workers (stop message, then ``terminate``, then ``kill``, each with a
 short join) and unlinks the shared block.
@@ -57,6 +61,7 @@ _THREAD_VARS = ("OMP_NUM_THREADS", "OPENBLAS_NUM_THREADS", "MKL_NUM_THREADS", "N
                 "VECLIB_MAXIMUM_THREADS", "BLIS_NUM_THREADS")
 _START_TIMEOUT = 60.0   # floor of the bound on worker start-up (interpreter + imports + env construction)
 _JOIN = 0.5             # the "short join" after stop / terminate / kill
+_BLAME = 2.0            # grace for lower-numbered workers to report a failure of their own (see _blame)
 _env_lock = threading.Lock()
 _WORKER = None
 
@@ -109,7 +114,7 @@ def _resolve(factory):
     return getattr(importlib.import_module(mod), fn)
 
 
-def _worker_main(conn, w, e0, e1, env_id, spec, seed, factory):
+def _worker_main(conn, w, e0, e1, env_id, spec, seed, factory, max_episode_steps=0):
     """One worker: build the bank's vector, report its geometry, attach the shared block, then
     serve reset / step / seed / noops until a stop message or the parent's end of the pipe closes."""
     global _WORKER
@@ -120,7 +125,7 @@ def _worker_main(conn, w, e0, e1, env_id, spec, seed, factory):
     try:
         try:
             make_fn = _resolve(factory)
-            vec = RawAtariVector([make_fn(env_id) for _ in range(e0, e1)], spec)
+            vec = RawAtariVector([make_fn(env_id) for _ in range(e0, e1)], spec, max_episode_steps)
             if seed is not None:
                 vec.seed(seed + e0)
             conn.send(("ready", tuple(vec.raw_shape), int(vec.n_actions)))
@@ -211,8 +216,12 @@ _parked = []   # blocks unlinked while a caller still held a view of them (kept 
 
 class ProcRawAtariVector:
     def __init__(self, env_id: str, n_envs: int, spec: PreprocessSpec = PreprocessSpec(), workers: int = 2,
-                 seed: int | None = None, factory: str | None = None, timeout: float = 60.0):
+                 seed: int | None = None, factory: str | None = None, timeout: float = 60.0,
+                 max_episode_steps: int = 0):
         n_envs, workers = int(n_envs), int(workers)
+        if int(max_episode_steps) < 0:
+            raise ValueError("max_episode_steps must be >= 0 (0 = no cap)")
+        self.max_episode_steps = int(max_episode_steps)
         self.banks = bank_ranges(n_envs, workers)   # (ValueError before any process starts)
         if factory is not None and (":" not in factory or not all(factory.partition(":")[::2])):
             raise ValueError(f"factory must be 'module:function', got {factory!r}")
@@ -239,7 +248,8 @@ class ProcRawAtariVector:
                 for w, (e0, e1) in enumerate(self.banks):
                     ours, theirs = ctx.Pipe(duplex=True)
                     p = ctx.Process(target=_worker_main, name=f"apex-env-worker-{w}", daemon=True,
-                                    args=(theirs, w, e0, e1, self.env_id, self.spec, seed, factory))
+                                    args=(theirs, w, e0, e1, self.env_id, self.spec, seed, factory,
+                                          self.max_episode_steps))
                     p.start()
                     theirs.close()
                     self._procs.append(p)
@@ -286,35 +296,70 @@ class ProcRawAtariVector:
         except (OSError, ValueError) as e:
             self._fail(w, f"is gone: {type(e).__name__}: {e}")
 
-    def _poll(self, pending, deadline: float):
+    def _poll(self, pending, deadline: float, block: bool = True):
         """Block until at least one worker of ``pending`` has answered (bounded by ``deadline``);
-        return ``[(w, message)]`` in the order the answers were seen."""
+        return ``[(w, message)]`` in the order the answers were seen.  ``block=False``: look once
+        without waiting; nothing ready is ``[]`` while the deadline has not passed."""
         objs = {}
         for w in sorted(pending):
             objs[self._conns[w]] = w
             objs[self._procs[w].sentinel] = w
-        ready = mpc.wait(list(objs), max(0.0, deadline - time.monotonic()))
+        ready = mpc.wait(list(objs), max(0.0, deadline - time.monotonic()) if block else 0.0)
         if not ready:
+            if not block and time.monotonic() < deadline:
+                return []
             self._fail(min(pending), f"gave no answer within the time limit ({self.timeout:g} s)")
-        out, seen = [], set()
+        out, seen, failed = [], set(), {}
         for o in ready:
             w = objs[o]
             if w in seen:
                 continue
             seen.add(w)
-            conn, msg = self._conns[w], None
-            try:
-                if conn.poll(0):                    # (also true at end-of-file)
-                    msg = conn.recv()
-            except (EOFError, OSError):
-                msg = None
-            if msg is None:
-                self._procs[w].join(_JOIN)
-                self._fail(w, f"exited unexpectedly (exit code {self._procs[w].exitcode})")
-            if msg[0] == "err":
-                self._fail(w, "raised:\n" + msg[1])
-            out.append((w, msg))
+            msg, what = self._answer(w)
+            if what is not None:
+                failed[w] = what
+            else:
+                out.append((w, msg))
+        if failed:
+            self._blame(failed, {w for w in pending if w not in seen and w < min(failed)}, deadline)
         return out
+
+    def _answer(self, w: int):
+        """Worker ``w`` has something to say: ``(message, None)``, or ``(None, what went wrong)``."""
+        conn, msg = self._conns[w], None
+        try:
+            if conn.poll(0):                    # (also true at end-of-file)
+                msg = conn.recv()
+        except (EOFError, OSError):
+            msg = None
+        if msg is None:
+            self._procs[w].join(_JOIN)
+            return None, f"exited unexpectedly (exit code {self._procs[w].exitcode})"
+        if msg[0] == "err":
+            return None, "raised:\n" + msg[1]
+        return msg, None
+
+    def _blame(self, failed: dict, lower: set, deadline: float):
+        """Raise for the LOWEST-numbered failed worker.  A fault common to all workers (a bad
+        factory, a missing env) reaches the parent in any order, so the lower-numbered workers still
+        pending get a short grace (``_BLAME`` s, within ``deadline``) to report theirs: which worker
+        the error names does not depend on the timing of the workers."""
+        end = min(deadline, time.monotonic() + _BLAME)
+        while lower:
+            objs = {}
+            for w in lower:
+                objs[self._conns[w]] = w
+                objs[self._procs[w].sentinel] = w
+            ready = mpc.wait(list(objs), max(0.0, end - time.monotonic()))
+            if not ready:
+                break
+            for w in {objs[o] for o in ready}:
+                lower.discard(w)
+                what = self._answer(w)[1]       # (an answer that is no failure is dropped: the pool is broken)
+                if what is not None:
+                    failed[w] = what
+        w = min(failed)
+        self._fail(w, failed[w])
 
     def _gather(self, pending, deadline: float) -> dict:
         got, pending = {}, set(pending)
@@ -400,6 +445,23 @@ class ProcRawAtariVector:
             for w, _ in self._poll(self._pending, deadline):
                 self._pending.discard(w)
                 self._ready.append(w)
+        b = self._ready.popleft()
+        e0, e1 = self.banks[b]
+        return b, self._reward[e0:e1], self._done[e0:e1]
+
+    def poll_bank(self):
+        """:meth:`wait_bank` with a zero wait: the next finished bank, or ``None`` at once while
+        every pending worker is still stepping.  Each bank still arrives exactly once per step; a
+        worker that raised, exited or has been silent past the step's time limit raises as there."""
+        self._usable()
+        if not self._ready:
+            if not self._pending:
+                raise RuntimeError("ProcRawAtariVector: no step in flight (every bank was taken)")
+            for w, _ in self._poll(self._pending, self._deadline, block=False):
+                self._pending.discard(w)
+                self._ready.append(w)
+            if not self._ready:
+                return None
         b = self._ready.popleft()
         e0, e1 = self.banks[b]
         return b, self._reward[e0:e1], self._done[e0:e1]

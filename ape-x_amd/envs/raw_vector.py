@@ -17,6 +17,11 @@ Differences from ``AtariPreprocess``:
   observation's -- the convention of the GPU env, whose done step renders the reset frame.
 * ``step`` returns ``(reward [N] float64, done [N] bool)``; the reward is the raw, unclipped
   sum over the repeat window (clipping is the consumer's business).
+* ``max_episode_steps > 0`` caps an agent-level episode (the reference evaluator's
+  ``max_episode_length``): the agent step at which an env's episode reaches that many agent steps
+  reports done and the env is started again through the same path as any other done -- with
+  ``episode_life`` a game that is not over takes the soft start, as the reference's ``env.reset()``
+  through ``EpisodicLifeEnv`` does.  The default 0 is no cap.
 
 The vector-env protocol the engine relies on.  :class:`apex_amd.envs.proc_vector.ProcRawAtariVector`
 provides the same five members over worker processes (one ``RawAtariVector`` per worker), plus a
@@ -64,9 +69,13 @@ class PairPool(RepeatPool):
 
 
 class RawAtariVector:
-    def __init__(self, raw_envs, spec: PreprocessSpec = PreprocessSpec()):
+    def __init__(self, raw_envs, spec: PreprocessSpec = PreprocessSpec(), max_episode_steps: int = 0):
         self.envs = list(raw_envs)
         self.spec = spec
+        if int(max_episode_steps) < 0:
+            raise ValueError("max_episode_steps must be >= 0 (0 = no cap)")
+        self.max_episode_steps = int(max_episode_steps)
+        self.episode_steps = [0] * len(self.envs)   # agent steps of each env's episode in progress
         self.fixed_noops: list[int | None] = [None] * len(self.envs)
         e0 = self.envs[0]
         if meaning(e0, 0) != "NOOP":
@@ -118,6 +127,7 @@ class RawAtariVector:
     def reset(self, out: np.ndarray) -> None:
         self._check(out)
         for i in range(len(self.envs)):
+            self.episode_steps[i] = 0
             self._start_into(i, out)
 
     def step(self, actions, out: np.ndarray):
@@ -127,8 +137,11 @@ class RawAtariVector:
         done = np.zeros(n, dtype=bool)
         for i in range(n):
             pair, r, d, _ = self._agent_step(i, int(actions[i]))
+            self.episode_steps[i] += 1
+            d = d or 0 < self.max_episode_steps <= self.episode_steps[i]
             rew[i], done[i] = r, d
             if d:
+                self.episode_steps[i] = 0
                 self._start_into(i, out)
             else:
                 out[i] = pair

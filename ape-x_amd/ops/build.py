@@ -54,6 +54,7 @@ HIP_SOURCES = [
     "ipc_kernels.hip",
     "vector_kernels.hip",
     "host_env_kernels.hip",
+    "host_eval_kernels.hip",
     "comm.cpp",
     "ipc.cpp",
 ]

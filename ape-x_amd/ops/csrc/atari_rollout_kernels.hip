@@ -10,27 +10,10 @@
 // launch are those n_steps stepwise steps leave, bit for bit, whenever both nets pick the same
 // actions.  (Q itself is fp32-class in another accumulation order, not bit-equal.)
 //
-// Where the data lives (LDS, 160 KiB per CU, one workgroup per CU):
-//   fr   4 x 7,056 B   the env's 4-frame stack as a 4-slot ring (chan -> slot in `csp`); loaded
-//                      once through hist, then only the rendered frame is added per step
-//   w1b  48 KiB        conv1 weight, split once into hi / mid / lo bf16 planes [k / 8][n][k % 8]
-//                      (one 16-B read per fragment and term)
-//   a1   400 x 36 f32  conv1 output NHWC, pixel pitch 36 (16-B aligned, 2-way on conv2's reads);
-//                      dead after conv2, so a3 [49][64] (FC1's k order p * 64 + c) reuses it
-//   a2   81 x 68 f32   conv2 output, pitch 68 (conflict-free 16-B reads for conv3)
-// Weights are read through L2 from the layouts that exist: features.0.weight, the forward
-// arena's w2p / w3p / wfc1p (k-contiguous rows), head weights and biases from the master.
-//
-// conv1 runs on v_mfma_f32_32x32x16_bf16 with the project's exact three-term split: u8 pixels
-// are exact in bf16 and a weight is hi + mid + lo exactly, so three products per 16 k, each exact
-// in fp32.  conv2 / conv3 run on v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32 accumulate): a wave
-// owns a 32 x 32 output tile (M padded to the tile: padded rows read a clamped pixel and are never
-// stored) over one k-part; a lane fetches 16 B of A and of B per 8 k and issues 4 MFMAs, lane half
-// h supplying k = 8c + 4h + j to MFMA j for both operands.  conv2 splits K over 2 and conv3 over 4
-// wave groups that add their tiles into LDS in a fixed order (barrier-separated phases), so the
-// result is deterministic.  FC1 is a 256 x 3136 GEMV on the VALU: wave w owns rows 16w .. 16w + 15,
-// per k half a lane holds its 7 (then 6) 16-B pieces of a3 in registers and reads each weight row as coalesced 16-B
-// loads; the lanes' partial sums meet in wave_sum's fixed butterfly, the two k halves in LDS.
+// The forward -- LDS layout, conv1 on v_mfma_f32_32x32x16_bf16 with the exact three-term split,
+// conv2 / conv3 on v_mfma_f32_32x32x2_f32 with fixed-order k-part adds, FC1 and the heads on the
+// VALU -- is atari_fwd_dev.h's, shared with host_eval_act_k.  Here the 4-frame stack `fr` is loaded
+// once through hist, then only the rendered frame is added per step.
 //
 // No workgroup writes a word another workgroup of the launch reads: env e owns state row e, its
 // hist / log rows and the frame-ring slots j * E + e; the step counter is only read.  The step
@@ -38,96 +21,14 @@
 #include <stdexcept>
 
 #include "atari_env_dev.h"
+#include "atari_fwd_dev.h"
 #include "common.h"
 #include "kernels.h"
 
 namespace apex {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bfx8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ uint32_t pack_bf16_hi(float lo, float hi) {  // two exact bf16 halves
-  return __builtin_amdgcn_perm(__float_as_uint(hi), __float_as_uint(lo), 0x07060302u);
-}
-__device__ __forceinline__ float trunc_bf16(float x) { return __uint_as_float(__float_as_uint(x) & 0xFFFF0000u); }
-
-constexpr int kT = 1024, kWaves = kT / 64;
-constexpr int kFrameDw = kScreen * kScreen / 4;  // 1764
-constexpr int kP1 = 36, kP2 = 68, kP3 = 64;      // LDS pixel pitches of a1 / a2 / a3 (floats)
-
-// The weights do not change during a launch, so the compiler would hoist their loads out of the
-// step loop (and spill them): every step's weight offsets go through this.
-__device__ __forceinline__ int opaque_i(int x) {
-  asm volatile("" : "+v"(x));
-  return x;
-}
-
-// C/D fragment of the 32x32 MFMA: register i of lane l is row (i & 3) + 8 (i >> 2) + 4 (l >> 5),
-// column l & 31.  `phase` of `phases` k-parts: 0 stores, the others add; the last adds bias + ReLU.
-template <int M, int POUT>
-__device__ __forceinline__ void tile_store(float* out, const f32x16& acc, int mt, int n, int kh, float bias,
-                                           bool first, bool last) {
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const int m = mt * 32 + (i & 3) + 8 * (i >> 2) + 4 * kh;
-    if (m < M) {
-      float v = acc[i];
-      float* o = out + m * POUT + n;
-      if (!first) v += *o;
-      if (last) v = fmaxf(v + bias, 0.f);
-      *o = v;
-    }
-  }
-}
-
-// conv2 / conv3 from an NHWC fp32 LDS image: out[m = oy * OUTW + ox][n] over k = (ky, kx, c).
-// Called by every thread (it holds KPARTS barriers); unit = wave index.
-template <int CIN, int KW, int STRIDE, int INW, int OUTW, int M, int PIN, int POUT, int KPARTS>
-__device__ __forceinline__ void conv_lds(const float* in, float* out, const float* __restrict__ w,
-                                         const float* __restrict__ bias, int unit, int lane) {
-  constexpr int K = KW * KW * CIN, MT = (M + 31) / 32, NT = 2, CP = K / 8 / KPARTS;
-  static_assert(CP * 8 * KPARTS == K && CP % 2 == 0 && CIN % 8 == 0 && MT * NT * KPARTS <= kWaves, "conv tiling");
-  const bool valid = unit < MT * NT * KPARTS;
-  const int kpart = unit / (MT * NT), tile = unit % (MT * NT), mt = tile % MT, nt = tile / MT;
-  const int r = lane & 31, kh = lane >> 5, n = nt * 32 + r;
-  f32x16 acc = {};
-  if (valid) {
-    const int m = min(mt * 32 + r, M - 1), oy = m / OUTW, ox = m % OUTW;
-    const float* arow = in + ((STRIDE * oy) * INW + STRIDE * ox) * PIN + kh * 4;
-    const float* brow = w + opaque_i(n * K + kh * 4);
-    auto load = [&](int ch, f32x4& a, f32x4& b) {
-      const int k0 = ch * 8, tap = k0 / CIN, c0 = k0 % CIN, ky = tap / KW, kx = tap % KW;
-      a = *reinterpret_cast<const f32x4*>(arow + (ky * INW + kx) * PIN + c0);
-      b = *reinterpret_cast<const f32x4*>(brow + k0);
-    };
-    // two chunks per iteration, the next two in flight under the 8 MFMAs (the last iteration
-    // re-reads its own chunks instead of branching)
-    const int c0 = kpart * CP, c1 = c0 + CP;
-    f32x4 a0, b0, a1, b1;
-    load(c0, a0, b0);
-    load(c0 + 1, a1, b1);
-#pragma unroll 1
-    for (int ch = c0; ch < c1; ch += 2) {
-      const int nx = min(ch + 2, c1 - 2);
-      f32x4 na0, nb0, na1, nb1;
-      load(nx, na0, nb0);
-      load(nx + 1, na1, nb1);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[j], b0[j], acc, 0, 0, 0);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[j], b1[j], acc, 0, 0, 0);
-      a0 = na0; b0 = nb0; a1 = na1; b1 = nb1;
-    }
-  }
-  const float bv = valid ? bias[n] : 0.f;
-#pragma unroll
-  for (int ph = 0; ph < KPARTS; ++ph) {
-    if (valid && kpart == ph) tile_store<M, POUT>(out, acc, mt, n, kh, bv, ph == 0, ph == KPARTS - 1);
-    __syncthreads();
-  }
-}
+using namespace atari_fwd;
 
 __global__ __launch_bounds__(kT) void atari_rollout_k(AtariRollout R) {
   __shared__ __attribute__((aligned(16))) uint32_t fr[4 * kFrameDw];
@@ -140,16 +41,9 @@ __global__ __launch_bounds__(kT) void atari_rollout_k(AtariRollout R) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, e = blockIdx.x;
   const int A = p.n_actions, E = p.E;
   const int64_t step0 = R.counter[0];
-  float* a3 = a1;
 
   // ---- stage once: conv1 weight, the 4-frame stack, the env's state / log / hist rows
-  for (int i = tid; i < 32 * 256; i += kT) {  // w = hi + mid + lo exactly (truncation: 8 + 8 + 8 bits)
-    const int n = i >> 8, k = i & 255, at = ((k >> 3) * 32 + n) * 8 + (k & 7);
-    const float w = R.w1[i], hi = trunc_bf16(w), r = w - hi, mid = trunc_bf16(r);
-    w1b[0][at] = (uint16_t)(__float_as_uint(hi) >> 16);
-    w1b[1][at] = (uint16_t)(__float_as_uint(mid) >> 16);
-    w1b[2][at] = (uint16_t)(__float_as_uint(r - mid) >> 16);
-  }
+  stage_w1(R.w1, w1b, tid);
   for (int c = 0; c < 4; ++c) {
     const int id = min(max(R.hist[e * 4 + c], 0), p.F - 1);  // (a frame id is always a ring slot)
     const uint32_t* src = reinterpret_cast<const uint32_t*>(R.frames + (size_t)id * p.frame_bytes);
@@ -165,98 +59,10 @@ __global__ __launch_bounds__(kT) void atari_rollout_k(AtariRollout R) {
 
   for (int k = 0; k < R.n_steps; ++k) {
     const int64_t step = step0 + k;
-    // ---- conv1: M = 400 (13 tiles), N = 32, K = 256 = (c, ky, kx) on v_mfma_f32_32x32x16_bf16 with
-    // the exact three-term weight split: u8 pixels are exact in bf16, every product is exact in
-    // fp32, only the fp32 accumulation rounds.  A 16-k step is two pixel rows (lane half h: row
-    // ky = (2s + h) & 7, its 8 kx) of channel s >> 2.
-    if (wave < 13) {
-      const int r = lane & 31, kh = lane >> 5;
-      const int m = min(wave * 32 + r, 399), oy = m / 20, ox = m % 20;
-      const uint32_t* arow = fr + (4 * oy) * 21 + ox;
-      f32x16 acc = {};
-#pragma unroll 4
-      for (int s = 0; s < 16; ++s) {
-        const int c = s >> 2, ky = (2 * s + kh) & 7;
-        const uint32_t* px = arow + ((csp >> (2 * c)) & 3) * kFrameDw + ky * 21;
-        const uint32_t p0 = px[0], p1 = px[1];
-        float f[8];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          f[j] = (float)((p0 >> (8 * j)) & 255u);
-          f[4 + j] = (float)((p1 >> (8 * j)) & 255u);
-        }
-        const bfx8 a = __builtin_bit_cast(bfx8, make_uint4(pack_bf16_hi(f[0], f[1]), pack_bf16_hi(f[2], f[3]),
-                                                            pack_bf16_hi(f[4], f[5]), pack_bf16_hi(f[6], f[7])));
-        const int at = ((2 * s + kh) * 32 + r) * 8;
-#pragma unroll
-        for (int t = 2; t >= 0; --t)  // lo, mid, hi
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              a, __builtin_bit_cast(bfx8, *reinterpret_cast<const uint4*>(&w1b[t][at])), acc, 0, 0, 0);
-      }
-      tile_store<400, kP1>(a1, acc, wave, r, kh, R.b1[r], true, true);
-    }
-    __syncthreads();
-    // ---- conv2: 81 x 64 x 512 (2 k-parts); conv3: 49 x 64 x 576 (4 k-parts) into a3 (a1 is dead)
-    conv_lds<32, 4, 2, 20, 9, 81, kP1, kP2, 2>(a1, a2, R.w2p, R.b2, wave, lane);
-    conv_lds<64, 3, 1, 9, 7, 49, kP2, kP3, 4>(a2, a3, R.w3p, R.b3, wave, lane);
-    // ---- FC1: h[n] = relu(sum_k a3[k] wfc1p[n][k] + b), k = p * 64 + c (3136 = 784 x 16 B)
-    // (two k halves, so a lane holds 7 pieces of a3 beside the 7 loads in flight)
-#pragma unroll 1
-    for (int half = 0; half < 2; ++half) {
-      f32x4 x[7];
-#pragma unroll
-      for (int i = 0; i < 7; ++i) {
-        const int q = lane + 64 * (7 * half + i);
-        x[i] = q < 784 ? reinterpret_cast<const f32x4*>(a3)[q] : f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-#pragma unroll 1
-      for (int j = 0; j < 16; ++j) {
-        const int n = wave * 16 + j;
-        const f32x4* wr = reinterpret_cast<const f32x4*>(R.wfc1p + opaque_i(n * 3136));
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < 7; ++i) {
-          const int q = lane + 64 * (7 * half + i);
-          if (q < 784) {
-            const f32x4 wv = wr[q];
-            s += x[i][0] * wv[0] + x[i][1] * wv[1] + x[i][2] * wv[2] + x[i][3] * wv[3];
-          }
-        }
-        s = wave_sum(s);
-        if (lane == 0) zs[half * 256 + n] = s;
-      }
-    }
-    __syncthreads();
-    if (tid < 256) hs[tid] = fmaxf(zs[tid] + zs[256 + tid] + (tid < 128 ? R.ba1[tid] : R.bv1[tid - 128]), 0.f);
-    __syncthreads();
-    // ---- heads: A advantage rows over h[0..127], the value row over h[128..255]
-    for (int o = wave; o <= A; o += kWaves) {
-      const float* wrow = (o < A ? R.wa2 + o * 128 : R.wv2) + opaque_i(0);
-      const float* hh = hs + (o < A ? 0 : 128);
-      float s = hh[2 * lane] * wrow[2 * lane] + hh[2 * lane + 1] * wrow[2 * lane + 1];
-      s = wave_sum(s);
-      if (lane == 0) advs[o] = s + (o < A ? R.ba2[o] : R.bv2[0]);
-    }
-    __syncthreads();
+    forward(R, fr, csp, w1b, a1, a2, zs, hs, advs, A, tid, lane, wave);
     // ---- dueling combine, action (select_actions' rule and draw), env step (thread 0)
     if (tid == 0) {
-      float mean = 0.f;
-      for (int a = 0; a < A; ++a) mean += advs[a];
-      mean /= (float)A;
-      const float val = advs[A];
-      int best = 0;
-      float bvq = 0.f;
-      for (int a = 0; a < A; ++a) {
-        const float qv = val + (advs[a] - mean);
-        qs[a] = qv;
-        if (a == 0 || qv > bvq) { bvq = qv; best = a; }
-      }
-      float u[4];
-      uniform4(R.act_seed, (uint64_t)e, (uint64_t)step, u);
-      if (!(u[0] > R.eps[e])) {
-        const int rr = (int)(u[1] * (float)A);
-        best = rr < A ? rr : A - 1;
-      }
+      const int best = combine_select(advs, qs, A, R.act_seed, e, step, R.eps[e]);
       float st[S_STRIDE];
 #pragma unroll
       for (int i = 0; i < S_STRIDE; ++i) st[i] = sst[i];

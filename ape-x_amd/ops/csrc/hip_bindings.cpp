@@ -971,6 +971,30 @@ PYBIND11_MODULE(_apex_hip, m) {
     return r;
   });
   m.def("atari_rollout", [](const AtariRollout& r, uint64_t s) { atari_rollout(r, S(s)); });
+  // the act half of one host-env evaluator step in one launch (host_eval_kernels.hip)
+  py::class_<HostEvalAct>(m, "HostEvalAct");
+  // d: w1, b1, w2p, b2, w3p, b3, wfc1p, ba1, bv1, wa2, ba2, wv2, bv2, N, A, F, frame_bytes, advance, step,
+  // act_seed, eps, frames, hist, new_frame, done, counter, q, actions (a missing pointer is null: the launcher throws)
+  m.def("make_host_eval_act", [](py::dict d) {
+    auto opt = [&](const char* k) { return d.contains(k) ? d[k].cast<uint64_t>() : (uint64_t)0; };
+    HostEvalAct r{};
+    r.w1 = P<const float>(opt("w1")); r.b1 = P<const float>(opt("b1"));
+    r.w2p = P<const float>(opt("w2p")); r.b2 = P<const float>(opt("b2"));
+    r.w3p = P<const float>(opt("w3p")); r.b3 = P<const float>(opt("b3"));
+    r.wfc1p = P<const float>(opt("wfc1p"));
+    r.ba1 = P<const float>(opt("ba1")); r.bv1 = P<const float>(opt("bv1"));
+    r.wa2 = P<const float>(opt("wa2")); r.ba2 = P<const float>(opt("ba2"));
+    r.wv2 = P<const float>(opt("wv2")); r.bv2 = P<const float>(opt("bv2"));
+    r.N = d["N"].cast<int>(); r.A = d["A"].cast<int>(); r.F = d["F"].cast<int>();
+    r.frame_bytes = d["frame_bytes"].cast<int>();
+    r.advance = d["advance"].cast<int>(); r.step = d["step"].cast<int64_t>();
+    r.act_seed = d["act_seed"].cast<uint64_t>();
+    r.eps = P<const float>(opt("eps")); r.frames = P<const uint8_t>(opt("frames")); r.hist = P<int>(opt("hist"));
+    r.new_frame = P<const int>(opt("new_frame")); r.done = P<const float>(opt("done"));
+    r.counter = P<int64_t>(opt("counter")); r.q = P<float>(opt("q")); r.actions = P<int>(opt("actions"));
+    return r;
+  });
+  m.def("host_eval_act", [](const HostEvalAct& r, uint64_t s) { host_eval_act(r, S(s)); });
   // one env's acting frame of the single-process AQL trainer (aql_frame_kernels.hip)
   py::class_<AqlFrame>(m, "AqlFrame");
   m.def("make_aql_frame", [](const AQLNet& net, const AqlEnv& env, const AqlInsert& ins, const TreeHandle& tree,

@@ -162,6 +162,38 @@ struct AtariRollout {
 };
 void atari_rollout(const AtariRollout& r, hipStream_t s);
 
+// ---- host_eval_kernels.hip
+// The act half of one evaluator step over host emulators, one launch, one workgroup per env: with
+// advance != 0 frame_hist_step's stack advance of hist[e] from new_frame[e] / done[e] and
+// counter[0] = step (stored, never read here); then the fp32 Nature-CNN dueling forward of
+// atari_rollout on the 4-frame stack staged from the ring through hist[e] (ids clamped to
+// [0, F)), q[e][0..A) and actions[e] by select_actions' rule and draw at Philox key
+// (act_seed, e, step).  Nothing else is written.  Throws std::invalid_argument before any launch
+// unless 1 <= N <= 64, 1 <= A <= 18, F == 8 N, 84x84 frames, 16-byte aligned w2p / w3p / wfc1p, a
+// 4-byte aligned ring and every pointer present.
+struct HostEvalAct {
+  const float *w1, *b1;        // features.0 weight (32,4,8,8) / bias (master layout)
+  const float *w2p, *b2;       // conv2 weight (64,4,4,32) of the fp32 forward arena / bias
+  const float *w3p, *b3;       // conv3 weight (64,3,3,64) / bias
+  const float *wfc1p;          // (256,49,64): advantage.0 rows then value.0 rows
+  const float *ba1, *bv1;      // advantage.0 / value.0 bias [128]
+  const float *wa2, *ba2;      // advantage.2 [A][128] / [A]
+  const float *wv2, *bv2;      // value.2 [128] / [1]
+  int N, A, F, frame_bytes;    // envs, actions, ring slots (8 N), 84*84
+  int advance;                 // 0: hist and counter untouched (the step after a reset ingest)
+  int64_t step;                // this act's step: the Philox counter, and what counter[0] becomes
+  uint64_t act_seed;
+  const float* eps;            // [N]
+  const uint8_t* frames;       // [F][84*84]
+  int* hist;                   // [N][4]
+  const int* new_frame;        // [N]
+  const float* done;           // [N]
+  int64_t* counter;            // [1]
+  float* q;                    // [N][A]
+  int* actions;                // [N]
+};
+void host_eval_act(const HostEvalAct& r, hipStream_t s);
+
 struct NStepParams {
   int E, A, n, C;   // envs, actions, n-step, transition capacity
   float gamma;

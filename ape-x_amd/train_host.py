@@ -21,6 +21,17 @@ steps enqueued per env step), ``--workers``, ``--worker-timeout`` (seconds a wor
 ``--bps_interval`` learner steps: ``learner/loss``, ``learner/grad_norm``, ``learner/BPS``,
 ``actor/episode_reward`` (clipped return), ``actor/episode_length``, ``actor/episode_score``
 (unclipped game score), ``actor/frames_per_sec`` and ``replay/size``.
+
+``--eval-envs N`` (default 0 = off) adds the reference's evaluator (``eval.py``): ``N`` further
+emulators played greedily (epsilon 0, rewards unclipped, episodes capped at ``--max_episode_length``
+agent steps) with the published actor weights, refreshed every ``--eval-interval`` learner steps
+(``engine.host_eval``).  ``--eval-mode async`` (default) steps them in ``--eval-workers`` worker
+processes of their own and pumps the evaluator once per training iteration without ever waiting for
+it; ``--eval-mode step`` steps in-process emulators for ``--eval-steps`` blocking evaluator steps per
+interval (deterministic; tests and A/Bs).  ``--eval-kernel {fused,step}`` picks the one-launch act or
+the stepwise yardstick.  Evaluator env ``j`` is seeded ``seed + 1,000,003 + j``.  When episodes
+finished since the last log line: ``evaluator/episode_reward`` (game score), ``evaluator/episode_length``,
+``evaluator/episodes``, ``evaluator/capped_episodes`` and ``evaluator/steps``.
 """
 from __future__ import annotations
 
@@ -40,6 +51,14 @@ def parser():
                    help="seconds a worker may take for one step before the run is aborted")
     p.add_argument("--ingest", choices=["auto", "whole", "banked"], default="auto",
                    help="with --workers: ingest each worker's envs as they finish (banked) or all at once (whole)")
+    p.add_argument("--eval-envs", type=int, default=0, help="greedy evaluator emulators (0 = no evaluator; at most 64)")
+    p.add_argument("--eval-workers", type=int, default=1, help="evaluator worker processes (--eval-mode async)")
+    p.add_argument("--eval-interval", type=int, default=100, help="learner steps between evaluator weight refreshes")
+    p.add_argument("--eval-mode", choices=["async", "step"], default="async",
+                   help="async: worker pool pumped every iteration; step: in-process, blocking, deterministic")
+    p.add_argument("--eval-steps", type=int, default=64, help="evaluator steps per interval (--eval-mode step)")
+    p.add_argument("--eval-kernel", choices=["fused", "step"], default="fused",
+                   help="fused: one-launch act (host_eval_act); step: the stepwise forward")
     p.add_argument("--save-path", default="model.pth")
     p.add_argument("--resume", default=None, help="model.pth (+ .train.pt sidecar) to resume from")
     p.add_argument("--log-dir", default=None, help="event-file directory (default runs/<time>-<env>-host)")
@@ -53,6 +72,11 @@ def main(argv=None) -> int:
     args = parser().parse_args(argv)
     if args.workers < 0:
         raise SystemExit("--workers must be >= 0")
+    if not 0 <= args.eval_envs <= 64:
+        raise SystemExit("--eval-envs must be in [0, 64]")
+    if args.eval_envs and (args.eval_interval < 1 or args.eval_steps < 1 or
+                           not 1 <= args.eval_workers <= args.eval_envs):
+        raise SystemExit("--eval-interval / --eval-steps must be >= 1 and --eval-workers in [1, --eval-envs]")
     cfg = args_to_config(args)
     if not torch.cuda.is_available():
         raise SystemExit("apex_amd.train_host runs the GPU engine; use apex_amd.roles.* on CPU")
@@ -101,13 +125,43 @@ def _train(args, cfg, vec, spec, device) -> int:
                          use_graphs=cfg.kernel.use_graphs, exact_mass=R.exact_mass, seed=cfg.seed,
                          ingest=args.ingest if args.workers else "auto", learner=lc)
     eng = HostEnvEngine(ecfg, vec, device)
+    evaluation = None
     try:
-        return _loop(args, cfg, eng, device)
+        evaluation = _make_evaluation(args, cfg, spec, eng, device)
+        return _loop(args, cfg, eng, device, evaluation)
     finally:
+        if evaluation is not None:
+            evaluation.close()   # side stream drained, staging unregistered, evaluator pool closed
         eng.close()   # unregisters the shared staging block, then closes the pool that owns it
 
 
-def _loop(args, cfg, eng, device) -> int:
+def _make_evaluation(args, cfg, spec, eng, device):
+    """The evaluator of ``--eval-envs`` emulators (None when off): a :class:`HostEnvEvaluation` over
+    its own worker pool (async) or a :class:`HostEvaluator` over in-process emulators (step)."""
+    if not args.eval_envs:
+        return None
+    from .engine.host_eval import HostEnvEvaluation, HostEvaluator, eval_seed
+
+    cap, sd = int(cfg.env.max_episode_length), eval_seed(cfg.seed)
+    if args.eval_mode == "step":
+        from .envs.core import make
+        from .envs.raw_vector import RawAtariVector
+
+        vec = RawAtariVector([make(cfg.env.env) for _ in range(args.eval_envs)], spec, max_episode_steps=cap)
+        vec.seed(sd)
+        return HostEvaluator(eng.actor_model, vec, device, kernel=args.eval_kernel, seed=sd)
+    from .envs.proc_vector import ProcRawAtariVector
+
+    pool = ProcRawAtariVector(cfg.env.env, args.eval_envs, spec, workers=args.eval_workers, seed=sd,
+                              timeout=args.worker_timeout, max_episode_steps=cap)
+    try:
+        return HostEnvEvaluation(HostEvaluator(eng.actor_model, pool, device, kernel=args.eval_kernel, seed=sd), pool)
+    except BaseException:
+        pool.close()
+        raise
+
+
+def _loop(args, cfg, eng, device, evaluation=None) -> int:
     import torch
 
     from .train import load_engine, save_engine
@@ -132,9 +186,23 @@ def _loop(args, cfg, eng, device) -> int:
     bps_every = max(1, L.bps_interval)
     t_last, step_last, act_last, next_log = time.perf_counter(), start, 0, start + bps_every
     next_save = (start // L.save_interval + 1) * L.save_interval if L.save_interval else None
+    next_refresh = start + args.eval_interval
+    ev_core = getattr(evaluation, "ev", evaluation)   # the HostEvaluator (its ledger holds the totals)
+    if evaluation is not None:
+        print(f"evaluator: {args.eval_envs} greedy host envs, {args.eval_mode} mode, {args.eval_kernel} act kernel",
+              flush=True)
     while not max_step or eng.learn_steps < max_step:
         eng.iteration()
         step = eng.learn_steps
+        if evaluation is not None:
+            ev_core.learn_step = step
+            # (a refused refresh -- the target set is still read -- is simply tried again next iteration)
+            if step >= next_refresh and evaluation.refresh(eng.actor_flat, eng.actor_net):
+                next_refresh = step + args.eval_interval
+                if args.eval_mode == "step":
+                    evaluation.run(args.eval_steps)
+            if args.eval_mode == "async":
+                evaluation.pump()
         if step >= next_log:
             next_log = step + bps_every
             st = eng.stats()  # (synchronises)
@@ -148,6 +216,14 @@ def _loop(args, cfg, eng, device) -> int:
                 line["actor/episode_length"] = st["episode_length"]
                 line["actor/episode_score"] = st["episode_score"]
             line["replay/size"] = float(st["replay_size"])
+            done_eps = evaluation.poll() if evaluation is not None else []
+            if done_eps:
+                n = float(len(done_eps))
+                line["evaluator/episode_reward"] = sum(e[0] for e in done_eps) / n
+                line["evaluator/episode_length"] = sum(e[1] for e in done_eps) / n
+                line["evaluator/episodes"] = float(ev_core.ledger.episodes)
+                line["evaluator/capped_episodes"] = float(ev_core.ledger.capped)
+                line["evaluator/steps"] = float(ev_core.ledger.steps)
             t_last, step_last, act_last = now, step, eng.actor_steps
             print(f"Step: {step} " + " ".join(f"{k}={v:.4g}" for k, v in line.items()), flush=True)
             if writer is not None:
