@@ -164,6 +164,8 @@ struct HasMaskBits<P, decltype((void)P::MASK_BITS, void())> : std::true_type {};
 // ml, tile column 0 (nullptr for a row past the problem; rows are 16-byte aligned), optionally
 // fin4(a, c, nl, v) = the four values stored at tile columns nl .. nl + 3 (bias + ReLU).  A policy
 // whose store cannot always widen (ELEM_STORE: wide_rows(a) block-uniform) keeps store() too.
+// The line-owned epilogue uses the same hooks: fin4 / the mask word / the sign bits on the lane's
+// own row before its LDS transpose, out_row once per 8-row store group after it.
 template <class P, class = void>
 struct HasFin4 : std::false_type {};
 template <class P>
@@ -338,13 +340,21 @@ __device__ __forceinline__ uint2 ds_tr16(const char* p) {
 // k-slots at every depth: bit-identical results (tests/test_gpu_f32_prefetch.py).
 // XB: the launch carries sign bits (a kernel of its own: with the hooks compiled into the plain
 // kernels behind a null-pointer test, those ran 1.3 % slower per step with every pointer null).
-// RW: the row-owned epilogue (operand roles swapped on the MFMA; APEX_F32_EPILOGUE picks per launch
-// class); false = the element epilogue.  Same products, same k order: bit-identical results.
-template <class P, int SS, int D, bool XB = false, bool RW = true>
+// EP: the epilogue (APEX_F32_EPILOGUE picks per launch class): 0 = the element epilogue, 1 = the
+// row-owned one (operand roles swapped on the MFMA), 2 = the line-owned one (row-owned values,
+// transposed through a wave-private piece of the LDS tile so every store instruction writes whole
+// 128-byte lines).  Same products, same k order: bit-identical results.
+constexpr int kEpElem = 0, kEpRow = 1, kEpLine = 2;
+// floats of the LDS tile a line-owned wave may transpose through (4 waves x 32 x 32 at least)
+constexpr int kLineLdsFloats = 4 * 1024;
+template <class P, int SS, int EP>
+struct LdsFloats;
+template <class P, int SS, int D, bool XB = false, int EP = kEpRow>
 __device__ __forceinline__ void gemm_body(const typename P::Args& args, int block, float* lds,
                                           typename P::Smem& sm) {
   using G = Geo<P>;
   using GS = GeoS<P>;
+  constexpr bool RW = EP != kEpElem, LN = EP == kEpLine;
   constexpr bool COLSUM = HasColsum<P>::value;
   constexpr bool WBITS = XB && HasReluBits<P>::value, RBITS = XB && HasMaskBits<P>::value;
   static_assert(!COLSUM || (!P::A_KMAJ && 256 % G::RA == 0), "colsum needs MN-major A");
@@ -714,10 +724,56 @@ __device__ __forceinline__ void gemm_body(const typename P::Args& args, int bloc
     } else {
       bool wbits = false;
       if constexpr (WBITS) wbits = P::want_bits(ctx);  // block-uniform
+      // Line-owned stores: a wave keeps NREG 32 x 32 fp32 images (4 KB each) in its own piece of the
+      // LDS tile (the loop's last barrier retired every fragment read, and no other wave touches
+      // the piece: no workgroup barrier).  Lane (r, h) writes its four 16-byte runs of row r, run
+      // c = h + 2j at chunk c ^ (r & 7) of the row's 128 bytes: the 8 lanes of a ds_write_b128
+      // group (8 consecutive rows, one c) cover all 32 banks once.  It reads back as lane L = row
+      // 8k + (L >> 3), chunk L & 7 for k = 0..3: 8 consecutive lanes hold one row's 128 bytes, so a
+      // store instruction writes 8 whole lines; a ds_read_b128 group of 16 lanes (4 half rows, two
+      // of the low and two of the high chunks, row parities 0 1 0 1) lands on 16 distinct 16-byte
+      // bank groups of 64 banks.  The LDS serves one wave's operations in order; the counted wait
+      // holds a block's read-back until its own writes have retired (NREG - 1 blocks of four
+      // operations stand between them), the wave-scope fences keep the compiler from crossing it.
+      constexpr int NBLK = G::TM * G::TN;
+      constexpr int NREG = LN ? (NBLK < LdsFloats<P, SS, EP>::value / kLineLdsFloats
+                                     ? NBLK : LdsFloats<P, SS, EP>::value / kLineLdsFloats) : 1;
+      static_assert(NREG >= 1, "the LDS tile holds one 32 x 32 image per wave");
+      constexpr int LNWAIT = 4 * (NREG - 1) < 15 ? 4 * (NREG - 1) : 15;
+      float* const lreg = lds + wave * NREG * 1024;
+      const int lr = lane >> 3, lc = lane & 7;
+      auto line_out = [&](int b0) {  // blocks b0 .. b0 + NREG - 1: read back, whole-line stores
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+#pragma unroll
+        for (int b = b0; b < b0 + NREG && b < NBLK; ++b) {
+          const int mi = b / G::TN, ni = b % G::TN;
+          __builtin_amdgcn_s_waitcnt(0xC07F | (LNWAIT << 8));  // lgkmcnt(LNWAIT) alone
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+          const float* img = lreg + (b % NREG) * 1024;
+          f32x4 w[4];
+#pragma unroll
+          for (int k = 0; k < 4; ++k) w[k] = *reinterpret_cast<const f32x4*>(img + (8 * k + lr) * 32 + ((lc ^ lr) * 4));
+          const int nl = wn * G::WTN + ni * 32 + 4 * lc;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            float* const orow = P::out_row(args, ctx, wm * G::WTM + mi * 32 + 8 * k + lr);
+            if (orow) {
+              if constexpr (HasMaskBits<P>::value && !RBITS) {  // the fp32 activation at the output's offsets
+                const f32x4 mk = ld4(args.mask + (orow - args.out) + nl);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) w[k][i] = mk[i] > 0.f ? w[k][i] : 0.f;
+              }
+              *reinterpret_cast<f32x4*>(orow + nl) = w[k];
+            }
+          }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // (the next round's writes stay behind)
+      };
 #pragma unroll
       for (int mi = 0; mi < G::TM; ++mi) {
         const int ml = wm * G::WTM + mi * 32 + r;
-        float* const orow = P::out_row(args, ctx, ml);  // nullptr: a row past the problem
+        float* orow = nullptr;
+        if constexpr (!LN) orow = P::out_row(args, ctx, ml);  // nullptr: a row past the problem
 #pragma unroll
         for (int ni = 0; ni < G::TN; ++ni) {
           const int nl0 = wn * G::WTN + ni * 32 + 4 * h;
@@ -740,7 +796,13 @@ __device__ __forceinline__ void gemm_body(const typename P::Args& args, int bloc
 #pragma unroll
               for (int i = 0; i < 4; ++i) v[j][i] = (kw >> (8 * j + i)) & 1u ? v[j][i] : 0.f;
           }
-          if (orow) {
+          if constexpr (LN) {
+            float* img = lreg + ((mi * G::TN + ni) % NREG) * 1024 + r * 32;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(img + (((h + 2 * j) ^ (r & 7)) * 4)) = v[j];
+            if ((mi * G::TN + ni + 1) % NREG == 0 || mi * G::TN + ni + 1 == NBLK)  // (unrolled: compile-time)
+              line_out((mi * G::TN + ni) / NREG * NREG);
+          } else if (orow) {
             if constexpr (HasMaskBits<P>::value && !RBITS) {  // the fp32 activation at the output's offsets
               const float* mrow = args.mask + (orow - args.out);
 #pragma unroll
@@ -823,7 +885,9 @@ __device__ __forceinline__ void gemm_body(const typename P::Args& args, int bloc
 
   if constexpr (COLSUM) {
     if (P::want_colsum(ctx)) {  // block-uniform
-      // the last loop barrier retired every LDS read: reuse the tile buffer
+      // the last loop barrier retired every LDS read: reuse the tile buffer (line-owned epilogue:
+      // once every wave has read its transposed blocks back)
+      if constexpr (LN) __syncthreads();
       *reinterpret_cast<f32x4*>(lds + 4 * t) = csum;
       __syncthreads();
       if (t < G::BM) {
@@ -844,32 +908,34 @@ struct MaxI {
 // form SS: 0 = register split (Geo image), 1 = stage-split double buffer, 2 = stage-split single
 // buffer, 3 = form 2 compiled for >= 3 waves per SIMD (amdgpu_waves_per_eu: the 128 x 64 conv2
 // tile 204 -> 150 VGPRs, the others 104 -> 92, no spills)
-template <class P, int SS>
+// (the line-owned epilogue transposes through the tile: one 32 x 32 image per wave at least)
+template <class P, int SS, int EP>
 struct LdsFloats {
   static constexpr int value =
-      SS ? MaxI<GeoS<P>::LDS_BYTES / (SS >= 2 ? 8 : 4), 4 * 256>::value : Geo<P>::LDS_FLOATS;
+      MaxI<SS ? MaxI<GeoS<P>::LDS_BYTES / (SS >= 2 ? 8 : 4), 4 * 256>::value : Geo<P>::LDS_FLOATS,
+           EP == kEpLine ? kLineLdsFloats : 0>::value;
 };
 template <int SS>
 struct BodyForm {
   static constexpr int value = SS == 3 ? 2 : SS;
 };
 
-template <class P, int SS, int D, bool XB = false, bool RW = true>
+template <class P, int SS, int D, bool XB = false, int EP = kEpRow>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SS == 3 || D > 1 ? 3 : 1))) void gemm_k(
     typename P::Args args) {
-  __shared__ __attribute__((aligned(16))) float lds[LdsFloats<P, SS>::value];
+  __shared__ __attribute__((aligned(16))) float lds[LdsFloats<P, SS, EP>::value];
   __shared__ typename P::Smem sm;
-  gemm_body<P, BodyForm<SS>::value, D, XB, RW>(args, xcd_chunk(blockIdx.x, gridDim.x), lds, sm);
+  gemm_body<P, BodyForm<SS>::value, D, XB, EP>(args, xcd_chunk(blockIdx.x, gridDim.x), lds, sm);
 }
 
 // Two independent GEMMs in one launch: blocks [0, n1) run P1, the rest P2 (P1 first: the
 // longer per-block problem starts early).
 // r (stage > 0): the learner's priority-tree write riding the launch as extra workgroups
 // (tree_dev.h tree_ride: the leaves in block 0, a level's recompute past the GEMM tiles).
-template <class P1, class P2, int SS, int D, bool XB = false, bool RW = true>
+template <class P1, class P2, int SS, int D, bool XB = false, int EP = kEpRow>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SS == 3 || D > 1 ? 3 : 1))) void gemm2_k(
     typename P1::Args a1, typename P2::Args a2, int n1, TreeRide r) {
-  __shared__ __attribute__((aligned(16))) float lds[MaxI<LdsFloats<P1, SS>::value, LdsFloats<P2, SS>::value>::value];
+  __shared__ __attribute__((aligned(16))) float lds[MaxI<LdsFloats<P1, SS, EP>::value, LdsFloats<P2, SS, EP>::value>::value];
   __shared__ union {
     typename P1::Smem s1;
     typename P2::Smem s2;
@@ -877,9 +943,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SS == 3 || 
   int b = blockIdx.x;
   if (r.stage && tree_ride(r, r.nhost, lds, &b)) return;  // (grid-uniform stage, block-uniform role)
   if (b < n1)
-    gemm_body<P1, BodyForm<SS>::value, D, XB, RW>(a1, b, lds, sm.s1);
+    gemm_body<P1, BodyForm<SS>::value, D, XB, EP>(a1, b, lds, sm.s1);
   else
-    gemm_body<P2, BodyForm<SS>::value, D, XB, RW>(a2, b - n1, lds, sm.s2);
+    gemm_body<P2, BodyForm<SS>::value, D, XB, EP>(a2, b - n1, lds, sm.s2);
 }
 
 __device__ __forceinline__ F32Prob pick(const F32Set& s, int i) {
@@ -2035,56 +2101,72 @@ int batch_resolve_mask() {
   return g_batch_resolve;
 }
 // Epilogue of the GEMM bodies per launch class, read at launch time (a captured graph keeps the
-// one it was captured with): bit 0 = the learner-sized forward launches, bit 1 = the backward
-// pairs, bit 2 = the forward launches below the learner's size; a set bit = the row-owned
-// epilogue (operand roles swapped on the MFMA, 16-byte stores), a clear one = the element
-// epilogue (one dword per lane and store).  Bit-identical results (tests/test_gpu_f32_epilogue.py).
-// A class's DEFAULT epilogue is built for every form and depth, its other one only for the forms
-// the defaults run (forward: 0 and 3, backward pairs: 3) at depth 1 -- asking for it elsewhere
-// throws.  Whole step on one box, builds and masks alternated in separate processes
-// (profiles/epilogue_rows.md): the learner-sized forward gains 3.7 % (conv2 forward 59.8 -> 53.9 us);
-// the backward pairs lose (conv2 pair 45.6 -> 47.3 us per launch, step -0.2 %: 32 rows x 32 bytes
-// per store instruction against 2 rows x 128) and the small launches stay inside the noise.
-constexpr int kEpilogueDefault = 1;
+// one it was captured with).  Class c (0 = the learner-sized forward launches, 1 = the backward
+// pairs, 2 = the forward launches below the learner's size): bit 3 + c set = the line-owned
+// epilogue (the row-owned values transposed through LDS, whole 128-byte lines per store
+// instruction); else bit c set = the row-owned epilogue (operand roles swapped on the MFMA,
+// 16-byte stores, 32 rows x 32 bytes per instruction), clear = the element epilogue (one dword per
+// lane and store).  Values 0-7 mean what they meant before the line-owned epilogue existed.
+// Bit-identical results (tests/test_gpu_f32_epilogue.py, tests/test_gpu_f32_epilogue_lines.py).
+// A class's DEFAULT epilogue is built for every form and depth, its other two only for the forms
+// the defaults run (forward: 0 and 3, backward pairs: 3) at depth 1 -- asking for one elsewhere
+// throws.  Whole step on one box, builds and masks alternated in separate processes:
+// row-owned against element (profiles/epilogue_rows.md): the learner-sized forward +3.7 %, the
+// backward pairs lose (32 rows x 32 bytes per store instruction against 2 rows x 128), the small
+// launches inside the noise.  Line-owned (profiles/epilogue_lines.md): every class on it reads
+// +1.0 to +1.7 % over mask 1 and over the parent build in three sessions, every round; one class
+// alone on it stays near the noise pair (pairs +0.1 to +0.9 %, small forward +0.5 to +0.9 %,
+// learner-sized forward level).
+constexpr int kEpilogueDefault = 8 + 16 + 32;
 int g_epilogue = -1;
 int epilogue_mask() {
   if (g_epilogue < 0) {
     const char* e = std::getenv("APEX_F32_EPILOGUE");
-    g_epilogue = e ? std::atoi(e) & 7 : kEpilogueDefault;
+    g_epilogue = e ? std::atoi(e) & 63 : kEpilogueDefault;
   }
   return g_epilogue;
 }
 // cls: 0 = learner-sized forward, 1 = backward pair, 2 = small forward
-bool row_epilogue(int cls) { return (epilogue_mask() >> cls) & 1; }
-constexpr bool row_epilogue_default(int cls) { return (kEpilogueDefault >> cls) & 1; }
+constexpr int epilogue_of(int mask, int cls) {
+  return (mask >> (3 + cls)) & 1 ? kEpLine : ((mask >> cls) & 1 ? kEpRow : kEpElem);
+}
+int epilogue_kind(int cls) { return epilogue_of(epilogue_mask(), cls); }
+constexpr int epilogue_default(int cls) { return epilogue_of(kEpilogueDefault, cls); }
 int prefetch_depth(int cls) { return std::min(3, 1 + ((prefetch_mask() >> (2 * cls)) & 3)); }
 
-template <class P, int D, bool XB, bool RW>
+template <class P, int D, bool XB, int EP>
 void launch1_f(const typename P::Args& a, int blocks, hipStream_t s, int form) {
   switch (form) {
-    case 1: gemm_k<P, 1, D, XB, RW><<<blocks, 256, 0, s>>>(a); break;
-    case 2: gemm_k<P, 2, D, XB, RW><<<blocks, 256, 0, s>>>(a); break;
-    case 3: gemm_k<P, 3, D, XB, RW><<<blocks, 256, 0, s>>>(a); break;
-    default: gemm_k<P, 0, D, XB, RW><<<blocks, 256, 0, s>>>(a);
+    case 1: gemm_k<P, 1, D, XB, EP><<<blocks, 256, 0, s>>>(a); break;
+    case 2: gemm_k<P, 2, D, XB, EP><<<blocks, 256, 0, s>>>(a); break;
+    case 3: gemm_k<P, 3, D, XB, EP><<<blocks, 256, 0, s>>>(a); break;
+    default: gemm_k<P, 0, D, XB, EP><<<blocks, 256, 0, s>>>(a);
   }
+}
+// a forward class's non-default epilogue EP (forms 0 and 3, depth 1); false: not built
+template <class P, int D, bool XB, int EP>
+bool launch1_o(const typename P::Args& a, int blocks, hipStream_t s, int form) {
+  if constexpr (D == 1) {
+    if (form == 0) {
+      gemm_k<P, 0, 1, XB, EP><<<blocks, 256, 0, s>>>(a);
+      return true;
+    }
+    if (form == 3) {
+      gemm_k<P, 3, 1, XB, EP><<<blocks, 256, 0, s>>>(a);
+      return true;
+    }
+  }
+  return false;
 }
 // CLS 0: a learner-sized forward launch; CLS 2: a launch below the learner's size (the actor's /
 // evaluator's forward) -- bits 4-5 of the form mask, when set, give those launches a form of their
 // own (form + 1; 0 = the forward form)
 template <class P, int CLS, int D, bool XB>
 void launch1_d(const typename P::Args& a, int blocks, hipStream_t s, int form) {
-  constexpr bool DEF = row_epilogue_default(CLS);
-  if (row_epilogue(CLS) == DEF) return launch1_f<P, D, XB, DEF>(a, blocks, s, form);
-  if constexpr (D == 1) {
-    if (form == 0) {
-      gemm_k<P, 0, 1, XB, !DEF><<<blocks, 256, 0, s>>>(a);
-      return;
-    }
-    if (form == 3) {
-      gemm_k<P, 3, 1, XB, !DEF><<<blocks, 256, 0, s>>>(a);
-      return;
-    }
-  }
+  constexpr int DEF = epilogue_default(CLS), O1 = (DEF + 1) % 3, O2 = (DEF + 2) % 3;
+  const int ep = epilogue_kind(CLS);
+  if (ep == DEF) return launch1_f<P, D, XB, DEF>(a, blocks, s, form);
+  if (ep == O1 ? launch1_o<P, D, XB, O1>(a, blocks, s, form) : launch1_o<P, D, XB, O2>(a, blocks, s, form)) return;
   throw std::invalid_argument("f32: a forward class's non-default epilogue is built for forms 0 and 3 at prefetch depth 1");
 }
 template <class P, int CLS, bool XB>
@@ -2113,12 +2195,14 @@ void launch1(const typename P::Args& a, int blocks, hipStream_t s, bool bits = f
 template <class P1, class P2, int D, bool XB>
 void launch2_d(const typename P1::Args& a1, const typename P2::Args& a2, int n1, int nb, const TreeRide& r,
                hipStream_t s) {
-  constexpr bool DEF = row_epilogue_default(1);
+  constexpr int DEF = epilogue_default(1), O1 = (DEF + 1) % 3, O2 = (DEF + 2) % 3;
   const int form = (stage_split_mask() >> 2) & 3;
-  if (row_epilogue(1) != DEF) {
+  const int ep = epilogue_kind(1);
+  if (ep != DEF) {
     if constexpr (D == 1) {
       if (form == 3) {
-        gemm2_k<P1, P2, 3, 1, XB, !DEF><<<nb, 256, 0, s>>>(a1, a2, n1, r);
+        if (ep == O1) gemm2_k<P1, P2, 3, 1, XB, O1><<<nb, 256, 0, s>>>(a1, a2, n1, r);
+        else gemm2_k<P1, P2, 3, 1, XB, O2><<<nb, 256, 0, s>>>(a1, a2, n1, r);
         return;
       }
     }
@@ -2176,7 +2260,7 @@ void f32_set_stage_split(int mask) { g_stage_split = mask; }
 int f32_stage_split() { return stage_split_mask(); }
 void f32_set_prefetch(int mask) { g_prefetch = mask; }
 int f32_prefetch() { return prefetch_mask(); }
-void f32_set_epilogue(int mask) { g_epilogue = mask < 0 ? -1 : mask & 7; }
+void f32_set_epilogue(int mask) { g_epilogue = mask < 0 ? -1 : mask & 63; }
 int f32_epilogue() { return epilogue_mask(); }
 void f32_set_batch_resolve(int mask) { g_batch_resolve = mask < 0 ? -1 : mask & 3; }
 int f32_batch_resolve() { return batch_resolve_mask(); }

@@ -513,9 +513,11 @@ void f32_set_prefetch(int mask);
 int f32_prefetch();
 // GEMM epilogue per launch class: bit 0 = learner-sized forward, bit 1 = backward pairs, bit 2 =
 // small forward; set = the row-owned epilogue (16-byte stores), clear = the element epilogue;
-// unset (< 0) reads APEX_F32_EPILOGUE (default 1: profiles/epilogue_rows.md).  A class's
-// non-default epilogue exists for the default forms at prefetch depth 1 only (a launch throws
-// elsewhere).  Bit-identical results; read at launch (graphs keep the epilogue they captured).
+// bits 3-5 = the same classes on the line-owned epilogue (row-owned values transposed through LDS,
+// whole 128-byte lines per store instruction; it overrides the class's low bit);
+// unset (< 0) reads APEX_F32_EPILOGUE (default 56: profiles/epilogue_rows.md, epilogue_lines.md).
+// A class's non-default epilogues exist for the default forms at prefetch depth 1 only (a launch
+// throws elsewhere).  Bit-identical results; read at launch (graphs keep the epilogue they captured).
 void f32_set_epilogue(int mask);
 int f32_epilogue();
 // What the draw / the forward of the gradient pass resolve once for the backward: mask = 1 (the

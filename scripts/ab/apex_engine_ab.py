@@ -12,7 +12,10 @@ A variant is a comma-separated list of overrides ('-' = the defaults):
   br=MASK        APEX_F32_BATCH_RESOLVE: 1 = ReLU sign bits for the input gradients + 2 = the drawn
                  batch's compact rows (default 1; 0 = the fp32 masks and the idx lookups)
   ep=MASK        APEX_F32_EPILOGUE: 1 = row-owned GEMM epilogue of the learner-sized forward + 2 = of
-                 the backward pairs + 4 = of the small forward launches (default 1)
+                 the backward pairs + 4 = of the small forward launches; 8 / 16 / 32 = the same
+                 classes on the line-owned epilogue (whole-line stores via an LDS transpose; it
+                 overrides the class's low bit) (default 56)
+  ext=DIR        APEX_HIP_EXT_DIR: load the kernel library of another build (e.g. the parent's)
   env:NAME=VAL   any other environment variable
   arg:--flag[=VAL]  a bench.py flag (e.g. arg:--actor-at=loss)
 e.g. ``python scripts/ab/apex_engine_ab.py - ss=4 ss=8 ss=8,arg:--actor-at=loss``.
@@ -44,6 +47,8 @@ def run(variant: str, steps: int, warmup: int, timeout: float) -> float:
             env["APEX_F32_BATCH_RESOLVE"] = item[3:]
         elif item.startswith("ep="):
             env["APEX_F32_EPILOGUE"] = item[3:]
+        elif item.startswith("ext="):
+            env["APEX_HIP_EXT_DIR"] = os.path.abspath(item[4:])
         elif item.startswith("env:"):
             k, v = item[4:].split("=", 1)
             env[k] = v
