@@ -26,11 +26,9 @@
 //     chunks; LDS double buffer + register prefetch of the next k-block (one barrier per
 //     k-block; a sched_barrier pins the prefetch ahead of the MFMA block, otherwise the
 //     scheduler sinks late-needed loads next to their LDS store and exposes their latency);
-//     pitches padded so the fragment reads are bank-conflict free.  The prefetch is a ring of
-//     D register stages (gemm_body<P, SS, D>, APEX_F32_PREFETCH): D = 2, 3 keep two or three
-//     k-blocks of loads in flight.  Every launch class runs D = 1: deeper rings measured
-//     slower or equal per launch and per step (profiles/r7_prefetch_ring.md) -- the waits of
-//     these GEMMs are not load latency.
+//     pitches padded so the fragment reads are bank-conflict free.  (A ring of two or three
+//     prefetched k-blocks measured slower or equal and was retired:
+//     profiles/gemm_variants_retired.md.)
 //   * k-chunk mapping: for a chunk of 8 k, lane (r = l & 31, h = l >> 5) holds elements
 //     k = 4h .. 4h+3 of its A row / B column (one ds_read_b128 when K-major, four ds_read_b32
 //     when MN-major); MFMA i of the chunk consumes element i of both -- the 32x32x2 MFMA's
@@ -62,6 +60,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <stdexcept>
 #include <type_traits>
 
 #include "common.h"
@@ -329,15 +328,12 @@ __device__ __forceinline__ uint2 ds_tr16(const char* p) {
 // fp32-MFMA form (v_mfma_f32_32x32x2_f32) it replaced in round 5 ran 2142 vs 2378 learner
 // steps/s at the same fp32-class accuracy (profiles/r5_x6.md, tests/test_gpu_f32_net.py).
 //
-// D = prefetch depth: a ring of D register stages.  The loads of k-block kb + D are issued
-// before compute(kb) and the LDS store after it takes k-block kb + 1, which has then had D - 1
-// whole iterations to land (D = 1: the one-block-ahead prefetch).  The k loop is unrolled by D so
-// every stage index is a compile-time constant (a runtime-indexed register array would live in
-// scratch).  For D > 1 the loads past the last k-block are issued unconditionally and never
-// stored -- a guarded prefetch makes the compiler drain with vmcnt(0): raw-buffer row loads may
-// run past the operand's range (zeros, or other bytes of the same operand), the other loaders
-// get the k-block index clamped to the last one.  Same k order, same staged values, same MFMA
-// k-slots at every depth: bit-identical results (tests/test_gpu_f32_prefetch.py).
+// SS: 0 = the register split and 1 = the stage split on an LDS double buffer (the next k-block is
+// stored into the other image while this one computes, one barrier per k-block), 2 = the stage
+// split on one image (the next k-block waits in registers and is stored after a second barrier).
+// The loads of k-block kb + 1 are issued before compute(kb) in all three.  Same k order, same
+// staged values, same MFMA k-slots: bit-identical results (tests/test_gpu_f32_net.py,
+// tests/test_gpu_f32_kloop_edges.py).
 // XB: the launch carries sign bits (a kernel of its own: with the hooks compiled into the plain
 // kernels behind a null-pointer test, those ran 1.3 % slower per step with every pointer null).
 // EP: the epilogue (APEX_F32_EPILOGUE picks per launch class): 0 = the element epilogue, 1 = the
@@ -349,7 +345,7 @@ constexpr int kEpElem = 0, kEpRow = 1, kEpLine = 2;
 constexpr int kLineLdsFloats = 4 * 1024;
 template <class P, int SS, int EP>
 struct LdsFloats;
-template <class P, int SS, int D, bool XB = false, int EP = kEpRow>
+template <class P, int SS, bool XB = false, int EP = kEpRow>
 __device__ __forceinline__ void gemm_body(const typename P::Args& args, int block, float* lds,
                                           typename P::Smem& sm) {
   using G = Geo<P>;
@@ -371,8 +367,7 @@ __device__ __forceinline__ void gemm_body(const typename P::Args& args, int bloc
     for (int j = 0; j < G::TN; ++j)
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-  static_assert(D >= 1 && D <= 3, "prefetch depth");
-  f32x4 ra[D][G::NA], rb[D][G::NB];
+  f32x4 ra[G::NA], rb[G::NB];
   f32x4 csum = zero4();
   typename RowAOf<P>::type rowa[G::NA];
   typename RowBOf<P>::type rowb[G::NB];
@@ -400,24 +395,21 @@ __device__ __forceinline__ void gemm_body(const typename P::Args& args, int bloc
         mw[mi][ni] = P::mask_word(args, ctx, wm * G::WTM + mi * 32 + r, wn * G::WTN + ni * 32);
   }
 
-  auto gload = [&](int kbr, auto S) {
-    constexpr int st = decltype(S)::value;
-    // pointer loaders (no raw-buffer range check): a k-block past the end reloads the last one
-    const int kbc = D > 1 ? min(kbr, ctx.kb1 - 1) : kbr;
+  auto gload = [&](int kbr) {
 #pragma unroll
     for (int j = 0; j < G::NA; ++j) {
       const int q = t + 256 * j;
       if (G::CA % 256 == 0 || q < G::CA) {
-        if constexpr (HasRowA<P>::value) ra[st][j] = P::load_a_row(args, ctx, rowa[j], kbr);
-        else ra[st][j] = P::load_a(args, ctx, sm, kbc, q / G::RA, q % G::RA);
+        if constexpr (HasRowA<P>::value) ra[j] = P::load_a_row(args, ctx, rowa[j], kbr);
+        else ra[j] = P::load_a(args, ctx, sm, kbr, q / G::RA, q % G::RA);
       }
     }
 #pragma unroll
     for (int j = 0; j < G::NB; ++j) {
       const int q = t + 256 * j;
       if (G::CB % 256 == 0 || q < G::CB) {
-        if constexpr (HasRowB<P>::value) rb[st][j] = P::load_b_row(args, ctx, rowb[j], kbr);
-        else rb[st][j] = P::load_b(args, ctx, sm, kbc, q / G::RB, q % G::RB);
+        if constexpr (HasRowB<P>::value) rb[j] = P::load_b_row(args, ctx, rowb[j], kbr);
+        else rb[j] = P::load_b(args, ctx, sm, kbr, q / G::RB, q % G::RB);
       }
     }
   };
@@ -441,8 +433,7 @@ __device__ __forceinline__ void gemm_body(const typename P::Args& args, int bloc
     *reinterpret_cast<uint2*>(base + plane + off) = mi;
     *reinterpret_cast<uint2*>(base + 2 * plane + off) = lo;
   };
-  auto sstore = [&](int buf, auto S) {
-    constexpr int st = decltype(S)::value;
+  auto sstore = [&](int buf) {
     if constexpr (SS) {
       char* As = reinterpret_cast<char*>(lds) + buf * (GS::SA + GS::SB);
       char* Bs = As + GS::SA;
@@ -454,14 +445,14 @@ __device__ __forceinline__ void gemm_body(const typename P::Args& args, int bloc
       for (int j = 0; j < G::NA; ++j) {
         const int q = t + 256 * j;
         if (G::CA % 256 == 0 || q < G::CA) {
-          ss_store(As, GS::PLA, KA{}, WA{}, G::RA, q, ra[st][j]);
-          if constexpr (COLSUM) csum += ra[st][j];
+          ss_store(As, GS::PLA, KA{}, WA{}, G::RA, q, ra[j]);
+          if constexpr (COLSUM) csum += ra[j];
         }
       }
 #pragma unroll
       for (int j = 0; j < G::NB; ++j) {
         const int q = t + 256 * j;
-        if (G::CB % 256 == 0 || q < G::CB) ss_store(Bs, GS::PLB, KB{}, WB{}, G::RB, q, rb[st][j]);
+        if (G::CB % 256 == 0 || q < G::CB) ss_store(Bs, GS::PLB, KB{}, WB{}, G::RB, q, rb[j]);
       }
       return;
     }
@@ -471,18 +462,17 @@ __device__ __forceinline__ void gemm_body(const typename P::Args& args, int bloc
     for (int j = 0; j < G::NA; ++j) {
       const int q = t + 256 * j;
       if (G::CA % 256 == 0 || q < G::CA) {
-        *reinterpret_cast<f32x4*>(As + (q / G::RA) * G::PA + 4 * (q % G::RA)) = ra[st][j];
-        if constexpr (COLSUM) csum += ra[st][j];
+        *reinterpret_cast<f32x4*>(As + (q / G::RA) * G::PA + 4 * (q % G::RA)) = ra[j];
+        if constexpr (COLSUM) csum += ra[j];
       }
     }
 #pragma unroll
     for (int j = 0; j < G::NB; ++j) {
       const int q = t + 256 * j;
       if (G::CB % 256 == 0 || q < G::CB)
-        *reinterpret_cast<f32x4*>(Bs + (q / G::RB) * G::PB + 4 * (q % G::RB)) = rb[st][j];
+        *reinterpret_cast<f32x4*>(Bs + (q / G::RB) * G::PB + 4 * (q % G::RB)) = rb[j];
     }
   };
-  using S0 = std::integral_constant<int, 0>;
   // the cross terms accumulate apart from hi.hi (summed in the epilogue)
   f32x16 accx[G::TM][G::TN];
 #pragma unroll
@@ -610,94 +600,37 @@ __device__ __forceinline__ void gemm_body(const typename P::Args& args, int bloc
     }
   };
 
-  using S1 = std::integral_constant<int, 1 % D>;
-  using S2 = std::integral_constant<int, 2 % D>;
   int kb = ctx.kb0;
-  int cur = 0;
   if (kb < ctx.kb1) {  // block-uniform (a workgroup without k-blocks loads nothing)
-    gload(kb, S0{});
-    if constexpr (D >= 2) gload(kb + 1, S1{});
-    if constexpr (D >= 3) gload(kb + 2, S2{});
-    sstore(0, S0{});
+    gload(kb);
+    sstore(0);
   }
   __syncthreads();
-  if constexpr (D == 1) {
-    if constexpr (SS == 2) {  // one LDS image (half the footprint): the next k-block waits in
-                              // registers and is stored after a second barrier
-      for (; kb < ctx.kb1; ++kb) {
-        const bool more = kb + 1 < ctx.kb1;
-        if (more) gload(kb + 1, S0{});
-        __builtin_amdgcn_sched_barrier(0);
-        compute(0);
-        if (more) {
-          __syncthreads();
-          sstore(0, S0{});
-        }
-        __syncthreads();
-      }
-    } else
+  if constexpr (SS == 2) {
     for (; kb < ctx.kb1; ++kb) {
       const bool more = kb + 1 < ctx.kb1;
-      if (more) gload(kb + 1, S0{});
+      if (more) gload(kb + 1);
+      __builtin_amdgcn_sched_barrier(0);
+      compute(0);
+      if (more) {  // the one image is free once every wave has read its fragments
+        __syncthreads();
+        sstore(0);
+      }
+      __syncthreads();
+    }
+  } else {
+    int cur = 0;
+    for (; kb < ctx.kb1; ++kb) {
+      const bool more = kb + 1 < ctx.kb1;
+      if (more) gload(kb + 1);
       // every MFMA of the block is issued before the LDS store waits on the next block's
       // global loads: unfenced, the scheduler sinks late-needed loads next to their store and
       // exposes their latency
       __builtin_amdgcn_sched_barrier(0);
       compute(cur);
-      if (more) sstore(cur ^ 1, S0{});
+      if (more) sstore(cur ^ 1);
       __syncthreads();
       cur ^= 1;
-    }
-  } else {
-    // The ring loop has no exit and no condition inside an iteration of D k-blocks: it runs
-    // while all D stores of the iteration are needed, and the last 1..D k-blocks (already in
-    // LDS / in the stages, at compile-time indices: every iteration restores the ring's
-    // alignment) drain in a tail that loads nothing.  (With a skippable store or a mid-iteration
-    // exit the compiler guards the next overwrite of a stage with a near-full vmcnt drain at
-    // the head of every iteration.)
-    // one k-block: LDS holds kb; its MFMAs, then stage SN (k-block kb + 1) goes to LDS
-    auto mma = [&]() {
-      __builtin_amdgcn_sched_barrier(0);
-      compute(SS == 2 ? 0 : cur);
-    };
-    auto next = [&](auto SN) {
-      if constexpr (SS == 2) {
-        __syncthreads();
-        sstore(0, SN);
-      } else {
-        sstore(cur ^ 1, SN);
-        cur ^= 1;
-      }
-      __syncthreads();
-      ++kb;
-    };
-    if (kb < ctx.kb1) {
-      while (kb + D < ctx.kb1) {  // stage SL is free (stored an iteration ago) and takes kb + D
-        gload(kb + D, S0{});
-        mma();
-        next(S1{});
-        gload(kb + D, S1{});
-        mma();
-        next(S2{});
-        if constexpr (D >= 3) {
-          gload(kb + D, S2{});
-          mma();
-          next(S0{});
-        }
-      }
-      const int m = ctx.kb1 - kb;  // 1..D k-blocks left
-      mma();
-      if (m >= 2) {
-        next(S1{});
-        mma();
-        if constexpr (D >= 3) {
-          if (m >= 3) {
-            next(S2{});
-            mma();
-          }
-        }
-      }
-      __syncthreads();  // (the column-sum epilogue reuses the LDS tile)
     }
   }
 #pragma unroll
@@ -920,20 +853,20 @@ struct BodyForm {
   static constexpr int value = SS == 3 ? 2 : SS;
 };
 
-template <class P, int SS, int D, bool XB = false, int EP = kEpRow>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SS == 3 || D > 1 ? 3 : 1))) void gemm_k(
+template <class P, int SS, bool XB = false, int EP = kEpRow>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SS == 3 ? 3 : 1))) void gemm_k(
     typename P::Args args) {
   __shared__ __attribute__((aligned(16))) float lds[LdsFloats<P, SS, EP>::value];
   __shared__ typename P::Smem sm;
-  gemm_body<P, BodyForm<SS>::value, D, XB, EP>(args, xcd_chunk(blockIdx.x, gridDim.x), lds, sm);
+  gemm_body<P, BodyForm<SS>::value, XB, EP>(args, xcd_chunk(blockIdx.x, gridDim.x), lds, sm);
 }
 
 // Two independent GEMMs in one launch: blocks [0, n1) run P1, the rest P2 (P1 first: the
 // longer per-block problem starts early).
 // r (stage > 0): the learner's priority-tree write riding the launch as extra workgroups
 // (tree_dev.h tree_ride: the leaves in block 0, a level's recompute past the GEMM tiles).
-template <class P1, class P2, int SS, int D, bool XB = false, int EP = kEpRow>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SS == 3 || D > 1 ? 3 : 1))) void gemm2_k(
+template <class P1, class P2, int SS, bool XB = false, int EP = kEpRow>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SS == 3 ? 3 : 1))) void gemm2_k(
     typename P1::Args a1, typename P2::Args a2, int n1, TreeRide r) {
   __shared__ __attribute__((aligned(16))) float lds[MaxI<LdsFloats<P1, SS, EP>::value, LdsFloats<P2, SS, EP>::value>::value];
   __shared__ union {
@@ -943,9 +876,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SS == 3 || 
   int b = blockIdx.x;
   if (r.stage && tree_ride(r, r.nhost, lds, &b)) return;  // (grid-uniform stage, block-uniform role)
   if (b < n1)
-    gemm_body<P1, BodyForm<SS>::value, D, XB, EP>(a1, b, lds, sm.s1);
+    gemm_body<P1, BodyForm<SS>::value, XB, EP>(a1, b, lds, sm.s1);
   else
-    gemm_body<P2, BodyForm<SS>::value, D, XB, EP>(a2, b - n1, lds, sm.s2);
+    gemm_body<P2, BodyForm<SS>::value, XB, EP>(a2, b - n1, lds, sm.s2);
 }
 
 __device__ __forceinline__ F32Prob pick(const F32Set& s, int i) {
@@ -953,18 +886,46 @@ __device__ __forceinline__ F32Prob pick(const F32Set& s, int i) {
 }
 
 // ------------------------------------------------------------------ forward policies
-template <int BM_, int BN_, int BK_, int WM_>
-struct Conv2FwdT {  // a2 = relu(conv(a1, W2) + b2); k = (ky, kx, ci) = tap * 32 + ci; w = w2p
-  static constexpr int BM = BM_, BN = BN_, BK = BK_, WM = WM_;
-  static constexpr bool A_KMAJ = true, B_KMAJ = true, SMEM = false;
-  static_assert(512 % BK == 0 && BN <= 64, "k-blocks tile K = 512");
+// The tile context and the output hooks of the forward policies with a 64-channel output
+// (conv2, conv3): out[m][64] = relu(acc + bias), M rows
+struct FwdOut64 {
   using Args = F32Set;
-  using Smem = NoSmem;
   struct Ctx {
     F32Prob p;
     int M, m0, n0, kb0, kb1;
     Rsrc in, w;
   };
+  static __device__ float stored(const Args&, const Ctx& c, int n, float v) {
+    return fmaxf(v + c.p.bias[c.n0 + n], 0.f);
+  }
+  static __device__ void store(const Args& a, const Ctx& c, int ml, int n, float v) {
+    const int m = c.m0 + ml;
+    if (m < c.M) c.p.out[(size_t)m * 64 + c.n0 + n] = stored(a, c, n, v);
+  }
+  static constexpr bool FIN4 = true;
+  static __device__ float* out_row(const Args&, const Ctx& c, int ml) {
+    const int m = c.m0 + ml;
+    return m < c.M ? c.p.out + (size_t)m * 64 + c.n0 : nullptr;
+  }
+  static __device__ f32x4 fin4(const Args&, const Ctx& c, int n, f32x4 v) {
+    const f32x4 b = ld4(c.p.bias + c.n0 + n);
+    return f32x4{fmaxf(v[0] + b[0], 0.f), fmaxf(v[1] + b[1], 0.f), fmaxf(v[2] + b[2], 0.f), fmaxf(v[3] + b[3], 0.f)};
+  }
+  // sign bits [M][2]: word (n0 + nl0) / 32 of row m (gemm_body's HasReluBits epilogue)
+  static constexpr bool RELU_BITS = true;
+  static __device__ bool want_bits(const Ctx& c) { return c.p.relu_bits != nullptr; }
+  static __device__ uint32_t* bits_ptr(const Ctx& c, int ml, int nl0) {
+    const int m = c.m0 + ml;
+    return m < c.M ? c.p.relu_bits + (size_t)m * 2 + ((c.n0 + nl0) >> 5) : nullptr;
+  }
+};
+
+template <int BM_, int BN_, int BK_, int WM_>
+struct Conv2FwdT : FwdOut64 {  // a2 = relu(conv(a1, W2) + b2); k = (ky, kx, ci) = tap * 32 + ci; w = w2p
+  static constexpr int BM = BM_, BN = BN_, BK = BK_, WM = WM_;
+  static constexpr bool A_KMAJ = true, B_KMAJ = true, SMEM = false;
+  static_assert(512 % BK == 0 && BN <= 64, "k-blocks tile K = 512");
+  using Smem = NoSmem;
   static constexpr int NT = 64 / BN;
   static __host__ __device__ int tiles(int B) { return NT * ((B * 81 + BM - 1) / BM); }
   static __device__ void decode(const Args& a, int block, Ctx& c, Smem&) {
@@ -1011,43 +972,14 @@ struct Conv2FwdT {  // a2 = relu(conv(a1, W2) + b2); k = (ky, kx, ci) = tap * 32
   static __device__ f32x4 load_b_row(const Args&, const Ctx& c, const RowB& r, int kb) {
     return bld4(c.w, r.off + (uint32_t)(kb * BK * 4));
   }
-  static __device__ float stored(const Args&, const Ctx& c, int n, float v) {
-    return fmaxf(v + c.p.bias[c.n0 + n], 0.f);
-  }
-  static __device__ void store(const Args& a, const Ctx& c, int ml, int n, float v) {
-    const int m = c.m0 + ml;
-    if (m < c.M) c.p.out[(size_t)m * 64 + c.n0 + n] = stored(a, c, n, v);
-  }
-  static constexpr bool FIN4 = true;
-  static __device__ float* out_row(const Args&, const Ctx& c, int ml) {
-    const int m = c.m0 + ml;
-    return m < c.M ? c.p.out + (size_t)m * 64 + c.n0 : nullptr;
-  }
-  static __device__ f32x4 fin4(const Args&, const Ctx& c, int n, f32x4 v) {
-    const f32x4 b = ld4(c.p.bias + c.n0 + n);
-    return f32x4{fmaxf(v[0] + b[0], 0.f), fmaxf(v[1] + b[1], 0.f), fmaxf(v[2] + b[2], 0.f), fmaxf(v[3] + b[3], 0.f)};
-  }
-  // sign bits [M][2]: word (n0 + nl0) / 32 of row m (gemm_body's HasReluBits epilogue)
-  static constexpr bool RELU_BITS = true;
-  static __device__ bool want_bits(const Ctx& c) { return c.p.relu_bits != nullptr; }
-  static __device__ uint32_t* bits_ptr(const Ctx& c, int ml, int nl0) {
-    const int m = c.m0 + ml;
-    return m < c.M ? c.p.relu_bits + (size_t)m * 2 + ((c.n0 + nl0) >> 5) : nullptr;
-  }
 };
 
 template <int BM_, int BN_, int BK_, int WM_>
-struct Conv3FwdT {  // a3 = relu(conv(a2, W3) + b3); k = tap * 64 + ci; w = w3p
+struct Conv3FwdT : FwdOut64 {  // a3 = relu(conv(a2, W3) + b3); k = tap * 64 + ci; w = w3p
   static constexpr int BM = BM_, BN = BN_, BK = BK_, WM = WM_;
   static constexpr bool A_KMAJ = true, B_KMAJ = true, SMEM = false;
   static_assert(576 % BK == 0 && 64 % BK == 0 || BK == 64, "a k-block stays inside one tap");
-  using Args = F32Set;
   using Smem = NoSmem;
-  struct Ctx {
-    F32Prob p;
-    int M, m0, n0, kb0, kb1;
-    Rsrc in, w;
-  };
   static constexpr int NT = 64 / BN;
   static __host__ __device__ int tiles(int B) { return NT * ((B * 49 + BM - 1) / BM); }
   static __device__ void decode(const Args& a, int block, Ctx& c, Smem&) {
@@ -1092,29 +1024,6 @@ struct Conv3FwdT {  // a3 = relu(conv(a2, W3) + b3); k = tap * 64 + ci; w = w3p
   }
   static __device__ f32x4 load_b_row(const Args&, const Ctx& c, const RowB& r, int kb) {
     return bld4(c.w, r.off + (uint32_t)(kb * BK * 4));
-  }
-  static __device__ float stored(const Args&, const Ctx& c, int n, float v) {
-    return fmaxf(v + c.p.bias[c.n0 + n], 0.f);
-  }
-  static __device__ void store(const Args& a, const Ctx& c, int ml, int n, float v) {
-    const int m = c.m0 + ml;
-    if (m < c.M) c.p.out[(size_t)m * 64 + c.n0 + n] = stored(a, c, n, v);
-  }
-  static constexpr bool FIN4 = true;
-  static __device__ float* out_row(const Args&, const Ctx& c, int ml) {
-    const int m = c.m0 + ml;
-    return m < c.M ? c.p.out + (size_t)m * 64 + c.n0 : nullptr;
-  }
-  static __device__ f32x4 fin4(const Args&, const Ctx& c, int n, f32x4 v) {
-    const f32x4 b = ld4(c.p.bias + c.n0 + n);
-    return f32x4{fmaxf(v[0] + b[0], 0.f), fmaxf(v[1] + b[1], 0.f), fmaxf(v[2] + b[2], 0.f), fmaxf(v[3] + b[3], 0.f)};
-  }
-  // sign bits [M][2]: word (n0 + nl0) / 32 of row m (gemm_body's HasReluBits epilogue)
-  static constexpr bool RELU_BITS = true;
-  static __device__ bool want_bits(const Ctx& c) { return c.p.relu_bits != nullptr; }
-  static __device__ uint32_t* bits_ptr(const Ctx& c, int ml, int nl0) {
-    const int m = c.m0 + ml;
-    return m < c.M ? c.p.relu_bits + (size_t)m * 2 + ((c.n0 + nl0) >> 5) : nullptr;
   }
 };
 
@@ -2059,32 +1968,34 @@ SplitPlan wgrad_plan(int layer, int B, int target) {
   }
 }
 
-// GEMM form per direction, read at launch time (a captured graph keeps the form it was
+// GEMM form per launch class, read at launch time (a captured graph keeps the form it was
 // captured with): mask = forward form + 4 x backward-pair form (+ 16 x (1 + form) of the
 // forward launches below the learner's size, the actor's; unset = the forward form), form 0 =
 // register split, 1 = stage-split (double-buffered LDS image), 2 = stage-split, single LDS
 // image, 3 = form 2 held to >= 3 waves per SIMD.  Every form gives bit-identical results.
+// The prefetch ring that had a mask beside this one was retired
+// (profiles/gemm_variants_retired.md): its environment variable, read once, makes every read of
+// the form mask -- every GEMM launch -- throw rather than be ignored, whoever set the mask.
 int g_stage_split = -1;
 int stage_split_mask() {
+  static const bool ring_asked = [] {
+    const char* pf = std::getenv("APEX_F32_PREFETCH");
+    return pf && std::atoi(pf) != 0;
+  }();
+  if (ring_asked)
+    throw std::invalid_argument("APEX_F32_PREFETCH: the fp32 GEMMs' prefetch ring was retired "
+                                "(profiles/gemm_variants_retired.md)");
   if (g_stage_split < 0) {
     const char* e = std::getenv("APEX_F32_STAGE_SPLIT");
     g_stage_split = e ? std::atoi(e) : kStageSplitDefault;
   }
   return g_stage_split;
 }
-
-// Prefetch depth of the GEMM bodies per launch class, read at launch time (a captured graph
-// keeps the depth it was captured with): mask = (D - 1) of the learner-sized forward launches
-// + 4 x (D - 1) of the backward pairs + 16 x (D - 1) of the forward launches below the learner's
-// size (the actor's / evaluator's), D = 1..3.  Every depth gives bit-identical results.
-constexpr int kPrefetchDefault = 0;
-int g_prefetch = -1;
-int prefetch_mask() {
-  if (g_prefetch < 0) {
-    const char* e = std::getenv("APEX_F32_PREFETCH");
-    g_prefetch = e ? std::atoi(e) : kPrefetchDefault;
-  }
-  return g_prefetch;
+// cls: 0 = learner-sized forward, 1 = backward pair, 2 = small forward
+int form_of(int cls) {
+  const int m = stage_split_mask();
+  if (cls == 2 && ((m >> 4) & 3)) return ((m >> 4) & 3) - 1;
+  return (m >> (cls == 1 ? 2 : 0)) & 3;
 }
 // What is resolved once for the backward (kernels.h f32_set_batch_resolve): 1 = ReLU sign bits,
 // 2 = the drawn batch's compact rows; consulted by the callers that wire the pointers.  Whole step,
@@ -2108,9 +2019,8 @@ int batch_resolve_mask() {
 // 16-byte stores, 32 rows x 32 bytes per instruction), clear = the element epilogue (one dword per
 // lane and store).  Values 0-7 mean what they meant before the line-owned epilogue existed.
 // Bit-identical results (tests/test_gpu_f32_epilogue.py, tests/test_gpu_f32_epilogue_lines.py).
-// A class's DEFAULT epilogue is built for every form and depth, its other two only for the forms
-// the defaults run (forward: 0 and 3, backward pairs: 3) at depth 1 -- asking for one elsewhere
-// throws.  Whole step on one box, builds and masks alternated in separate processes:
+// Every class is built with all three at every form.  Whole step on one box, builds and masks
+// alternated in separate processes:
 // row-owned against element (profiles/epilogue_rows.md): the learner-sized forward +3.7 %, the
 // backward pairs lose (32 rows x 32 bytes per store instruction against 2 rows x 128), the small
 // launches inside the noise.  Line-owned (profiles/epilogue_lines.md): every class on it reads
@@ -2131,98 +2041,42 @@ constexpr int epilogue_of(int mask, int cls) {
   return (mask >> (3 + cls)) & 1 ? kEpLine : ((mask >> cls) & 1 ? kEpRow : kEpElem);
 }
 int epilogue_kind(int cls) { return epilogue_of(epilogue_mask(), cls); }
-constexpr int epilogue_default(int cls) { return epilogue_of(kEpilogueDefault, cls); }
-int prefetch_depth(int cls) { return std::min(3, 1 + ((prefetch_mask() >> (2 * cls)) & 3)); }
 
-template <class P, int D, bool XB, int EP>
-void launch1_f(const typename P::Args& a, int blocks, hipStream_t s, int form) {
-  switch (form) {
-    case 1: gemm_k<P, 1, D, XB, EP><<<blocks, 256, 0, s>>>(a); break;
-    case 2: gemm_k<P, 2, D, XB, EP><<<blocks, 256, 0, s>>>(a); break;
-    case 3: gemm_k<P, 3, D, XB, EP><<<blocks, 256, 0, s>>>(a); break;
-    default: gemm_k<P, 0, D, XB, EP><<<blocks, 256, 0, s>>>(a);
+// The run-time (form, epilogue) pair of a launch class as compile-time constants: f(SS, EP) with
+// two std::integral_constant<int>, every class built for all twelve.
+template <class F>
+void with_form_epilogue(int cls, F&& f) {
+  const int ep = epilogue_kind(cls);
+  auto with_ep = [&](auto SS) {
+    switch (ep) {
+      case kEpElem: f(SS, std::integral_constant<int, kEpElem>{}); break;
+      case kEpRow: f(SS, std::integral_constant<int, kEpRow>{}); break;
+      default: f(SS, std::integral_constant<int, kEpLine>{});
+    }
+  };
+  switch (form_of(cls)) {
+    case 1: with_ep(std::integral_constant<int, 1>{}); break;
+    case 2: with_ep(std::integral_constant<int, 2>{}); break;
+    case 3: with_ep(std::integral_constant<int, 3>{}); break;
+    default: with_ep(std::integral_constant<int, 0>{});
   }
 }
-// a forward class's non-default epilogue EP (forms 0 and 3, depth 1); false: not built
-template <class P, int D, bool XB, int EP>
-bool launch1_o(const typename P::Args& a, int blocks, hipStream_t s, int form) {
-  if constexpr (D == 1) {
-    if (form == 0) {
-      gemm_k<P, 0, 1, XB, EP><<<blocks, 256, 0, s>>>(a);
-      return true;
-    }
-    if (form == 3) {
-      gemm_k<P, 3, 1, XB, EP><<<blocks, 256, 0, s>>>(a);
-      return true;
-    }
-  }
-  return false;
-}
+
 // CLS 0: a learner-sized forward launch; CLS 2: a launch below the learner's size (the actor's /
-// evaluator's forward) -- bits 4-5 of the form mask, when set, give those launches a form of their
-// own (form + 1; 0 = the forward form)
-template <class P, int CLS, int D, bool XB>
-void launch1_d(const typename P::Args& a, int blocks, hipStream_t s, int form) {
-  constexpr int DEF = epilogue_default(CLS), O1 = (DEF + 1) % 3, O2 = (DEF + 2) % 3;
-  const int ep = epilogue_kind(CLS);
-  if (ep == DEF) return launch1_f<P, D, XB, DEF>(a, blocks, s, form);
-  if (ep == O1 ? launch1_o<P, D, XB, O1>(a, blocks, s, form) : launch1_o<P, D, XB, O2>(a, blocks, s, form)) return;
-  throw std::invalid_argument("f32: a forward class's non-default epilogue is built for forms 0 and 3 at prefetch depth 1");
-}
-template <class P, int CLS, bool XB>
-void launch1_x(const typename P::Args& a, int blocks, hipStream_t s) {
-  const int m = stage_split_mask();
-  const int form = CLS == 2 && ((m >> 4) & 3) ? ((m >> 4) & 3) - 1 : m & 3;
-  switch (prefetch_depth(CLS)) {
-    case 2: launch1_d<P, CLS, 2, XB>(a, blocks, s, form); break;
-    case 3: launch1_d<P, CLS, 3, XB>(a, blocks, s, form); break;
-    default: launch1_d<P, CLS, 1, XB>(a, blocks, s, form);
-  }
-}
+// evaluator's forward)
 // bits: the launch writes ReLU sign bits (policies with the hook: the kernels compiled with it)
 template <class P, int CLS>
 void launch1(const typename P::Args& a, int blocks, hipStream_t s, bool bits = false) {
   if (blocks <= 0) return;
-  if constexpr (HasReluBits<P>::value) {
-    if (bits) launch1_x<P, CLS, true>(a, blocks, s);
-    else launch1_x<P, CLS, false>(a, blocks, s);
-  } else {
-    launch1_x<P, CLS, false>(a, blocks, s);
-  }
-  LAUNCH_CHECK();
-}
-
-template <class P1, class P2, int D, bool XB>
-void launch2_d(const typename P1::Args& a1, const typename P2::Args& a2, int n1, int nb, const TreeRide& r,
-               hipStream_t s) {
-  constexpr int DEF = epilogue_default(1), O1 = (DEF + 1) % 3, O2 = (DEF + 2) % 3;
-  const int form = (stage_split_mask() >> 2) & 3;
-  const int ep = epilogue_kind(1);
-  if (ep != DEF) {
-    if constexpr (D == 1) {
-      if (form == 3) {
-        if (ep == O1) gemm2_k<P1, P2, 3, 1, XB, O1><<<nb, 256, 0, s>>>(a1, a2, n1, r);
-        else gemm2_k<P1, P2, 3, 1, XB, O2><<<nb, 256, 0, s>>>(a1, a2, n1, r);
-        return;
-      }
+  with_form_epilogue(CLS, [&](auto SS, auto EP) {
+    constexpr int ss = decltype(SS)::value;
+    constexpr int ep = decltype(EP)::value;
+    if constexpr (HasReluBits<P>::value) {
+      if (bits) return gemm_k<P, ss, true, ep><<<blocks, 256, 0, s>>>(a);
     }
-    throw std::invalid_argument("f32: the backward pairs' non-default epilogue is built for form 3 at prefetch depth 1");
-  }
-  switch (form) {
-    case 1: gemm2_k<P1, P2, 1, D, XB, DEF><<<nb, 256, 0, s>>>(a1, a2, n1, r); break;
-    case 2: gemm2_k<P1, P2, 2, D, XB, DEF><<<nb, 256, 0, s>>>(a1, a2, n1, r); break;
-    case 3: gemm2_k<P1, P2, 3, D, XB, DEF><<<nb, 256, 0, s>>>(a1, a2, n1, r); break;
-    default: gemm2_k<P1, P2, 0, D, XB, DEF><<<nb, 256, 0, s>>>(a1, a2, n1, r);
-  }
-}
-template <class P1, class P2, bool XB>
-void launch2_x(const typename P1::Args& a1, const typename P2::Args& a2, int n1, int nb, const TreeRide& r,
-               hipStream_t s) {
-  switch (prefetch_depth(1)) {
-    case 2: launch2_d<P1, P2, 2, XB>(a1, a2, n1, nb, r, s); break;
-    case 3: launch2_d<P1, P2, 3, XB>(a1, a2, n1, nb, r, s); break;
-    default: launch2_d<P1, P2, 1, XB>(a1, a2, n1, nb, r, s);
-  }
+    gemm_k<P, ss, false, ep><<<blocks, 256, 0, s>>>(a);
+  });
+  LAUNCH_CHECK();
 }
 
 template <class P1, class P2>
@@ -2235,9 +2089,13 @@ void launch2(const typename P1::Args& a1, int n1, const typename P2::Args& a2, i
     r.nhost = n1 + n2;
   }
   const int nb = n1 + n2 + tree_ride_blocks(r);
-  // the input gradient (P2) masks with sign bits: the kernels compiled with that hook
-  if (P2::use_bits(a2)) launch2_x<P1, P2, true>(a1, a2, n1, nb, r, s);
-  else launch2_x<P1, P2, false>(a1, a2, n1, nb, r, s);
+  with_form_epilogue(1, [&](auto SS, auto EP) {
+    constexpr int ss = decltype(SS)::value;
+    constexpr int ep = decltype(EP)::value;
+    // the input gradient (P2) masks with sign bits: the kernels compiled with that hook
+    if (P2::use_bits(a2)) gemm2_k<P1, P2, ss, true, ep><<<nb, 256, 0, s>>>(a1, a2, n1, r);
+    else gemm2_k<P1, P2, ss, false, ep><<<nb, 256, 0, s>>>(a1, a2, n1, r);
+  });
   LAUNCH_CHECK();
 }
 
@@ -2258,8 +2116,6 @@ void fwd_launch(const F32Set& set, hipStream_t s) {
 
 void f32_set_stage_split(int mask) { g_stage_split = mask; }
 int f32_stage_split() { return stage_split_mask(); }
-void f32_set_prefetch(int mask) { g_prefetch = mask; }
-int f32_prefetch() { return prefetch_mask(); }
 void f32_set_epilogue(int mask) { g_epilogue = mask < 0 ? -1 : mask & 63; }
 int f32_epilogue() { return epilogue_mask(); }
 void f32_set_batch_resolve(int mask) { g_batch_resolve = mask < 0 ? -1 : mask & 3; }

@@ -553,8 +553,6 @@ PYBIND11_MODULE(_apex_hip, m) {
   m.def("f32_fc1_splits", &f32_fc1_splits);
   m.def("f32_set_stage_split", &f32_set_stage_split);
   m.def("f32_stage_split", &f32_stage_split);
-  m.def("f32_set_prefetch", &f32_set_prefetch);
-  m.def("f32_prefetch", &f32_prefetch);
   m.def("f32_set_epilogue", &f32_set_epilogue);
   m.def("f32_epilogue", &f32_epilogue);
   m.def("f32_set_batch_resolve", &f32_set_batch_resolve);

@@ -502,22 +502,18 @@ int f32_fc1_splits();
 // GEMM form: mask = forward form + 4 x backward-pair form; form 0 = per-wave register split,
 // 1 = stage-split LDS image (split once per staged element, double-buffered), 2 = the same
 // with one LDS image, 3 = form 2 held to >= 3 waves per SIMD; -1 reads APEX_F32_STAGE_SPLIT.  Bit-identical in every form; read at
-// launch (graphs keep the form they captured).
+// launch (graphs keep the form they captured).  The prefetch ring's knob that stood beside it was
+// retired (profiles/gemm_variants_retired.md): with a non-zero APEX_F32_PREFETCH in the environment
+// f32_stage_split() and every GEMM launch throw std::invalid_argument.
 void f32_set_stage_split(int mask);
 int f32_stage_split();
-// GEMM prefetch depth D = 1..3 (k-blocks of operand loads in flight per workgroup): mask =
-// (D - 1) of the learner-sized forward launches + 4 x (D - 1) of the backward pairs + 16 x
-// (D - 1) of the forward launches below the learner's size; unset reads APEX_F32_PREFETCH.
-// Bit-identical at every depth; read at launch (graphs keep the depth they captured).
-void f32_set_prefetch(int mask);
-int f32_prefetch();
 // GEMM epilogue per launch class: bit 0 = learner-sized forward, bit 1 = backward pairs, bit 2 =
 // small forward; set = the row-owned epilogue (16-byte stores), clear = the element epilogue;
 // bits 3-5 = the same classes on the line-owned epilogue (row-owned values transposed through LDS,
 // whole 128-byte lines per store instruction; it overrides the class's low bit);
 // unset (< 0) reads APEX_F32_EPILOGUE (default 56: profiles/epilogue_rows.md, epilogue_lines.md).
-// A class's non-default epilogues exist for the default forms at prefetch depth 1 only (a launch
-// throws elsewhere).  Bit-identical results; read at launch (graphs keep the epilogue they captured).
+// Every class has all three at every form.  Bit-identical results; read at launch (graphs keep
+// the epilogue they captured).
 void f32_set_epilogue(int mask);
 int f32_epilogue();
 // What the draw / the forward of the gradient pass resolve once for the backward: mask = 1 (the

@@ -7,8 +7,6 @@ as one JSON line.
 A variant is a comma-separated list of overrides ('-' = the defaults):
   ss=MASK        APEX_F32_STAGE_SPLIT: f32 GEMM forms, forward + 4 x backward pairs
                  (0 register split, 1 stage-split, 2 stage-split single LDS image, 3 = 2 at >= 3 waves/SIMD)
-  pf=MASK        APEX_F32_PREFETCH: f32 GEMM prefetch depth D, (D - 1) of the learner's forward
-                 + 4 x (D - 1) of the backward pairs + 16 x (D - 1) of the actor's small launches
   br=MASK        APEX_F32_BATCH_RESOLVE: 1 = ReLU sign bits for the input gradients + 2 = the drawn
                  batch's compact rows (default 1; 0 = the fp32 masks and the idx lookups)
   ep=MASK        APEX_F32_EPILOGUE: 1 = row-owned GEMM epilogue of the learner-sized forward + 2 = of
@@ -41,8 +39,6 @@ def run(variant: str, steps: int, warmup: int, timeout: float) -> float:
     for item in ([] if variant == "-" else variant.split(",")):
         if item.startswith("ss="):
             env["APEX_F32_STAGE_SPLIT"] = item[3:]
-        elif item.startswith("pf="):
-            env["APEX_F32_PREFETCH"] = item[3:]
         elif item.startswith("br="):
             env["APEX_F32_BATCH_RESOLVE"] = item[3:]
         elif item.startswith("ep="):

@@ -6,9 +6,8 @@ three-term split; the percentage is of the 157.3 TF fp32 MFMA peak, for comparis
 
 ``python scripts/bench_f32.py [--B 512] [--iters 50] [--only NAME] [--graph 1]`` prints
 us/launch and achieved TFLOP/s (157.3 TF = fp32 MFMA peak); ``--graph 0`` launches
-eagerly (for rocprofv3 --pmc, one dispatch per launch).  ``--prefetch D`` runs every GEMM at
-prefetch depth D (1..3 k-blocks of operand loads in flight), ``--stage-split MASK`` in the
-given GEMM forms (APEX_F32_STAGE_SPLIT's mask), ``--epilogue MASK`` with the row-owned (bits 0-2 set),
+eagerly (for rocprofv3 --pmc, one dispatch per launch).  ``--stage-split MASK`` runs the GEMMs in the
+given forms (APEX_F32_STAGE_SPLIT's mask), ``--epilogue MASK`` with the row-owned (bits 0-2 set),
 line-owned (bits 3-5 set: 8 / 16 / 32, over the class's low bit) or element epilogue per launch class
 (APEX_F32_EPILOGUE's mask: forward, backward pairs, small forward; 56 = line-owned everywhere),
 ``--sign-bits 1`` with the ReLU sign bits (the conv
@@ -40,16 +39,12 @@ ap.add_argument("--tile2", action="store_true", help="+ forward tiles: conv2 128
 ap.add_argument("--c1-grids", default="", help="extra conv1 forward cases at these workgroup counts")
 ap.add_argument("--wgrad-targets", default="", help="extra conv2/conv3 backward cases at these wgrad workgroup "
                                                     "targets, e.g. 512,1024 (default plan: the plain cases)")
-ap.add_argument("--prefetch", type=int, default=0, choices=[0, 1, 2, 3],
-                help="GEMM prefetch depth of every launch class (0: the defaults / APEX_F32_PREFETCH)")
 ap.add_argument("--stage-split", type=int, default=-1, help="GEMM form mask (-1: the defaults)")
 ap.add_argument("--epilogue", type=int, default=-1, help="GEMM epilogue mask, 0..63: row-owned bits 0-2, line-owned bits 3-5 (-1: the defaults)")
 ap.add_argument("--sign-bits", type=int, default=0, choices=[0, 1], help="ReLU sign bits written / read (see above)")
 a = ap.parse_args()
 dev = torch.device("cuda")
 hip = ops.hip()
-if a.prefetch:
-    hip.f32_set_prefetch((a.prefetch - 1) * (1 + 4 + 16))
 if a.stage_split >= 0:
     hip.f32_set_stage_split(a.stage_split)
 if a.epilogue >= 0:

@@ -19,6 +19,7 @@ PAD_SAMPLES = 128      # a tile reaches at most 127 rows (samples, for the posit
 
 FORMS_DEFAULT = 3 + 4 * 3 + 16 * (0 + 1)   # learner forward / backward pairs form 3, small forward form 0
 FORMS_SMALL_3 = 3 + 4 * 3 + 16 * (3 + 1)   # the small-forward tiles on form 3 too
+FORMS_REGISTER = 0 + 4 * 0 + 16 * (0 + 1)  # every class on the register split (form 0)
 
 
 def _model(dev, A=18, seed=0):
@@ -137,7 +138,8 @@ def _same(a, b):
 BATCHES = [1, 33, 70, 130]
 
 
-@pytest.mark.parametrize("forms", [FORMS_DEFAULT, FORMS_SMALL_3], ids=["small-form0", "small-form3"])
+@pytest.mark.parametrize("forms", [FORMS_DEFAULT, FORMS_SMALL_3, FORMS_REGISTER],
+                         ids=["small-form0", "small-form3", "all-form0"])
 @pytest.mark.parametrize("resolve", [0, 1], ids=["masks", "bits"])
 @pytest.mark.parametrize("B", BATCHES)
 def test_row_epilogue_bit_identical(cuda, B, resolve, forms):

@@ -21,6 +21,7 @@ PAD_SAMPLES = 128      # a tile reaches at most 127 rows (samples, for the posit
 
 FORMS_DEFAULT = 3 + 4 * 3 + 16 * (0 + 1)   # learner forward / backward pairs form 3, small forward form 0
 FORMS_SMALL_3 = 3 + 4 * 3 + 16 * (3 + 1)   # the small-forward tiles on form 3 too
+FORMS_REGISTER = 0 + 4 * 0 + 16 * (0 + 1)  # every class on the register split (form 0)
 
 ELEMENT = 0
 LINES = 8 + 16 + 32    # every class line-owned
@@ -145,7 +146,8 @@ def _same(a, b):
 BATCHES = [1, 33, 70, 130]
 
 
-@pytest.mark.parametrize("forms", [FORMS_DEFAULT, FORMS_SMALL_3], ids=["small-form0", "small-form3"])
+@pytest.mark.parametrize("forms", [FORMS_DEFAULT, FORMS_SMALL_3, FORMS_REGISTER],
+                         ids=["small-form0", "small-form3", "all-form0"])
 @pytest.mark.parametrize("resolve", [0, 1], ids=["masks", "bits"])
 @pytest.mark.parametrize("B", BATCHES)
 def test_line_epilogue_bit_identical(cuda, B, resolve, forms):
@@ -230,50 +232,34 @@ def test_captured_learner_steps_identical_with_line_epilogue(cuda):
     assert torch.isfinite(la.flat).all() and la.idx.unique().numel() > 8
 
 
-def _kind(mask, cls):
-    return 2 if (mask >> (3 + cls)) & 1 else (mask >> cls) & 1
-
-
-def _mask_with(cls, kind):
-    return (8 << cls) if kind == 2 else (kind << cls)
-
-
-@pytest.mark.parametrize("what", ["forward-form1", "forward-depth2", "pairs-form2", "pairs-depth2"])
-def test_unbuilt_epilogue_combination_raises(cuda, what):
-    """A class's non-default epilogues are built for the default forms at prefetch depth 1 only:
-    a launch that asks for one elsewhere throws (nothing falls back to another kernel)."""
+@pytest.mark.parametrize("forms", [3 + 4 * 0 + 16 * (3 + 1), 1 + 4 * 1 + 16 * (1 + 1), 2 + 4 * 2 + 16 * (2 + 1)],
+                         ids=["swapped", "form1", "form2"])
+def test_every_epilogue_is_built_at_every_form(cuda, forms):
+    """Every class is built with every epilogue at every form (nothing is left to throw): the
+    element and row-owned epilogues at forms that are not the classes' defaults (swapped: the small
+    forward on form 3 and the pairs on form 0; every class on form 1; on form 2) launch and compute
+    the bits of the defaults.  The prefetch ring's setter is gone with the ring."""
     from apex_amd import ops
-    from apex_amd.models.fused_f32 import F32DuelingNet, F32Workspace, forward_multi_f32
 
     hip = ops.hip()
-    prev = hip.f32_epilogue(), hip.f32_stage_split(), hip.f32_prefetch()
-    B = 8
-    try:
-        hip.f32_set_epilogue(-1)
-        default = hip.f32_epilogue()
-        cls = 2 if what.startswith("forward") else 1   # B = 8: the small forward class
-        other = 2 if _kind(default, cls) != 2 else 0   # an epilogue that is not the class's default
-        hip.f32_set_epilogue(_mask_with(cls, other))
-        if what == "forward-form1":
-            hip.f32_set_stage_split(3 + 4 * 3 + 16 * (1 + 1))
-        elif what == "forward-depth2":
-            hip.f32_set_prefetch(16)
-        elif what == "pairs-form2":
-            hip.f32_set_stage_split(3 + 4 * 2 + 16 * (0 + 1))
-        else:
-            hip.f32_set_prefetch(4)
-        net = F32DuelingNet(_model(cuda))
-        net.enable_backward(B)
-        for p in net.model.parameters():
-            p.grad = torch.zeros_like(p)
-        ws = F32Workspace(B, 18, cuda, keep_for_backward=True)
-        x = _frames(B, cuda)
-        with pytest.raises(ValueError, match="non-default epilogue"):
-            forward_multi_f32([(net, x, ws, None, None)], sign_bits=True)
-            ws.dz.zero_()
-            net._fc1_bwd(ws)
-        torch.cuda.synchronize()
-    finally:
-        hip.f32_set_epilogue(prev[0])
-        hip.f32_set_stage_split(prev[1])
-        hip.f32_set_prefetch(prev[2])
+    assert not hasattr(hip, "f32_set_prefetch") and not hasattr(hip, "f32_prefetch")
+    ref = _run(cuda, 8, LINES, 1, FORMS_DEFAULT)
+    for epi in (ELEMENT, 7):
+        _same(ref, _run(cuda, 8, epi, 1, forms))
+
+
+def test_retired_prefetch_variable_throws():
+    """A non-zero APEX_F32_PREFETCH is not ignored: in a process that has it, reading the form mask
+    (as every GEMM launch does) raises, also after the mask was set by hand; zero is accepted.  The
+    variable is read once per process, hence the child processes (they load the library only)."""
+    import os
+    import subprocess
+    import sys
+
+    code = ("from apex_amd import ops\nhip = ops.hip()\nhip.f32_set_stage_split(31)\n"
+            "try:\n    print('mask', hip.f32_stage_split())\nexcept ValueError as e:\n    print('raised', e)\n")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for value, want in (("4", "raised APEX_F32_PREFETCH"), ("0", "mask 31")):
+        env = dict(os.environ, APEX_F32_PREFETCH=value, APEX_NO_AUTOBUILD="1")
+        out = subprocess.run([sys.executable, "-c", code], env=env, cwd=root, capture_output=True, text=True, timeout=120)
+        assert want in out.stdout, (value, out.stdout, out.stderr[-500:])
