@@ -38,6 +38,9 @@ and the target network is synced after the learner steps of every iteration whos
 a multiple of ``target_update_interval`` -- iteration 0 included (AQL_dis.py:127-129);
 ``target_update_steps > 0`` switches to a learner-step cadence instead (round-2 default).
 
+Everything but the environments lives in :class:`AQLEngineCore`; :mod:`apex_amd.engine.aql_host`
+puts gym-API envs stepped on the host under it (any env id, not only the three device envs).
+
 Reference behaviours kept: q.features (the state embedding feeding the proposal) receives
 gradient only from the proposal loss, which optimizer_q zeroes before its own backward, so
 it never changes (its Adam step sees a None/zero gradient); the discrete proposal loss
@@ -493,17 +496,18 @@ class AQLLearner:
                 "steps": int(self.step_ctr.item())}
 
 
-class AQLEngine(GreedyRollouts):
-    """Actors + replay + learner of AQL_dis on one GPU (see module docstring)."""
+class AQLEngineCore:
+    """What an AQL engine is apart from its environments: the three networks, the replay, the
+    learner, the acting buffers with the epsilon ladder, the acting forward's handles, the publish
+    wiring and the iteration counters.  :class:`AQLEngine` steps device envs under it,
+    :class:`apex_amd.engine.aql_host.AQLHostEngine` gym-API envs on the host."""
 
-    def __init__(self, cfg: AQLEngineConfig, device: str | torch.device = "cuda"):
+    def _init_core(self, cfg: AQLEngineConfig, device, n_envs: int) -> None:
+        """Models (from ``self.host_env``'s spaces), replay, learner, acting buffers, the ring's
+        insert handle.  The caller has set ``self.host_env``."""
         self.cfg = cfg
         self.device = dev = torch.device(device)
         self.hip = h = ops.hip()
-        if cfg.env_id not in ENV_KINDS:
-            raise ValueError(f"GPU AQL env must be one of {sorted(ENV_KINDS)}")
-        self.kind = ENV_KINDS[cfg.env_id]
-        self.host_env = envs.make(cfg.env_id)
         torch.manual_seed(cfg.seed)
         kw = dict(propose_sample=cfg.propose_sample, uniform_sample=cfg.uniform_sample, action_var=cfg.action_var,
                   device=dev)
@@ -522,12 +526,11 @@ class AQLEngine(GreedyRollouts):
         self.actor_flat = flatten_module_params(self.actor_model)
         self.actor_eps = flatten_noise(self.actor_model)
         self.publish()
-        E = cfg.n_envs
+        E = int(n_envs)
         self.E = E
         self.K = cfg.learner_steps if cfg.learner_steps is not None else max(1, E // cfg.batch_size)
         f32 = dict(dtype=torch.float32, device=dev)
         self.obs_buf = torch.zeros(E, self.obs, **f32)
-        self.phys = torch.zeros(E, 4, **f32)
         self.ep_len = torch.zeros(E, dtype=torch.int32, device=dev)
         self.ep_ret = torch.zeros(E, **f32)
         self.ep_count = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -550,13 +553,125 @@ class AQLEngine(GreedyRollouts):
         else:
             self.low = self.high = torch.zeros(1, **f32)
         self.var = self.model.proposal.action_var.to(**f32).contiguous()
+        self.seed = (cfg.seed * 0x2545F491 + 0xAC7) & 0xFFFFFFFFFFFF
+        self.ins = h.make_aql_insert(dict(self.replay.table_ptrs(), C=self.replay.capacity,
+                                          filled=self.replay.filled.data_ptr(), slots=self.slots.data_ptr()))
+        self._pub_in_graph = False
+        self._iterations = 0
+        self.learner_steps = 0
+        self._g_actor = self._g_learn = self._g_iter = None
+        self._ep_read = 0
+        self.target_syncs = collections.deque(maxlen=4096)  # iterations after which the target was synced
+
+    def _init_acting(self, act_blocks: int = 0) -> None:
+        """The acting forward's handles: the published copy's net and the learner's MFMA candidate
+        forward over it (online net, s only, row = env index)."""
+        self.actor_net = FusedAQL(self.actor_model)._net()
+        self.actL = self.hip.make_aql_act(self.actor_net, self.obs_buf.data_ptr(), self.amu.data_ptr(),
+                                          self.ws.data_ptr(), self.qbuf.data_ptr(), self.E, act_blocks)
+
+    @staticmethod
+    def _s() -> int:
+        return torch.cuda.current_stream().cuda_stream
+
+    # ------------------------------------------------------------------ phases
+    def publish(self) -> None:
+        """set_worker_weights: the actors' copy of the online network (noise included)."""
+        s = self._s()
+        self.hip.copy_f32(self.actor_flat.data_ptr(), self.learner.flat.data_ptr(), self.learner.P, s)
+        self.hip.copy_f32(self.actor_eps.data_ptr(), self.learner.eps.data_ptr(), self.learner.eps.numel(), s)
+
+    def _propose_q(self, h, s, E) -> None:
+        """Proposal and candidate Q (the learner's MFMA candidate forward on the online net, s
+        only) for all E envs."""
+        # (the effective NoisyNet weights ride along in the proposal launch)
+        h.aql_propose(self.actor_net, self.obs_buf.data_ptr(), E, self.low.data_ptr(), self.high.data_ptr(),
+                      self.var.data_ptr(), self.seed ^ 0x9909, self.actor_ctr.data_ptr(), self.amu.data_ptr(), 0, s,
+                      self.ws.data_ptr())
+        h.aql_act_q(self.actL, s)
+
+    def _act(self, h, s, E) -> None:
+        """Proposal, candidate Q and epsilon-greedy selection for all E envs."""
+        self._propose_q(h, s, E)
+        h.aql_select(self.qbuf.data_ptr(), self.amu.data_ptr(), E, self.T, self.adim, self.eps.data_ptr(),
+                     self.seed ^ 0xA9C1, self.actor_ctr.data_ptr(), self.act_idx.data_ptr(), self.env_act.data_ptr(), s)
+
+    def learn_steps(self, publish: bool = False, gate: torch.Tensor | None = None) -> bool:
+        """The iteration's K SGD steps; in the fused sequence each step but the last also draws
+        the next step's rows (nothing inserts between them), so only the first forward samples.
+        ``publish``: the last step also writes the acting copies (returns whether it did).
+        ``gate``: only the first ``gate[0]`` of the K steps run (:meth:`AQLLearner.step`)."""
+        pre = self.learner.predraw
+        pub = False
+        for k in range(self.K):
+            pub = bool(self.learner.step(drawn=pre and k > 0, draw_next=pre and k + 1 < self.K,
+                                         publish=publish and k + 1 == self.K, gate=gate, j=k))
+        return pub
+
+    def _beta(self) -> float:
+        c = self.cfg  # AQL_dis.py:59 operator precedence kept
+        return min(1.0, c.beta_start + self.iterations * (1.0 - c.beta_start) / c.max_step * c.n_workers)
+
+    @property
+    def iterations(self) -> int:
+        return self._iterations
+
+    @iterations.setter
+    def iterations(self, v: int) -> None:
+        """An assignment from outside the iteration loop (a checkpoint load, the central
+        engine's recorded-batch count): the fused acting tail's device iteration counter, which
+        computes the PER beta on the device (AQL_dis.py:59), follows it -- the two can never
+        disagree silently.  The loop's own increments go to ``_iterations`` (the tail kernel
+        bumps its device copy itself)."""
+        self._iterations = int(v)
+        if getattr(self, "_tail", None) is not None:
+            self._iter_dev.fill_(self._iterations)
+
+    def _after_learn(self) -> None:
+        """The iteration's bookkeeping after its K learner steps: the step count, the target
+        cadence, the iteration count."""
+        before = self.learner_steps
+        self.learner_steps += self.K
+        if target_sync_due(self.cfg, self.iterations, before, self.learner_steps):
+            self.learner.sync_target()
+            self.target_syncs.append(self.iterations)
+        self._iterations += 1
+
+    def finished_episodes(self) -> list[tuple[float, int]]:
+        """(return, length) of the episodes finished since the last call (host sync)."""
+        n = int(self.ep_count.item())
+        lo = max(self._ep_read, n - self.log_cap)
+        out = []
+        if n > lo:
+            log = self.ep_log.cpu()
+            out = [(float(log[k % self.log_cap, 0]), int(log[k % self.log_cap, 1])) for k in range(lo, n)]
+        self._ep_read = n
+        return out
+
+    @property
+    def transitions_per_iteration(self) -> int:
+        return self.E
+
+
+class AQLEngine(AQLEngineCore, GreedyRollouts):
+    """Actors + replay + learner of AQL_dis on one GPU (see module docstring)."""
+
+    def __init__(self, cfg: AQLEngineConfig, device: str | torch.device = "cuda"):
+        if cfg.env_id not in ENV_KINDS:
+            raise ValueError(f"GPU AQL env must be one of {sorted(ENV_KINDS)}.  Any other gym-API env trains on "
+                             "host envs: train_aql --host-envs / apex_amd.engine.aql_host.AQLHostEngine.")
+        self.kind = ENV_KINDS[cfg.env_id]
+        self.host_env = envs.make(cfg.env_id)
+        self._init_core(cfg, device, cfg.n_envs)
+        h, dev, E = self.hip, self.device, self.E
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.phys = torch.zeros(E, 4, **f32)
         if self.kind == 0:
             self.dynA = torch.as_tensor(self.host_env.unwrapped._A, **f32).contiguous()
             self.dynB = torch.as_tensor(self.host_env.unwrapped._B, **f32).contiguous()
             self.dynw = torch.as_tensor(self.host_env.unwrapped._w, **f32).contiguous()
         else:
             self.dynA = self.dynB = self.dynw = torch.zeros(1, **f32)
-        self.seed = (cfg.seed * 0x2545F491 + 0xAC7) & 0xFFFFFFFFFFFF
         self.env = h.make_aql_env(dict(
             kind=self.kind, E=E, obs=self.obs, adim=self.adim, T=self.T,
             max_steps=int(getattr(self.host_env, "_max_episode_steps", None) or 1_000_000),
@@ -564,8 +679,6 @@ class AQLEngine(GreedyRollouts):
             ep_ret=self.ep_ret.data_ptr(), dynA=self.dynA.data_ptr(), dynB=self.dynB.data_ptr(),
             dynw=self.dynw.data_ptr(), seed=self.seed, counter=self.actor_ctr.data_ptr(),
             ep_count=self.ep_count.data_ptr(), ep_log=self.ep_log.data_ptr(), log_cap=self.log_cap))
-        self.ins = h.make_aql_insert(dict(self.replay.table_ptrs(), C=self.replay.capacity,
-                                          filled=self.replay.filled.data_ptr(), slots=self.slots.data_ptr()))
         # overlap: the acting step writes its transitions into staging half h (rows 0..E-1);
         # the learner's graph applies the other half (the previous acting step's) to the ring
         # before its first sample, so acting never touches a table or tree the learner reads
@@ -574,7 +687,6 @@ class AQLEngine(GreedyRollouts):
         # launch (no publish copies after it); overlap mode publishes after the acting step
         if not self.overlap:
             self.learner.set_publish(self.actor_flat, self.actor_eps)
-        self._pub_in_graph = False
         self._half = 0
         if self.overlap:
             self._zero64 = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -607,34 +719,16 @@ class AQLEngine(GreedyRollouts):
                 ticket=self._ticket.data_ptr(), beta_out=self.learner.beta.data_ptr(), iter=self._iter_dev.data_ptr(),
                 beta0=float(cfg.beta_start), beta_omb=1.0 - cfg.beta_start, beta_max_step=float(cfg.max_step),
                 beta_workers=float(cfg.n_workers)))
-        self.actor_net = FusedAQL(self.actor_model)._net()
-        # acting on the learner's MFMA candidate forward (online net, s only, row = env index)
         # (64 acting workgroups beside the learner in overlap mode: most CUs stay the learner's)
-        self.actL = h.make_aql_act(self.actor_net, self.obs_buf.data_ptr(), self.amu.data_ptr(), self.ws.data_ptr(),
-                                   self.qbuf.data_ptr(), E, 64 if cfg.overlap else 0)
+        self._init_acting(64 if cfg.overlap else 0)
         h.aql_env_reset(self.env, self._s())
-        self._iterations = 0
-        self.learner_steps = 0
-        self._g_actor = self._g_learn = self._g_iter = None
-        self._ep_read = 0
-        self.target_syncs = collections.deque(maxlen=4096)  # iterations after which the target was synced
         # greedy evaluation: the registered TimeLimit (greedy_eval's), the eval-mode handle of the
         # online net (NoisyNet means; same parameter storage, the module stays in train mode)
         self.eval_limit = int(getattr(self.host_env, "_max_episode_steps", None) or 10_000)
         self.eval_net = self.learner.fused_on._net(noisy=False)
         self._eval = None
 
-    @staticmethod
-    def _s() -> int:
-        return torch.cuda.current_stream().cuda_stream
-
     # ------------------------------------------------------------------ phases
-    def publish(self) -> None:
-        """set_worker_weights: the actors' copy of the online network (noise included)."""
-        s = self._s()
-        self.hip.copy_f32(self.actor_flat.data_ptr(), self.learner.flat.data_ptr(), self.learner.P, s)
-        self.hip.copy_f32(self.actor_eps.data_ptr(), self.learner.eps.data_ptr(), self.learner.eps.numel(), s)
-
     def actor_step(self, half: int | None = None, into=None) -> None:
         """One acting step of all E envs.  ``half`` (overlap mode): write the transitions into
         staging half ``half`` instead of the ring (see :meth:`apply_staged`); ``into``: an
@@ -655,39 +749,12 @@ class AQLEngine(GreedyRollouts):
         h.per_write_leaves(r.tree, self.slots.data_ptr(), 0, E, r.alpha, r.max_prio.data_ptr(), 0,
                            r.sorted_scratch.data_ptr(), r.filled.data_ptr(), E, self.actor_ctr.data_ptr(), 1, s)
 
-    def _propose_q(self, h, s, E) -> None:
-        """Proposal and candidate Q (the learner's MFMA candidate forward on the online net, s
-        only) for all E envs."""
-        # (the effective NoisyNet weights ride along in the proposal launch)
-        h.aql_propose(self.actor_net, self.obs_buf.data_ptr(), E, self.low.data_ptr(), self.high.data_ptr(),
-                      self.var.data_ptr(), self.seed ^ 0x9909, self.actor_ctr.data_ptr(), self.amu.data_ptr(), 0, s,
-                      self.ws.data_ptr())
-        h.aql_act_q(self.actL, s)
-
-    def _act(self, h, s, E) -> None:
-        """Proposal, candidate Q and epsilon-greedy selection for all E envs."""
-        self._propose_q(h, s, E)
-        h.aql_select(self.qbuf.data_ptr(), self.amu.data_ptr(), E, self.T, self.adim, self.eps.data_ptr(),
-                     self.seed ^ 0xA9C1, self.actor_ctr.data_ptr(), self.act_idx.data_ptr(), self.env_act.data_ptr(), s)
-
     def apply_staged(self, half: int) -> None:
         """Overlap mode, learner stream: staging half ``half`` -> the ring at max priority."""
         h, s, E, r = self.hip, self._s(), self.E, self.replay
         h.aql_apply_staged(self._stage_ins[half], self.ins, E, self.obs, self.T * self.adim, s)
         h.per_write_leaves(r.tree, self.slots.data_ptr(), 0, E, r.alpha, r.max_prio.data_ptr(), 0,
                            r.sorted_scratch.data_ptr(), r.filled.data_ptr(), E, 0, 0, s)
-
-    def learn_steps(self, publish: bool = False, gate: torch.Tensor | None = None) -> bool:
-        """The iteration's K SGD steps; in the fused sequence each step but the last also draws
-        the next step's rows (nothing inserts between them), so only the first forward samples.
-        ``publish``: the last step also writes the acting copies (returns whether it did).
-        ``gate``: only the first ``gate[0]`` of the K steps run (:meth:`AQLLearner.step`)."""
-        pre = self.learner.predraw
-        pub = False
-        for k in range(self.K):
-            pub = bool(self.learner.step(drawn=pre and k > 0, draw_next=pre and k + 1 < self.K,
-                                         publish=publish and k + 1 == self.K, gate=gate, j=k))
-        return pub
 
     def fill(self, threshold: int | None = None) -> None:
         """Act until the replay holds more than ``threshold`` transitions (AQL_dis.py:120:
@@ -736,25 +803,6 @@ class AQLEngine(GreedyRollouts):
             self._pub_in_graph = self.learn_steps(publish=True)
         torch.cuda.synchronize(self.device)
 
-    def _beta(self) -> float:
-        c = self.cfg  # AQL_dis.py:59 operator precedence kept
-        return min(1.0, c.beta_start + self.iterations * (1.0 - c.beta_start) / c.max_step * c.n_workers)
-
-    @property
-    def iterations(self) -> int:
-        return self._iterations
-
-    @iterations.setter
-    def iterations(self, v: int) -> None:
-        """An assignment from outside the iteration loop (a checkpoint load, the central
-        engine's recorded-batch count): the fused acting tail's device iteration counter, which
-        computes the PER beta on the device (AQL_dis.py:59), follows it -- the two can never
-        disagree silently.  The loop's own increments go to ``_iterations`` (the tail kernel
-        bumps its device copy itself)."""
-        self._iterations = int(v)
-        if getattr(self, "_tail", None) is not None:
-            self._iter_dev.fill_(self._iterations)
-
     def iteration(self) -> None:
         """One actor step of all envs, weight publish, K learner steps."""
         if self.overlap:
@@ -769,12 +817,7 @@ class AQLEngine(GreedyRollouts):
             pub = self.learn_steps(publish=True)
         if not pub:
             self.publish()
-        before = self.learner_steps
-        self.learner_steps += self.K
-        if target_sync_due(self.cfg, self.iterations, before, self.learner_steps):
-            self.learner.sync_target()
-            self.target_syncs.append(self.iterations)
-        self._iterations += 1
+        self._after_learn()
 
     def _iteration_overlap(self) -> None:
         """Acting step t (staging half h) on the acting stream || the learner (apply half 1-h,
@@ -799,29 +842,9 @@ class AQLEngine(GreedyRollouts):
             self.learn_steps()
         L.wait_event(self._ev_actor[hh])
         self.publish()
-        before = self.learner_steps
-        self.learner_steps += self.K
-        if target_sync_due(self.cfg, self.iterations, before, self.learner_steps):
-            self.learner.sync_target()
-            self.target_syncs.append(self.iterations)
-        self._iterations += 1
+        self._after_learn()
         self._ev_learn.record(L)
         self._half ^= 1
-
-    def finished_episodes(self) -> list[tuple[float, int]]:
-        """(return, length) of the episodes finished since the last call (host sync)."""
-        n = int(self.ep_count.item())
-        lo = max(self._ep_read, n - self.log_cap)
-        out = []
-        if n > lo:
-            log = self.ep_log.cpu()
-            out = [(float(log[k % self.log_cap, 0]), int(log[k % self.log_cap, 1])) for k in range(lo, n)]
-        self._ep_read = n
-        return out
-
-    @property
-    def transitions_per_iteration(self) -> int:
-        return self.E
 
     # ------------------------------------------------------------------ evaluation
     def evaluate(self, episodes: int = 10, seed: int | None = None, max_episode_steps: int | None = None) -> list[float]:
@@ -933,6 +956,9 @@ class AQLEvaluator(RolloutEvaluation):
     flags."""
 
     def __init__(self, engine: AQLEngine, episodes: int = 10, max_episode_steps: int | None = None, **side):
+        if not isinstance(engine, AQLEngine):
+            raise TypeError("AQLEvaluator plays aql_rollout's device envs: it needs an AQLEngine; a host-env engine "
+                            "evaluates on the host (AQLHostEngine.evaluate)")
         self.hip, self.n = engine.hip, int(episodes)
         cfg, dev = engine.cfg, engine.device
         self.model = AQL(env=engine.host_env, propose_sample=cfg.propose_sample, uniform_sample=cfg.uniform_sample,

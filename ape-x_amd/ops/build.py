@@ -46,6 +46,7 @@ HIP_SOURCES = [
     "aql_engine_kernels.hip",
     "aql_rollout_kernels.hip",
     "aql_frame_kernels.hip",
+    "aql_host_kernels.hip",
     "atari_rollout_kernels.hip",
     "conv1_kernels.hip",
     "fc_kernels.hip",

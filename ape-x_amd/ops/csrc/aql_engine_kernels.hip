@@ -1161,38 +1161,9 @@ __global__ __launch_bounds__(256) void aql_act_tail_k(AqlTail A) {
       env_step_wave(V, e, lane, s_act[wave], arg, A.amu, A.I, (A.filled[0] + e) % A.I.C, ctr);
     }
   } else {
-    __shared__ int sids[1024];
-    __shared__ int comp[64];
-    __shared__ int ncomp;
-    const TreeDesc& tr = A.tree;
-    const int64_t f = A.filled[0];
-    const float p = *A.max_prio;
-    for (int i = t; i < V.E; i += blockDim.x) {
-      const int id = (int)((f + i) % A.I.C);
-      sids[i] = id;
-      if (id < tr.size[0]) write_leaf(tr, id, p, A.alpha);
-    }
-    if (t == 0) {
-      ncomp = 0;
-      if (A.beta_out) {  // AQL_dis.py:59 in the host's double arithmetic, then to fp32
-#pragma clang fp contract(off)
-        const double it = (double)A.iter[0];
-        const double r = A.beta0 + it * A.beta_omb / A.beta_max_step * A.beta_workers;
-        A.beta_out[0] = (float)(r < 1.0 ? r : 1.0);
-      }
-    }
-    __syncthreads();
-    for (int i = t; i < V.E; i += blockDim.x) {  // one slot per distinct level-1 node (ring order)
-      const int id = sids[i];
-      if (id >= tr.size[0]) continue;
-      const int prev = i > 0 ? sids[i - 1] : -1;
-      if (prev >= 0 && prev < tr.size[0] && (prev >> kTreeLog2Fanout) == (id >> kTreeLog2Fanout)) continue;
-      const int k = atomicAdd(&ncomp, 1);
-      if (k < 64) comp[k] = id;
-    }
-    __syncthreads();
-    if (ncomp <= 64) update_levels_fast<4>(tr, comp, ncomp);
-    else update_levels_block(tr, sids, V.E, 1, tr.levels);
+    if (t == 0 && A.beta_out)
+      A.beta_out[0] = tail_beta(A.iter[0], A.beta0, A.beta_omb, A.beta_max_step, A.beta_workers);
+    ring_write_block(A.tree, A.filled[0], A.I.C, V.E, *A.max_prio, A.alpha);
   }
   __syncthreads();
   if (t == 0) {

@@ -1042,6 +1042,29 @@ PYBIND11_MODULE(_apex_hip, m) {
     return a;
   });
   m.def("aql_act_tail", [](const AqlTail& a, uint64_t s) { aql_act_tail(a, S(s)); });
+  // the acting tail over host envs (aql_host_kernels.hip); d: E, obs, adim, T, stage, obs_buf, amu, act_idx,
+  // ep_len, ep_ret, ep_count, ep_log, log_cap, alpha, max_prio, filled, counter, ticket [, beta_out, iter, beta*]
+  py::class_<AqlHostTail>(m, "AqlHostTail");
+  m.def("make_aql_host_tail", [](const AqlInsert& ins, const TreeHandle& tree, py::dict d) {
+    auto g = [&](const char* k) { return d[k].cast<uint64_t>(); };
+    auto opt = [&](const char* k) { return d.contains(k) ? d[k].cast<uint64_t>() : (uint64_t)0; };
+    AqlHostTail a{};
+    a.E = d["E"].cast<int>(); a.obs = d["obs"].cast<int>(); a.adim = d["adim"].cast<int>(); a.T = d["T"].cast<int>();
+    a.stage = P<const float>(g("stage")); a.obs_buf = P<float>(g("obs_buf")); a.amu = P<const float>(g("amu"));
+    a.act_idx = P<const int>(g("act_idx")); a.ep_len = P<int>(g("ep_len")); a.ep_ret = P<float>(g("ep_ret"));
+    a.ep_count = P<int>(g("ep_count")); a.ep_log = P<float>(g("ep_log")); a.log_cap = d["log_cap"].cast<int>();
+    a.I = ins;
+    a.tree = tree.d;
+    a.alpha = d["alpha"].cast<float>(); a.max_prio = P<const float>(g("max_prio"));
+    a.filled = P<int64_t>(g("filled")); a.counter = P<int64_t>(g("counter")); a.ticket = P<int>(g("ticket"));
+    a.beta_out = P<float>(opt("beta_out")); a.iter = P<int64_t>(opt("iter"));
+    a.beta0 = d.contains("beta0") ? d["beta0"].cast<double>() : 0.0;
+    a.beta_omb = d.contains("beta_omb") ? d["beta_omb"].cast<double>() : 0.0;
+    a.beta_max_step = d.contains("beta_max_step") ? d["beta_max_step"].cast<double>() : 1.0;
+    a.beta_workers = d.contains("beta_workers") ? d["beta_workers"].cast<double>() : 0.0;
+    return a;
+  });
+  m.def("aql_host_tail", [](const AqlHostTail& a, uint64_t s) { aql_host_tail(a, S(s)); });
   m.def("aql_select", [](uint64_t q, uint64_t a_mu, int B, int T, int adim, uint64_t eps, uint64_t seed,
                          uint64_t counter, uint64_t act_idx, uint64_t env_act, uint64_t s) {
     aql_select(P<const float>(q), P<const float>(a_mu), B, T, adim, P<const float>(eps), seed,

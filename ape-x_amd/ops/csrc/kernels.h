@@ -762,6 +762,36 @@ struct AqlTail {
   double beta0, beta_omb, beta_max_step, beta_workers;
 };
 void aql_act_tail(const AqlTail& a, hipStream_t s);
+// The acting tail over HOST envs (aql_host_kernels.hip aql_host_tail_k): aql_act_tail with the
+// device dynamics replaced by one staged host step.  `stage` is the device copy of the vector
+// env's staging block, fp32: next_obs [E][obs] | reset_obs [E][obs] | reward [E] | done [E] |
+// ended [E].  Env e's transition (obs_buf[e], amu[e], act_idx[e], reward, done, next_obs[e]) goes
+// into ring slot (filled + e) mod C; the episode bookkeeping is env_step_wave's with `ended` in
+// the place of its done (a length-cap reset keeps done = 0); obs_buf[e] = reset_obs[e].  One more
+// workgroup writes the tree, the last one to finish bumps the counters and writes the PER beta.
+struct AqlHostTail {
+  int E, obs, adim, T;
+  const float* stage;
+  float* obs_buf;            // [E][obs] the observation acted on; out: the next one to act on
+  const float* amu;          // [E][T][adim]
+  const int* act_idx;        // [E] the chosen candidate (aql_select)
+  int* ep_len;
+  float* ep_ret;
+  int* ep_count;
+  float* ep_log;             // [log_cap][2] (return, length) ring
+  int log_cap;
+  AqlInsert I;               // the replay ring (I.filled is `filled`)
+  TreeDesc tree;
+  float alpha;
+  const float* max_prio;
+  int64_t* filled;           // += E by the last workgroup
+  int64_t* counter;          // acting counter, += 1 by the last workgroup
+  int* ticket;               // zero between launches
+  float* beta_out;           // optional, as AqlTail
+  int64_t* iter;
+  double beta0, beta_omb, beta_max_step, beta_workers;
+};
+void aql_host_tail(const AqlHostTail& a, hipStream_t s);
 // N greedy episodes from reset to their first done in one launch (aql_rollout_kernels.hip; one
 // workgroup per episode, the weights staged once): episode b starts at aql_env_reset's draw for
 // env b and every step is aql_propose -> aql_candidate_q -> aql_select (eps 0) -> aql_env_step

@@ -568,4 +568,42 @@ __device__ __forceinline__ bool tree_ride(const TreeRide& r, int nhost, float* r
   return false;
 }
 
+// One acting step's ring write by one workgroup (E <= 1024): the leaves of slots (f + i) mod C,
+// i < E, at priority p (the running max: it does not move), then every level of their paths --
+// one walk per distinct level-1 node while those fit the one-shot walk.  The tree block of the
+// acting tails (aql_act_tail_k, aql_host_tail_k).
+__device__ __forceinline__ void ring_write_block(const TreeDesc& tr, int64_t f, int64_t C, int E, float p,
+                                                 float alpha) {
+  __shared__ int sids[1024];
+  __shared__ int comp[64];
+  __shared__ int ncomp;
+  const int t = threadIdx.x;
+  for (int i = t; i < E; i += blockDim.x) {
+    const int id = (int)((f + i) % C);
+    sids[i] = id;
+    if (id < tr.size[0]) write_leaf(tr, id, p, alpha);
+  }
+  if (t == 0) ncomp = 0;
+  __syncthreads();
+  for (int i = t; i < E; i += blockDim.x) {  // one slot per distinct level-1 node (ring order)
+    const int id = sids[i];
+    if (id >= tr.size[0]) continue;
+    const int prev = i > 0 ? sids[i - 1] : -1;
+    if (prev >= 0 && prev < tr.size[0] && (prev >> kTreeLog2Fanout) == (id >> kTreeLog2Fanout)) continue;
+    const int k = atomicAdd(&ncomp, 1);
+    if (k < 64) comp[k] = id;
+  }
+  __syncthreads();
+  if (ncomp <= 64) update_levels_fast<4>(tr, comp, ncomp);
+  else update_levels_block(tr, sids, E, 1, tr.levels);
+}
+
+// The acting tails' PER beta for iteration `it` (AQL_dis.py:59) in the host's double arithmetic,
+// then to fp32
+__device__ __forceinline__ float tail_beta(int64_t it, double beta0, double omb, double max_step, double workers) {
+#pragma clang fp contract(off)
+  const double r = beta0 + (double)it * omb / max_step * workers;
+  return (float)(r < 1.0 ? r : 1.0);
+}
+
 }  // namespace apex

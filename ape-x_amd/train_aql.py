@@ -35,6 +35,14 @@ snapshot was taken; the last one is drained at the end of the run).  Single-GPU 
 Losses are accumulated on the device (no host sync per learner step); the host reads
 them once per ``--log-interval`` iterations.
 
+``--host-envs``: the envs are ``--n-envs`` (default 10, the reference's workers) gym-API envs
+``envs.make(--env)`` stepped on the CPU (``envs/host_vector.py``; reset on ``done`` or after
+``--max-episode-length`` steps, batchrecoder_AQL.py:54-55) under the same replay, learner,
+checkpoints, tags and cadences (``apex_amd.engine.aql_host``): any id with flat observations,
+not only the three GPU envs.  The K learner steps of an iteration are queued before the host steps
+the envs (``--host-serial``: after); ``actor/env_steps_per_sec`` counts host env steps.  Single
+GPU, host evaluator.
+
 ``--gpus N`` (N > 1; or any launch with WORLD_SIZE > 1): the distributed form of AQL_dis
 across GPUs (``apex_amd.engine.central_aql``): rank 0 trains and checkpoints, ranks 1..N-1
 are actor GPUs pushing transitions over HIP IPC; one iteration = one packet per actor +
@@ -67,14 +75,33 @@ class _Parser(argparse.ArgumentParser):
         if a.gpus > 1 and a.eval_mode != "host":
             self.error(f"--eval-mode {a.eval_mode} is for the single-GPU engine: with --gpus {a.gpus} rank 0's "
                        "evaluator is the host one (--eval-mode host)")
+        if a.host_envs:
+            if a.eval_mode != "host":
+                self.error(f"--eval-mode {a.eval_mode} plays the GPU envs: with --host-envs the evaluator is the "
+                           "host one (--eval-mode host)")
+            if a.gpus > 1:
+                self.error(f"--host-envs is the single-GPU engine: --gpus {a.gpus} has no host-env form")
+            if a.overlap:
+                self.error("--overlap is the GPU envs' acting stream: --host-envs overlaps the host step with the "
+                           "learner by default (--host-serial turns that off)")
+        if a.n_envs is None:
+            a.n_envs = 10 if a.host_envs else 256
         return a
 
 
 def parser() -> argparse.ArgumentParser:
     p = _Parser(description="AQL_dis on MI355X (GPU-resident AQL engine)")
-    p.add_argument("--env", default="CartPole-v0", help="CartPole-v0/v1, Pendulum-v0/v1, BipedalWalker-v3")
+    p.add_argument("--env", default="CartPole-v0", help="GPU envs: CartPole-v0/v1, Pendulum-v0/v1, BipedalWalker-v3; with --host-envs any envs.make id "
+                        "with flat observations (MountainCarContinuous-v0, a real gym env under APEX_USE_GYM=1, ...)")
     p.add_argument("--max-step", type=int, default=1_000_000, help="iterations (AQL_dis max_step)")
-    p.add_argument("--n-envs", type=int, default=256, help="GPU envs (the reference's workers)")
+    p.add_argument("--n-envs", type=int, default=None,
+                   help="envs (the reference's workers); default 256 GPU envs, 10 with --host-envs")
+    p.add_argument("--host-envs", action="store_true",
+                   help="step gym-API envs on the host under the GPU replay and learner (engine.aql_host)")
+    p.add_argument("--host-serial", action="store_true",
+                   help="--host-envs: step the envs before the learner steps instead of beside them")
+    p.add_argument("--max-episode-length", type=int, default=50000,
+                   help="--host-envs: reset an env after this many steps (AQL_dis.py:51)")
     p.add_argument("--batch-size", type=int, default=32)
     p.add_argument("--gamma", type=float, default=0.99)
     p.add_argument("--n-steps", type=int, default=1)
@@ -220,7 +247,14 @@ def train(a) -> dict:
         return train_central(a, int(os.environ["RANK"]), world)
     dev = torch.device(a.device)
     torch.cuda.set_device(dev)
-    eng = AQLEngine(config_from_args(a), dev)
+    if a.host_envs:
+        from .engine.aql_host import AQLHostEngine
+        from .envs.host_vector import HostVectorEnv
+
+        vec = HostVectorEnv(a.env, a.n_envs, seed=a.seed, max_episode_length=a.max_episode_length)
+        eng = AQLHostEngine(config_from_args(a), vec, dev, host_overlap=not a.host_serial)
+    else:
+        eng = AQLEngine(config_from_args(a), dev)
     start = 0
     if a.resume is not None:
         idx = latest_index(a.save_dir) if a.resume == "latest" else int(a.resume)
@@ -233,7 +267,11 @@ def train(a) -> dict:
     eng.fill()
     if not a.no_graphs:
         eng.capture()
-    return _loop(a, eng, eng.iteration, eng.E, eng.finished_episodes, start, writer)
+    try:
+        return _loop(a, eng, eng.iteration, eng.E, eng.finished_episodes, start, writer)
+    finally:
+        if a.host_envs:
+            eng.close()
 
 
 def train_central(a, rank: int, world: int) -> dict:
