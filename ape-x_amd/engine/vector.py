@@ -30,7 +30,10 @@ Launch budget (kernel launches per step, all on the caller's stream, no host syn
   three async copies to pinned memory; eager, between graph replays.
 
 Serial actor-then-learner on one stream; overlap and multi-GPU topologies are the Atari
-engine's and are not offered here.
+engine's and are not offered here.  Envs other than ``VECTOR_ENVS`` -- any gym-API env with a
+flat observation and a discrete action space, stepped on the CPU -- train under the same
+replay and learner in :mod:`apex_amd.engine.vector_host`, which also overlaps the host's env
+step with the learner.
 """
 from __future__ import annotations
 
@@ -190,8 +193,11 @@ class VectorEngineConfig:
     fused_norm: bool = True          # grad-norm partials from the gradient launch (5 launches per SGD step)
     seed: int = 0
 
-    def validate(self) -> "VectorEngineConfig":
-        env_spec(self.env_id)
+    def validate(self, device_env: bool = True) -> "VectorEngineConfig":
+        """``device_env=False``: ``env_id`` is only a label (the host-env engine takes its shapes
+        from the vector env)."""
+        if device_env:
+            env_spec(self.env_id)
         if not 1 <= self.batch_size <= MAX_BATCH:
             raise ValueError(f"batch_size must be in [1, {MAX_BATCH}]")
         if self.nstep_mode not in ("reference", "textbook"):
@@ -495,6 +501,9 @@ class VectorEvaluator(RolloutEvaluation):
 
     def __init__(self, engine: VectorApexEngine, episodes: int = 10, max_episode_steps: int | None = None,
                  **side):
+        if not isinstance(engine, VectorApexEngine):
+            raise TypeError("VectorEvaluator plays vec_rollout's device envs: it needs a VectorApexEngine; a "
+                            "host-env engine evaluates on the host (VectorHostEngine.evaluate)")
         self.hip, self.n = engine.hip, int(episodes)
         self.model = copy.deepcopy(engine.learner.model)   # the snapshot
         self.model._flat = None

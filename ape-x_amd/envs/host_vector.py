@@ -1,5 +1,6 @@
 """An in-process vector of N gym-API envs with flat fp32 observations, for the host-env AQL
-engine (:mod:`apex_amd.engine.aql_host`).
+engine (:mod:`apex_amd.engine.aql_host`) and the host-env vector Ape-X engine
+(:mod:`apex_amd.engine.vector_host`, which has tighter shape limits of its own).
 
 The envs are whatever :func:`apex_amd.envs.make` returns (the in-package classic-control envs,
 or a real ``gym`` with ``APEX_USE_GYM=1``) or the callables handed in.  Env ``i`` is seeded

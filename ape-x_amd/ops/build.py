@@ -54,6 +54,7 @@ HIP_SOURCES = [
     "f32_kernels.hip",
     "ipc_kernels.hip",
     "vector_kernels.hip",
+    "vector_host_kernels.hip",
     "host_env_kernels.hip",
     "host_eval_kernels.hip",
     "comm.cpp",

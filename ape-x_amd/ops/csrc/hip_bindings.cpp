@@ -1105,6 +1105,21 @@ PYBIND11_MODULE(_apex_hip, m) {
     vec_classic_step(V, P<const int>(actions), P<const int64_t>(step), P<float>(reward), P<float>(done),
                      P<int>(new_frame), P<float>(ep_log), S(s));
   });
+  // the acting step's env half over host envs (vector_host_kernels.hip); d: E, obs, F, stage, ring, step,
+  // reward, done, new_frame, hist, ep_log, ep_ret, ep_len
+  py::class_<VecHostTail>(m, "VecHostTail");
+  m.def("make_vec_host_tail", [](py::dict d) {
+    auto g = [&](const char* k) { return d[k].cast<uint64_t>(); };
+    VecHostTail a{};
+    a.E = d["E"].cast<int>(); a.obs = d["obs"].cast<int>(); a.F = d["F"].cast<int>();
+    a.stage = P<const float>(g("stage")); a.ring = P<float>(g("ring")); a.step = P<const int64_t>(g("step"));
+    a.reward = P<float>(g("reward")); a.done = P<float>(g("done")); a.new_frame = P<int>(g("new_frame"));
+    a.hist = P<int>(g("hist")); a.ep_log = P<float>(g("ep_log")); a.ep_ret = P<float>(g("ep_ret"));
+    a.ep_len = P<float>(g("ep_len"));
+    return a;
+  });
+  m.def("vec_host_tail", [](const VecHostTail& a, bool reset, uint64_t s) { vec_host_tail(a, reset, S(s)); },
+        py::arg("tail"), py::arg("reset"), py::arg("stream"));
   py::class_<VecAct>(m, "VecAct");
   m.def("make_vec_act", [](const VecNet& net, uint64_t ring, uint64_t hist, int E, uint64_t eps, uint64_t seed,
                            uint64_t counter, uint64_t q, uint64_t actions) {

@@ -882,6 +882,29 @@ void vec_classic_reset(const VecEnv& V, const int64_t* step_counter, int* new_fr
                        hipStream_t s);
 void vec_classic_step(const VecEnv& V, const int* actions, const int64_t* step_counter, float* reward, float* done,
                       int* new_frame, float* ep_log, hipStream_t s);
+// The acting step's env half over HOST envs (vector_host_kernels.hip vec_host_tail_k):
+// vec_classic_step with the device dynamics replaced by one staged host step.  `stage` is the
+// device copy of the vector env's staging block, fp32: next_obs [E][obs] | reset_obs [E][obs] |
+// reward [E] | done [E] | ended [E].  reset_obs[e] goes to ring row ((step + 1) E + e) mod F (the
+// row into new_frame[e]), reward and the env's own done flag into the shard's step buffers, and
+// `ended` (done or the length cap: a cap reset keeps done = 0) closes the episode in ep_log[e] =
+// (return, length, count + 1, untouched) from the running pair ep_ret / ep_len.  reset = true is
+// vec_classic_reset's contract: reset_obs to row (step E + e) mod F, hist[e][0..3] and
+// new_frame[e] that row, ep_log[e] and the running pair zeroed.
+struct VecHostTail {
+  int E, obs, F;         // envs, observation floats, frame-ring rows
+  const float* stage;
+  float* ring;           // the replay's frame ring viewed as [F][obs] fp32
+  const int64_t* step;   // the shard's step counter (read only: nstep_emit bumps it)
+  float* reward;         // [E]
+  float* done;           // [E]
+  int* new_frame;        // [E]
+  int* hist;             // [E][4] (written by the reset form only)
+  float* ep_log;         // [E][4]
+  float* ep_ret;         // [E] running return
+  float* ep_len;         // [E] running length
+};
+void vec_host_tail(const VecHostTail& a, bool reset, hipStream_t s);
 // Q[E][A] of the observations at ring row hist[e][3] + select_actions_k's epsilon-greedy draw
 struct VecAct {
   VecNet net;

@@ -17,6 +17,13 @@ episode return) and, every ``--eval-interval`` steps, the greedy return of
 rollout on a weight snapshot beside training (:class:`VectorEvaluator`), syncs only the training
 stream at a log line, and reports a finished evaluation in the next record as
 ``greedy_mean_return`` with ``greedy_step``, the step of its snapshot.
+
+``--host-envs`` trains on gym-API envs stepped on the CPU instead
+(:class:`~apex_amd.engine.vector_host.VectorHostEngine`): ``--env`` is then any ``envs.make`` id
+with a flat observation (<= 8 floats) and a discrete action space (<= 7 actions), one *step* of
+the loop is one step of all E host envs + ``--learner-steps`` SGD steps, overlapped unless
+``--host-serial``, and ``--eval-mode`` must be ``step`` (the host evaluator).  Same log tags,
+checkpoints and JSON log.
 """
 from __future__ import annotations
 
@@ -33,10 +40,37 @@ from .engine.vector import VECTOR_ENVS, VectorApexEngine, VectorEngineConfig, Ve
 EVAL_MODES = ("step", "rollout", "async")
 
 
+class _Parser(argparse.ArgumentParser):
+    """The rules between flags are parser errors (exit status 2), as a bad choice is."""
+
+    def parse_args(self, args=None, namespace=None):
+        a = super().parse_args(args, namespace)
+        if a.host_envs:
+            if a.eval_mode != "step":
+                self.error("--host-envs evaluates on the host: --eval-mode must be 'step'")
+            if a.learner_steps < 1:
+                self.error("--learner-steps must be >= 1")
+        else:
+            if a.env not in VECTOR_ENVS:
+                self.error(f"argument --env: invalid choice: {a.env!r} (choose from "
+                           f"{', '.join(map(repr, sorted(VECTOR_ENVS)))}; any envs.make id with --host-envs)")
+            if a.learner_steps != 1 or a.host_serial:
+                self.error("--learner-steps and --host-serial belong to --host-envs")
+        return a
+
+
 def parser() -> argparse.ArgumentParser:
     d = VectorEngineConfig()
-    p = argparse.ArgumentParser(description="Ape-X DQN on vector-observation envs (GPU-resident engine)")
-    p.add_argument("--env", default=d.env_id, choices=sorted(VECTOR_ENVS))
+    p = _Parser(description="Ape-X DQN on vector-observation envs (GPU-resident engine)")
+    p.add_argument("--env", default=d.env_id,
+                   help=f"one of {sorted(VECTOR_ENVS)}; with --host-envs any envs.make id")
+    p.add_argument("--host-envs", action="store_true",
+                   help="step gym-API envs on the CPU (flat observation <= 8, discrete actions <= 7)")
+    p.add_argument("--learner-steps", type=int, default=1, help="(--host-envs) SGD steps per env step")
+    p.add_argument("--host-serial", action="store_true",
+                   help="(--host-envs) learner steps, then the acting step: no overlap with the host's env step")
+    p.add_argument("--max-episode-length", type=int, default=50000,
+                   help="(--host-envs) reset an env after this many steps of one episode (done stays 0)")
     p.add_argument("--envs", type=int, default=d.n_envs, help="GPU envs (the reference's actor processes)")
     p.add_argument("--max-step", type=int, default=100_000, help="learner SGD steps")
     p.add_argument("--batch-size", type=int, default=d.batch_size)
@@ -72,14 +106,29 @@ def config_from_args(a) -> VectorEngineConfig:
     return VectorEngineConfig(env_id=a.env, n_envs=a.envs, batch_size=a.batch_size, n_step=a.n_step, gamma=a.gamma,
                               lr=a.lr, replay_capacity=a.capacity, actor_steps_per_learner_step=a.actor_steps,
                               nstep_mode=a.nstep_mode, target_update_interval=a.target_update_interval,
-                              publish_param_interval=a.publish_interval, seed=a.seed).validate()
+                              publish_param_interval=a.publish_interval, seed=a.seed).validate(not a.host_envs)
+
+
+def _crossed(t: int, prev: int, interval: int) -> bool:
+    """A multiple of ``interval`` in (prev, t] (``t % interval == 0`` when t = prev + 1)."""
+    return t // interval > prev // interval
+
+
+def make_engine(a, cfg: VectorEngineConfig):
+    if not a.host_envs:
+        return VectorApexEngine(cfg, a.device)
+    from .engine.vector_host import VectorHostEngine
+    from .envs.host_vector import HostVectorEnv
+
+    vec = HostVectorEnv(a.env, a.envs, seed=a.seed, max_episode_length=a.max_episode_length)
+    return VectorHostEngine(cfg, vec, a.device, learner_steps=a.learner_steps, host_overlap=not a.host_serial)
 
 
 def train(a) -> dict:
     cfg = config_from_args(a)
     if not torch.cuda.is_available():
         raise RuntimeError("train_vector needs a GPU (the host-side trainer is apex_amd.trainers.apex_single)")
-    eng = VectorApexEngine(cfg, a.device)
+    eng = make_engine(a, cfg)
     eng.fill()
     mode = a.eval_mode
     asyn = VectorEvaluator(eng, a.eval_episodes) if mode == "async" and a.eval_interval > 0 else None
@@ -91,12 +140,13 @@ def train(a) -> dict:
     ep_seen = torch.zeros(cfg.n_envs, device=eng.device)
     try:
         while eng.learn_steps < a.max_step:
+            prev = eng.learn_steps
             eng.train_step()
-            t = eng.learn_steps
+            t = eng.learn_steps   # (prev + 1; prev + --learner-steps on host envs)
             final = t >= a.max_step
-            if t % a.save_interval == 0 or final:
+            if _crossed(t, prev, a.save_interval) or final:
                 eng.save(model_path(a.save_dir, t))
-            ev = a.eval_interval > 0 and (t % a.eval_interval == 0 or final)
+            ev = a.eval_interval > 0 and (_crossed(t, prev, a.eval_interval) or final)
             if ev and asyn is not None:
                 # snapshot + side-stream rollout; no log line and no sync of its own.  The last step's
                 # evaluation must run: wait out (and drop, they are superseded) earlier ones
@@ -105,7 +155,7 @@ def train(a) -> dict:
                     asyn.wait()
                     launched = asyn.launch(tag=t)
                 ev = False
-            if not (t % a.log_interval == 0 or final or ev):
+            if not (_crossed(t, prev, a.log_interval) or final or ev):
                 continue
             if asyn is not None:
                 torch.cuda.current_stream(eng.device).synchronize()  # the side stream keeps running
@@ -137,6 +187,8 @@ def train(a) -> dict:
     finally:
         if jl:
             jl.close()
+        if a.host_envs:
+            eng.close()
     return last
 
 
