@@ -1158,17 +1158,38 @@ constexpr int kC1xGridLearner = 384;
 constexpr int kC1xDrawMax = 8;  // samples per workgroup with the folded draw (2 per wave)
 constexpr int kC1xChunks = 4 * (kPlane / 16), kC1xPer = (kC1xChunks + 255) / 256;  // 16-byte u8 chunks
 
+// sample b's four frame ids (frame_plane's lookup, once per sample): idx[b] is read once and the
+// row's four adjacent ids come back together -- one 16-byte load where the row is 16-byte aligned,
+// else four loads issued before any is used: two dependent round trips, one wait for the four.
+// (Four frame_plane calls compiled to four serial idx -> ids pairs, each under its own branch:
+// eight dependent round trips per sample.)
+// Without ids the input is dense: planes 4 b .. 4 b + 3.
+__device__ __forceinline__ int4 frame_ids4(const FrameSrc& f, int b) {
+  if (!f.ids) return make_int4(4 * b, 4 * b + 1, 4 * b + 2, 4 * b + 3);
+  const int row = f.idx ? f.idx[b] : b;
+  const int* r = f.ids + (size_t)row * 4;
+  if ((reinterpret_cast<uintptr_t>(r) & 15) == 0) return *reinterpret_cast<const int4*>(r);
+  const int i0 = r[0], i1 = r[1], i2 = r[2], i3 = r[3];
+  return make_int4(i0, i1, i2, i3);
+}
+
+__device__ __forceinline__ int opaque_i(int x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
 // the sample's 4 x 441 16-byte u8 chunks -> registers (issued, not waited on); fid (the folded
 // draw): the sample's 4 frame ids, drawn by this workgroup
 __device__ __forceinline__ void c1x_load(const F32Set& set, int smp, uint4 (&v)[kC1xPer], const int* fid) {
-  const int B = set.B, prob = smp / B, b = smp - prob * B, t = threadIdx.x;
+  // (t opaque: the chunks' plane and offset are recomputed per sample, ~10 VALU each; hoisted out
+  // of the sample loop they held 7 registers across the tile loop, which has none to spare)
+  const int B = set.B, prob = smp / B, b = smp - prob * B, t = opaque_i(threadIdx.x);
   const F32Prob p = pick(set, prob);
   const uint8_t* fr = static_cast<const uint8_t*>(p.in);
-  const FrameSrc f{fr, p.ids, p.idx};
-  const uint4* s0 = reinterpret_cast<const uint4*>(fid ? fr + (size_t)fid[0] * kPlane : frame_plane(f, b, 0, kPlane));
-  const uint4* s1 = reinterpret_cast<const uint4*>(fid ? fr + (size_t)fid[1] * kPlane : frame_plane(f, b, 1, kPlane));
-  const uint4* s2 = reinterpret_cast<const uint4*>(fid ? fr + (size_t)fid[2] * kPlane : frame_plane(f, b, 2, kPlane));
-  const uint4* s3 = reinterpret_cast<const uint4*>(fid ? fr + (size_t)fid[3] * kPlane : frame_plane(f, b, 3, kPlane));
+  const int4 id = fid ? make_int4(fid[0], fid[1], fid[2], fid[3]) : frame_ids4(FrameSrc{fr, p.ids, p.idx}, b);
+  const uint4* s0 = reinterpret_cast<const uint4*>(fr + (size_t)id.x * kPlane);
+  const uint4* s1 = reinterpret_cast<const uint4*>(fr + (size_t)id.y * kPlane);
+  const uint4* s2 = reinterpret_cast<const uint4*>(fr + (size_t)id.z * kPlane);
+  const uint4* s3 = reinterpret_cast<const uint4*>(fr + (size_t)id.w * kPlane);
 #pragma unroll
   for (int k = 0; k < kC1xPer; ++k) {  // (no dynamically indexed pointer array: it would live in scratch)
     const int e = min(t + 256 * k, kC1xChunks - 1), c = e / 441;  // tail lanes reload a valid chunk
@@ -1196,15 +1217,16 @@ __device__ __forceinline__ void c1x_store(const uint4 (&v)[kC1xPer], uint32_t* x
 
 // Software-pipelined over the workgroup's samples: the next sample's frame chunks are
 // loaded into registers before this sample's MFMA loop, so the frame-ring (HBM) latency
-// hides behind compute; they are converted into LDS after the loop.
+// hides behind compute; they are converted into LDS after the loop.  No other global load is
+// issued between that prefetch and the end of the tile loop: vmcnt retires in order, so a wait for
+// any younger load waits out the whole frame gather (the lane's bias, loaded per sample, put a
+// vmcnt(0) in the tile loop's preheader; it now loads with the weights at a problem change).
 // The two 8-byte halves of a pixel fragment load as two ds_read_b64 (2 LDS cycles each,
 // 256 B/clk) instead of the ds_read2_b64 the compiler would merge them into (8 cycles,
-// 128 B/clk): the second address is hidden from the load/store merger (one v_add per fragment;
+// 128 B/clk): the addresses are hidden from the load/store merger (four v_adds per tile;
 // MI355X, 3 x 512 samples: 44.6 vs 46.5 us)
-__device__ __forceinline__ int opaque_i(int x) {
-  asm volatile("" : "+v"(x));
-  return x;
-}
+// sched_barrier mask: VALU (2), SALU (4) and VMEM (16) may cross; LDS instructions and MFMAs may not
+constexpr int kC1xPin = 0x2 | 0x4 | 0x10;
 // cs.out_idx (the learner): the PER draw folded in -- wave k draws sample s0 + k's slot (the
 // per_sample_k descent, same arithmetic: identical slots and IS weights) and its 4 frame ids go
 // to LDS before the first frame load; workgroups past cs.nhost scatter the staged actor rows.
@@ -1224,6 +1246,7 @@ __global__ __launch_bounds__(256, 2) void f32_conv1_fwd_x3_k(F32Set set, ConvSam
   }
   const __bf16* xb = reinterpret_cast<const __bf16*>(xs);
   W1Split w;
+  float4 bias4 = make_float4(0.f, 0.f, 0.f, 0.f);  // channels nh * 16 + 4 q .. + 3 of problem cur
   int cur = -1;
   uint4 v[kC1xPer];
   // a contiguous run of samples per workgroup: the weight split is redone only at a
@@ -1279,6 +1302,10 @@ __global__ __launch_bounds__(256, 2) void f32_conv1_fwd_x3_k(F32Set set, ConvSam
     if (prob != cur) {  // block-uniform
       cur = prob;
       split_w1(p.w + (nh * 16 + i) * 256 + (q >> 1) * 16 + (q & 1) * 4, w);
+      bias4.x = p.bias[nh * 16 + 4 * q];  // waited out with the weights, ahead of the prefetch below
+      bias4.y = p.bias[nh * 16 + 4 * q + 1];
+      bias4.z = p.bias[nh * 16 + 4 * q + 2];
+      bias4.w = p.bias[nh * 16 + 4 * q + 3];
     }
     __syncthreads();  // the previous sample's tiles are done with xs
     c1x_store(v, xs);
@@ -1286,15 +1313,13 @@ __global__ __launch_bounds__(256, 2) void f32_conv1_fwd_x3_k(F32Set set, ConvSam
     if (smp + 1 < s1) c1x_load(set, smp + 1, v, draw ? fid[smp + 1 - s0] : nullptr);  // in flight during the MFMAs
     // roles swapped on the MFMA (A = the weight slice, B = the pixels: identical lane maps),
     // so lane (i, q) ends with channels 4q .. 4q+3 of pixel i -- one 16-byte store
-    float* out = p.out + (size_t)b * 400 * 32 + nh * 16 + 4 * q;
+    // (a block-uniform base and a 32-bit lane offset: per-lane 64-bit pointers, one per tile of the
+    // pair, cost the tile loop four registers it no longer has to spare)
+    char* out = reinterpret_cast<char*>(p.out + (size_t)b * 400 * 32);
+    const uint32_t out_l = (uint32_t)(nh * 16 + 4 * q + i * 32) * 4u;
     // sign bits [B][400] words of 32 channels: this wave's 16 channels are half nh of a word
-    uint16_t* bits =
-        BITS && p.relu_bits ? reinterpret_cast<uint16_t*>(p.relu_bits + (size_t)b * 400) + nh : nullptr;
-    float4 bias4;
-    bias4.x = p.bias[nh * 16 + 4 * q];
-    bias4.y = p.bias[nh * 16 + 4 * q + 1];
-    bias4.z = p.bias[nh * 16 + 4 * q + 2];
-    bias4.w = p.bias[nh * 16 + 4 * q + 3];
+    char* bits = BITS && p.relu_bits ? reinterpret_cast<char*>(p.relu_bits + (size_t)b * 400) : nullptr;
+    const uint32_t bits_l = (uint32_t)(i * 2 + nh) * 2u;
     // pixel fragments: lane (i, q = 2p + h) reads 4 columns 4 ox + 4h .. +3 of kernel rows 2p and
     // 2p + 1 (two ds_read_b64, 42 dwords apart).  Within a 32-lane LDS group (q = 0, 1) lane
     // (ox, h = 1) reads the same dwords as lane (ox + 1, h = 0) -- stride-4 windows overlap by 4
@@ -1302,11 +1327,17 @@ __global__ __launch_bounds__(256, 2) void f32_conv1_fwd_x3_k(F32Set set, ConvSam
     // conflicts (rows in the lane groups gave 1.84 conflict cycles per LDS cycle)
     auto frags = [&](int tile, bfx8 (&a)[8]) {
       const int m = tile * 16 + i, oy = m / 20, ox = m - oy * 20;
-      const __bf16* a0 = xb + (4 * oy + 2 * (q >> 1)) * 84 + 4 * ox + 4 * (q & 1);
+      // in 8-byte units (4 bf16): kernel row 2p of k-block 0; its next kernel row is 21 units on and
+      // the odd k-blocks' rows (4 kernel rows down) 84 on.  Four opaque bases per tile, the planes as
+      // immediate offsets (the hidden addresses used to be one constant 21 per read, each in a
+      // register of its own across the MFMAs, beside one strength-reduced base per plane)
+      const int e0 = (4 * oy + 2 * (q >> 1)) * 21 + ox + (q & 1);
+      const int e[4] = {opaque_i(e0), opaque_i(e0 + 21), opaque_i(e0 + 84), opaque_i(e0 + 105)};
+      const uint2* x2 = reinterpret_cast<const uint2*>(xb);
 #pragma unroll
       for (int kb = 0; kb < 8; ++kb) {  // 8-byte aligned: two ds_read_b64
-        const uint2* ap = reinterpret_cast<const uint2*>(a0 + (kb >> 1) * kPlane + (kb & 1) * 4 * 84);
-        const uint2 lo = ap[0], hi = ap[opaque_i(21)];  // next kernel row (84 bf16 = 21 x 8 bytes)
+        const int pl = (kb >> 1) * (kPlane / 4);
+        const uint2 lo = x2[e[2 * (kb & 1)] + pl], hi = x2[e[2 * (kb & 1) + 1] + pl];  // hi: next kernel row
         a[kb] = __builtin_bit_cast(bfx8, make_uint4(lo.x, lo.y, hi.x, hi.y));
       }
     };
@@ -1324,7 +1355,7 @@ __global__ __launch_bounds__(256, 2) void f32_conv1_fwd_x3_k(F32Set set, ConvSam
       y.y = fmaxf(ah[1] + (am[1] + al[1]) + bias4.y, 0.f);
       y.z = fmaxf(ah[2] + (am[2] + al[2]) + bias4.z, 0.f);
       y.w = fmaxf(ah[3] + (am[3] + al[3]) + bias4.w, 0.f);
-      *reinterpret_cast<float4*>(out + (size_t)(tile * 16 + i) * 32) = y;
+      *reinterpret_cast<float4*>(out + (out_l + (uint32_t)tile * 2048u)) = y;
       if constexpr (decltype(WB)::value) {
         // the wave's 16 channels of pixel i from four ballots (bit 16 q + i of ballot j = channel
         // 4 q + j): VALU only, no branch in the tile loop (the sample's whole loop is compiled twice,
@@ -1336,10 +1367,14 @@ __global__ __launch_bounds__(256, 2) void f32_conv1_fwd_x3_k(F32Set set, ConvSam
         const uint32_t T = lo(b0) | lo(b1) << 1 | lo(b2) << 2 | lo(b3) << 3;  // bit j: q = 0, bit 16 + j: q = 1
         const uint32_t U = hi(b0) | hi(b1) << 1 | hi(b2) << 2 | hi(b3) << 3;  // bit j: q = 2, bit 16 + j: q = 3
         const uint32_t nb = (T & 0xFu) | ((T >> 12) & 0xF0u) | ((U & 0xFu) << 8) | ((U >> 4) & 0xF000u);
-        bits[(tile * 16 + i) * 2] = (uint16_t)nb;
+        *reinterpret_cast<uint16_t*>(bits + (bits_l + (uint32_t)tile * 64u)) = (uint16_t)nb;
       }
     };
     // ping-pong fragment buffers: the next tile's LDS reads are in flight during this tile's MFMAs.
+    // The scheduler sank the reads into the MFMA stream, next to their uses (13 lgkmcnt waits per
+    // pair of tiles, several right behind their reads); a scheduling barrier that neither LDS
+    // instructions nor MFMAs may cross keeps each tile's 16 reads ahead of the previous tile's first
+    // MFMA, so the waits in front of a tile's MFMAs cover the older buffer only.
     // Wave parity t0 owns tiles t0, t0 + 2, ...: 6 pairs (+ tile 24 for t0 = 0); every fragment
     // load is unconditional (the one past parity 1's last tile re-reads tile 24, unused), so the
     // buffers keep fixed registers (guarded loads + a mid-loop exit made the compiler copy them)
@@ -1350,9 +1385,13 @@ __global__ __launch_bounds__(256, 2) void f32_conv1_fwd_x3_k(F32Set set, ConvSam
       for (int pr = 0; pr < 6; ++pr) {
         const int tile = t0 + 4 * pr;
         frags(tile + 2, fb);
+        __builtin_amdgcn_sched_barrier(kC1xPin);
         tile_mfma(tile, fa, WB);
+        __builtin_amdgcn_sched_barrier(kC1xPin);
         frags(min(tile + 4, 24), fa);
+        __builtin_amdgcn_sched_barrier(kC1xPin);
         tile_mfma(tile + 2, fb, WB);
+        __builtin_amdgcn_sched_barrier(kC1xPin);
       }
       if (t0 == 0) tile_mfma(24, fa, WB);
     };
