@@ -57,6 +57,18 @@ class ActorShard(NStepShard):
                                self.step_counter.data_ptr(), self.new_frame.data_ptr(), self.st["hist"].data_ptr(),
                                self.ep_log.data_ptr(), self._stream())
 
+    def state_tensors(self) -> dict[str, torch.Tensor]:
+        """+ the env state and the staging sets (rows, slots, priorities) that ``apply_staged`` /
+        ``staged_rows`` read on a later step.  ``obs`` is rewritten by every ``observe()``."""
+        out = super().state_tensors()
+        out["env_state"] = self.env_state
+        for i in range(self.staged):
+            out[f"stage_slot[{i}]"] = self.stage_slot[i]
+            out[f"stage_prio[{i}]"] = self.stage_prio[i]
+            for k, v in self.stage[i].items():
+                out[f"stage[{i}].{k}"] = v
+        return out
+
     def observe(self) -> torch.Tensor:
         """Current stacked observations u8 [E,4,84,84] (gathered from the frame ring)."""
         self.replay.gather_frames(self.st["hist"], self.obs)

@@ -254,24 +254,31 @@ class ApexEngine:
         self._drain_mass()
         warm_up(self.device, self.train_step, warmup_iters)  # full eager train steps (counters, publish/target cadence)
         torch.cuda.synchronize(self.device)
-        self._pool = torch.cuda.graph_pool_handle()
-        if self.overlap:
-            self._capture_overlap_graphs(torch.cuda.graph_pool_handle())  # actor graphs run concurrently:
-        else:                                                           # never share their memory
-            L = self.learner
-            self._g_actor = capture_graph(self._actor_body, self._pool)
-            if self._dp:
-                self._g_learn_a = capture_graph(L.forward_phase, self._pool)
-                self._g_learn_a2 = capture_graph(L.backward_phase, self._pool)
-                self._g_learn_b = capture_graph(self._learn_b, self._pool)
-            else:  # no host collective in between: one graph per step
-                self._g_learn_a = capture_graph(lambda: (L.forward_phase(), self._learn_b()), self._pool)
+        self._capture_graphs()
         self._captured = True
         torch.cuda.synchronize(self.device)
         if self.overlap:
             self._ev_learn.record(torch.cuda.current_stream(self.device))
         for _ in range(warm_replays):
             self.train_step()
+
+    def _capture_graphs(self) -> None:
+        """The step's graphs from the eager bodies (every kernel has run before): launches
+        nothing.  Earlier graphs are dropped."""
+        self._g_actor = self._g_learn_a = self._g_learn_a2 = self._g_learn_b = self._g_dp = None
+        self._g_learn_front = None
+        self._pool = torch.cuda.graph_pool_handle()
+        if self.overlap:
+            self._capture_overlap_graphs(torch.cuda.graph_pool_handle())  # actor graphs run concurrently:
+            return                                                      # never share their memory
+        L = self.learner
+        self._g_actor = capture_graph(self._actor_body, self._pool)
+        if self._dp:
+            self._g_learn_a = capture_graph(L.forward_phase, self._pool)
+            self._g_learn_a2 = capture_graph(L.backward_phase, self._pool)
+            self._g_learn_b = capture_graph(self._learn_b, self._pool)
+        else:  # no host collective in between: one graph per step
+            self._g_learn_a = capture_graph(lambda: (L.forward_phase(), self._learn_b()), self._pool)
 
     def _capture_overlap_graphs(self, apool) -> None:
         """Overlap mode: graphs per staging half (actor: fill half h; learner: apply half
@@ -486,3 +493,89 @@ class ApexEngine:
 
     def save(self, path: str) -> None:
         torch.save(self.learner.model.state_dict(), path)
+
+    # ------------------------------------------------------------------ full-state checkpoints
+    def _state_supported(self) -> None:
+        if self._allreduce is not None or self._sharded is not None:
+            raise NotImplementedError("full-state checkpoints cover the single-GPU engine: not the data-parallel "
+                                      "(allreduce) or sharded topologies")
+
+    def state_tensors(self) -> dict[str, torch.Tensor]:
+        """Every persistent device tensor of the engine, ``<component>.<name>`` -> tensor."""
+        parts = {"replay": self.replay, "actor": self.actor, "learner": self.learner, "policy": self.policy}
+        return {f"{c}.{k}": t for c, obj in parts.items() for k, t in obj.state_tensors().items()}
+
+    def state_geometry(self) -> dict:
+        """What a checkpoint must agree on with the engine it is loaded into."""
+        rp, lc = self.replay, self.cfg.learner
+        return {"engine": "apex", "capacity": rp.capacity, "frame_capacity": rp.frame_capacity,
+                "frame_bytes": rp.frame_bytes, "E": self.actor.E, "A": self.actor.A, "n_step": self.actor.n,
+                "batch": lc.batch_size, "params": self.learner.P, "overlap": int(self.overlap),
+                "staged": self.actor.staged, "forward": lc.forward, "dtype": lc.dtype}
+
+    def host_state(self) -> dict:
+        return {"learn_steps": self.learn_steps, "actor_steps": self.actor_steps, "half": self._half,
+                "actor_seed": self.actor.host_state()["seed"], "replay_seed": self.replay.seed,
+                **self.learner.host_state()}
+
+    def load_host_state(self, st: dict) -> None:
+        self.learn_steps, self.actor_steps, self._half = int(st["learn_steps"]), int(st["actor_steps"]), int(st["half"])
+        self.actor.load_host_state({"seed": st["actor_seed"]})
+        self.replay.seed = int(st["replay_seed"])
+        self.learner.load_host_state(st)
+
+    def _quiesce(self) -> None:
+        """The actor stream joined to the current stream, then the device idle."""
+        if self._astream is not None:
+            torch.cuda.current_stream(self.device).wait_stream(self._astream)
+        torch.cuda.synchronize(self.device)
+
+    def save_state(self, path: str, chunk_bytes: int = 64 << 20) -> dict:
+        """Checkpoint the whole engine -- replay (live rows only), actor shard, learner, acting
+        weights, counters -- as the directory ``path`` (utils/engine_state.py).  Blocking: the
+        actor stream is joined and the device synchronised first.  Returns the manifest."""
+        from ..utils.engine_state import save_engine_state
+
+        self._state_supported()
+        self._quiesce()
+        rows = {f"replay.{k}": n for k, n in self.replay.live_rows(self.actor.frames_written()).items()}
+        tensors = {k: (t, rows[k]) if k in rows else t for k, t in self.state_tensors().items()}
+        return save_engine_state(path, tensors, self.host_state(), self.state_geometry(), chunk_bytes)
+
+    def load_state(self, path: str, chunk_bytes: int = 64 << 20) -> dict:
+        """Continue the run saved by :meth:`save_state`: every listed tensor is restored exactly, and
+        the continuation equals the uninterrupted run bit for bit wherever the engine itself is
+        reproducible (the serial engine; the overlapped engine with the one-launch tree write
+        of the fp32 HIP learner -- profiles/engine_state.md).  Call it on an engine built
+        with the same geometry, after ``fill()`` and ``capture()``: everything those wrote --
+        the warm-up train steps included -- is overwritten in place (the captured graphs keep
+        their addresses).  Then the packed weight copies are rebuilt from the loaded masters,
+        the host counters and the draw keys restored (the keys are launch arguments: graphs
+        captured under other keys are captured again, which launches nothing), and the overlap
+        events re-recorded on an idle device.  The checkpoint must cover every row this engine
+        has written (checked before anything is overwritten).  Returns the checkpoint's host
+        scalars."""
+        from ..utils.engine_state import check_covers, load_engine_state
+
+        self._state_supported()
+        self._quiesce()
+        check_covers(path, {f"replay.{k}": n
+                            for k, n in self.replay.live_rows(self.actor.frames_written()).items()})
+        host = load_engine_state(path, self.state_tensors(), self.state_geometry(), chunk_bytes)
+        keys = (self.actor.seed, self.replay.seed)
+        self.load_host_state(host)
+        self.learner.refresh_packed()
+        self.learner.refresh_target_packed()
+        self.policy.refresh_packed()
+        self._drain_mass()
+        torch.cuda.synchronize(self.device)
+        if self._captured and keys != (self.actor.seed, self.replay.seed):
+            self._capture_graphs()
+            torch.cuda.synchronize(self.device)
+        if self.overlap:
+            cur = torch.cuda.current_stream(self.device)
+            self._ev_learn.record(cur)
+            for ev in self._ev_actor:
+                ev.record(cur)
+        torch.cuda.synchronize(self.device)
+        return host

@@ -84,6 +84,28 @@ class HBMReplay:
                    self.leaf_min, *self.node_sum, *self.node_min]
         return sum(t.numel() * t.element_size() for t in tensors)
 
+    # ------------------------------------------------------------------ persistent state
+    def state_tensors(self) -> dict[str, torch.Tensor]:
+        """Every tensor a later step reads from an earlier one (full-state checkpoints,
+        utils/engine_state.py).  ``owner`` / ``wlist`` / ``ticket`` / ``sorted_scratch`` are
+        scratch: rewritten (or restored to their idle value) by every launch that reads them."""
+        out = {"frames": self.frames, "s_ids": self.s_ids, "s2_ids": self.s2_ids, "action": self.action,
+               "reward": self.reward, "done": self.done, "leaf_sum": self.leaf_sum, "leaf_min": self.leaf_min,
+               "max_prio": self.max_prio, "filled": self.filled}
+        for i, (ns, nm) in enumerate(zip(self.node_sum, self.node_min)):
+            out[f"node_sum[{i}]"] = ns
+            out[f"node_min[{i}]"] = nm
+        return out
+
+    def live_rows(self, frames_written: int) -> dict[str, int]:
+        """Leading rows of :meth:`state_tensors` that hold data: the transition tables and the
+        leaves up to ``min(capacity, filled)``, the frame ring up to ``frames_written`` (all of
+        it once it has wrapped).  Reads ``filled`` (a host sync)."""
+        n = min(self.capacity, int(self.filled.item()))
+        rows = {k: n for k in ("s_ids", "s2_ids", "action", "reward", "done", "leaf_sum", "leaf_min")}
+        rows["frames"] = max(0, min(self.frame_capacity, int(frames_written)))
+        return rows
+
     def trans_ptrs(self) -> dict:
         return {"s_ids": self.s_ids.data_ptr(), "s2_ids": self.s2_ids.data_ptr(), "action": self.action.data_ptr(),
                 "reward": self.reward.data_ptr(), "done": self.done.data_ptr()}

@@ -449,6 +449,81 @@ class HostEnvEngine:
         """``torch.save(state_dict)`` with the reference keys (utils/checkpoint.py)."""
         return save_model(self.learner.model, path)
 
+    # ------------------------------------------------------------------ full-state checkpoints
+    def state_tensors(self) -> dict[str, torch.Tensor]:
+        """What a replay-preserving resume restores: the replay, the learner, the acting weights
+        and the shard's step counter (it places the next frame and slot).  The emulators are host
+        objects: env state, open n-step windows and the episode accumulators are not saved."""
+        parts = {"replay": self.replay, "learner": self.learner, "policy": self.policy}
+        out = {f"{c}.{k}": t for c, obj in parts.items() for k, t in obj.state_tensors().items()}
+        out["actor.step_counter"] = self.actor.step_counter
+        return out
+
+    def state_geometry(self) -> dict:
+        rp, lc = self.replay, self.cfg.learner
+        return {"engine": "host_env", "capacity": rp.capacity, "frame_capacity": rp.frame_capacity,
+                "frame_bytes": rp.frame_bytes, "E": self.E, "A": self.A, "n_step": self.actor.n,
+                "batch": lc.batch_size, "params": self.learner.P, "forward": lc.forward, "dtype": lc.dtype}
+
+    def host_state(self) -> dict:
+        return {"learn_steps": self.learn_steps, "actor_steps": self.actor_steps, "actor_seed": self.actor.seed,
+                "replay_seed": self.replay.seed, **self.learner.host_state()}
+
+    def save_state(self, path: str, chunk_bytes: int = 64 << 20) -> dict:
+        """Checkpoint the replay (live rows only), the learner, the acting weights and the
+        counters as the directory ``path`` (utils/engine_state.py), between two iterations.
+        Blocking.  The transitions still inside the open n-step windows (at most n * E rows) are
+        not part of it: a resumed run starts its windows afresh."""
+        from ..utils.engine_state import save_engine_state
+
+        torch.cuda.synchronize(self.device)
+        rows = {f"replay.{k}": n for k, n in self.replay.live_rows(self.actor.frames_written()).items()}
+        tensors = {k: (t, rows[k]) if k in rows else t for k, t in self.state_tensors().items()}
+        return save_engine_state(path, tensors, self.host_state(), self.state_geometry(), chunk_bytes)
+
+    def load_state(self, path: str, chunk_bytes: int = 64 << 20) -> dict:
+        """Replay-preserving resume: restore what :meth:`save_state` wrote into this engine (built
+        with the same geometry over fresh envs), then start the envs afresh.  Not bit for bit --
+        the emulators cannot be restored, and the rows inside the n-step windows that were open
+        at save time (at most n * E) are lost.
+
+        The frame ring and the slots advance in lockstep (a step with counter ``c`` writes frames
+        ``(c + 1) * E + e`` and slots ``c * E + e``; a reset writes frames ``c * E + e``), so a
+        reset at the restored counter would land on the newest frames, which the newest
+        transitions reference.  One dead step is spent first: its E slots get priority 0 through
+        the ordinary tree write (which advances ``filled`` and the step counter, as after a step
+        whose windows emitted nothing), the n-step windows are cleared, and the reset then
+        writes the frames that step would have written."""
+        from ..utils.engine_state import check_covers, load_engine_state
+
+        torch.cuda.synchronize(self.device)
+        check_covers(path, {f"replay.{k}": n
+                            for k, n in self.replay.live_rows(self.actor.frames_written()).items()})
+        host = load_engine_state(path, self.state_tensors(), self.state_geometry(), chunk_bytes)
+        keys = (self.actor.seed, self.replay.seed)
+        self.learn_steps, self.actor_steps = int(host["learn_steps"]), int(host["actor_steps"])
+        self.actor.load_host_state({"seed": host["actor_seed"]})
+        self.replay.seed = int(host["replay_seed"])
+        self.learner.load_host_state(host)
+        self.learner.refresh_packed()
+        self.learner.refresh_target_packed()
+        self.policy.refresh_packed()
+        a, rp = self.actor, self.replay
+        step = int(a.step_counter.item())
+        a.slot.copy_(((step * self.E + torch.arange(self.E, device=self.device)) % rp.capacity).to(torch.int32))
+        a.prio.zero_()
+        rp.write_batch(pre=(a.slot, a.prio, rp.filled), bump=a.step_counter)   # the dead step
+        self.actor_steps += 1
+        for t in a.st.values():
+            t.zero_()
+        a.acc.zero_()
+        a.reset(self.vec)
+        torch.cuda.synchronize(self.device)
+        if self._g_learn is not None and keys != (a.seed, rp.seed):   # the draw key is a launch argument
+            self._g_learn = capture_graph(self._learn_body)
+            torch.cuda.synchronize(self.device)
+        return host
+
     def close(self) -> None:
         """Finish the queued work, release the staging block and close a vector env that has a
         ``close`` (a worker pool: its processes stop, its shared block is unlinked).  Idempotent."""

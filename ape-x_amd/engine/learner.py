@@ -494,6 +494,31 @@ class DQNLearner:
         if self.hip_net:
             self.net.repack()
 
+    def state_tensors(self) -> dict[str, torch.Tensor]:
+        """What a later step reads from an earlier one (full-state checkpoints): the weights, the
+        target, the optimizer moments, the step counter (also the PER draw counter), and the
+        last step's scalars ``stats()`` reports.  Workspaces, the gradient buffer, partials and
+        the sampled batch are rewritten by every step before they are read; the packed weight
+        copies are rebuilt on load (:meth:`refresh_packed`)."""
+        out = {"flat": self.flat, "tflat": self.tflat, "opt_s1": self.opt_s1, "opt_s2": self.opt_s2,
+               "step_counter": self.step_counter, "beta": self.beta, "norms": self.norms, "loss": self.loss}
+        if self.hip_net:
+            out["step_snap"] = self.step_snap
+        if self.rows is not None:
+            out.update({f"rows.{k}": v for k, v in self.rows.items()})
+        return out
+
+    def host_state(self) -> dict:
+        return {"host_steps": self.host_steps}
+
+    def load_host_state(self, st: dict) -> None:
+        self.host_steps = int(st["host_steps"])
+
+    def refresh_target_packed(self) -> None:
+        """The target net's packed copies from ``tflat`` (after a load)."""
+        if self.hip_net:
+            self.tnet.repack()
+
     def sync_target(self) -> None:
         self.hip.copy_f32(self.tflat.data_ptr(), self.flat.data_ptr(), self.P, self._stream())
         if self.hip_net:

@@ -104,6 +104,27 @@ class NStepShard:
                             self.done.data_ptr(), self.new_frame.data_ptr(), self.step_counter.data_ptr(),
                             slot.data_ptr(), prio.data_ptr(), self._stream(), bump)
 
+    def state_tensors(self) -> dict[str, torch.Tensor]:
+        """The shard's persistent device state (full-state checkpoints): the n-step batcher's
+        ``st`` and the per-step buffers a later step or the host reads.  A subclass adds its
+        front end's."""
+        out = {f"st.{k}": v for k, v in self.st.items()}
+        for k in ("eps", "new_frame", "ep_log", "q", "actions", "reward", "done", "slot", "prio", "step_counter"):
+            out[k] = getattr(self, k)
+        return out
+
+    def host_state(self) -> dict:
+        """Host scalars of the shard: the key of its counter-based draws."""
+        return {"seed": self.seed}
+
+    def load_host_state(self, st: dict) -> None:
+        self.seed = int(st["seed"])
+
+    def frames_written(self) -> int:
+        """Frame-ring positions written so far: a reset writes ``step * E + e``, a step
+        ``(step + 1) * E + e`` (reads ``step_counter``: a host sync)."""
+        return (int(self.step_counter.item()) + 1) * self.E
+
     def episode_stats(self) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """(last episode return, last episode length, finished episode count) per env."""
         return self.ep_log[:, 0], self.ep_log[:, 1], self.ep_log[:, 2]
@@ -129,6 +150,14 @@ class ActorPolicy:
             self.net = make_hip_net(model, dtype)
             self.ws = make_workspace(E, A, device, dtype)
             self.ws.q = q
+
+    def state_tensors(self) -> dict[str, torch.Tensor]:
+        return {"flat": self.flat}
+
+    def refresh_packed(self) -> None:
+        """Re-derive the HIP net's packed copies after ``flat`` was written from outside."""
+        if self.hip_net:
+            self.net.repack()
 
     def publish_from(self, learner) -> None:
         """Learner -> acting weights (flat parameters, and the HIP net's packed copies)."""

@@ -57,6 +57,7 @@ HIP_SOURCES = [
     "vector_host_kernels.hip",
     "host_env_kernels.hip",
     "host_eval_kernels.hip",
+    "checkpoint_kernels.hip",
     "comm.cpp",
     "ipc.cpp",
 ]

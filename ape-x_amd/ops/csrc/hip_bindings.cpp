@@ -628,6 +628,9 @@ PYBIND11_MODULE(_apex_hip, m) {
   m.def("copy_f32", [](uint64_t dst, uint64_t src, int64_t n, uint64_t s) {
     copy_f32(P<float>(dst), P<const float>(src), n, S(s));
   });
+  m.def("state_digest", [](uint64_t ptr, int64_t nbytes, uint64_t s) {
+    return state_digest(P<const void>(ptr), nbytes, S(s));
+  }, py::arg("ptr"), py::arg("nbytes"), py::arg("stream"));
 
   // ---- AQL kernels
   py::class_<AQLNet>(m, "AQLNet");

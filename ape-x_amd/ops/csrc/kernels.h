@@ -356,6 +356,13 @@ void copy_f32(float* dst, const float* src, int64_t n, hipStream_t s);
 // the engine's stream-concurrency probe).
 void spin_us(int us, hipStream_t s);
 
+// ---- checkpoint_kernels.hip (full-state checkpoints, utils/engine_state.py)
+// Position-sensitive 64-bit digest of `nbytes` bytes at `ptr` (any alignment): little-endian
+// 64-bit words, tail zero-padded, each salted with its index and mixed, summed mod 2^64 with
+// the length mixed in (`digest_host` in engine_state.py is the definition).  Two launches on
+// `s`, then the one host wait that reads the value back.
+uint64_t state_digest(const void* ptr, int64_t nbytes, hipStream_t s);
+
 // ---- conv_kernels.hip (Nature-CNN dueling net, bf16 MFMA)
 // layer 1: `in` is the u8 frame ring (ids/idx: FrameSrc, see common.h) or a dense u8 stack
 // Multi-problem forward launches: up to kMaxProbs independent passes of the same layer

@@ -332,6 +332,18 @@ __device__ __forceinline__ void update_levels_fast(const TreeDesc& t, const int*
   update_levels_block(t, sids, n, lo, hi);
 }
 
+// A slot whose actor row of this launch emitted nothing (raw priority 0) is voided: its old row
+// must not come back.  The learner may have drawn that slot in this very step -- the tree still
+// held the old priority -- and its leaf lands after the actor's, which would re-arm the slot for
+// another lap of the ring while the actor overwrites the old row's frames.  The voided slot's
+// dedup claim is therefore held by a sentinel no learner row can beat (and released at the end).
+constexpr int kVoidedClaim = 0x7fffffff;
+__device__ __forceinline__ void claim_voided(const TreeDesc& t, const BatchWrite& w, int i, int claim) {
+  const int id = w.pre_idx[i];
+  if (id >= 0 && id < t.size[0] && !(w.pre_prio[i] > 0.f))
+    __hip_atomic_store(w.owner + id, claim, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // The batched tree write of one workgroup (any block size >= 64 and >= B): the actor rows'
 // leaves, the learner priority mix + loss mean, deduplicated learner leaves, the running max
 // and counters; with ``small_levels_in_block`` every level of the dirty paths too.  ``red``:
@@ -350,6 +362,7 @@ __device__ __forceinline__ void batch_leaves_block(const TreeDesc& t, const Batc
     sids[i] = id;
     w.list[i] = id;
     if (id >= 0 && id < t.size[0]) pmax = fmaxf(pmax, write_leaf(t, id, w.pre_prio[i], w.alpha));
+    if (w.B > 0) claim_voided(t, w, i, kVoidedClaim);
   }
   float p = 0.f;
   if (w.B > 0) {
@@ -377,6 +390,10 @@ __device__ __forceinline__ void batch_leaves_block(const TreeDesc& t, const Batc
     const float wp = write_leaf(t, id, p, w.alpha);
     if (w.mix.delta != nullptr || w.prio != nullptr) pmax = fmaxf(pmax, wp);
     w.owner[id] = -1;  // release the claim (only the winner writes; losers never touch it again)
+  }
+  if (w.B > 0 && w.E > 0) {  // block-uniform
+    __syncthreads();
+    for (int i = k; i < w.E; i += blockDim.x) claim_voided(t, w, i, -1);
   }
   pmax = block_reduce_1024(pmax, red, true);
   if (k == 0 && pmax > 0.f) atomic_max_pos_float(w.max_prio, pmax);
@@ -445,6 +462,7 @@ __device__ __forceinline__ void ride_leaves(const TreeDesc& t, const BatchWrite&
     const int id = w.pre_idx[i];
     w.list[i] = id;
     if (id >= 0 && id < t.size[0]) pmax = fmaxf(pmax, write_leaf(t, id, w.pre_prio[i], w.alpha));
+    if (w.B > 0) claim_voided(t, w, i, kVoidedClaim);
   }
   float dmax = 0.f;
   if (w.mix.delta && w.B > 0) {
@@ -469,6 +487,10 @@ __device__ __forceinline__ void ride_leaves(const TreeDesc& t, const BatchWrite&
       if (w.mix.delta != nullptr || w.prio != nullptr) pmax = fmaxf(pmax, wp);
       w.owner[id] = -1;  // release the claim (only the winner writes; losers never touch it again)
     }
+  }
+  if (w.B > 0 && w.E > 0) {  // block-uniform
+    __syncthreads();
+    for (int i = k; i < w.E; i += nt) claim_voided(t, w, i, -1);
   }
   pmax = block_reduce_1024(pmax, red, true);
   if (k == 0) {

@@ -19,11 +19,23 @@ Reference cadences and tags are kept: target sync every ``--target_update_interv
 (learner.py:163-165), weights published every ``--publish_param_interval``
 (learner.py:169-170), ``model.pth`` written every ``--save_interval`` (learner.py:166-168)
 plus a ``model.pth.train.pt`` sidecar (optimizer moments, step counters, target net)
-for a true resume (``--resume``), ``learner/loss``, ``learner/grad_norm``,
+for a weights-and-optimizer resume (``--resume``: the replay is filled afresh), ``learner/loss``, ``learner/grad_norm``,
 ``learner/BPS`` every ``--bps_interval`` (learner.py:151-175), ``actor/episode_reward``
 and ``actor/episode_length`` (actor.py:91-92), plus ``learner/steps_per_sec``,
 ``actor/frames_per_sec`` and ``replay/size``.  The envs are the GPU
 synthetic Atari-shaped envs of ``ActorShard`` (no emulator in this image).
+
+Full-state checkpoints (single GPU): ``--state-dir D`` writes the whole engine -- the replay with
+its frame ring and priority tree, the env states, the n-step windows, the learner and every
+counter -- as the directory ``D`` at the end of the run and every ``--save-state-interval``
+learner steps (``utils/engine_state.py``: live rows only, streamed, atomic with a ``D.prev``
+fallback, digests verified on the GPU).  ``--resume-state D`` restores every one of those tensors
+exactly, and with the default learner (``--forward hip --dtype fp32``, one actor step per learner
+step: the tree write that rides the backward launches) the resumed run computes what the
+uninterrupted run would have, bit for bit.  Configurations whose tree write runs as separate
+launches on the forked tree stream (``--dtype bf16``, ``--actor-steps`` > 1) are restored as exactly
+but are not reproducible run to run once the slot ring has wrapped (profiles/engine_state.md), so
+neither is their continuation.  ``model.pth`` and its sidecar are written as before.
 """
 from __future__ import annotations
 
@@ -44,6 +56,7 @@ def parser():
     p.add_argument("--actor-steps", type=int, default=1, help="actor steps per learner step")
     p.add_argument("--save-path", default="model.pth")
     p.add_argument("--resume", default=None, help="model.pth (+ .train.pt sidecar) to resume from")
+    add_state_flags(p)
     p.add_argument("--log-dir", default=None, help="event-file directory (default runs/<time>-<env>-learner)")
     p.add_argument("--no-tb", action="store_true")
     p.add_argument("--same-device", action="store_true", help="all ranks on cuda:0 (1-GPU rehearsal with gloo)")
@@ -61,6 +74,41 @@ def parser():
                         "beside training, a chunk that would queue behind a running one is skipped (the "
                         "one-launch modes need --forward hip --dtype fp32)")
     return p
+
+
+def add_state_flags(p) -> None:
+    """The full-state checkpoint flags shared by the engine CLIs."""
+    p.add_argument("--state-dir", default=None,
+                   help="write full-state checkpoints (replay, env states, learner, counters) to this directory")
+    p.add_argument("--save-state-interval", type=int, default=0,
+                   help="learner steps between full-state checkpoints (0 = only at the end, when --state-dir is given)")
+    p.add_argument("--resume-state", default=None,
+                   help="full-state checkpoint directory to continue from (excludes --resume)")
+
+
+def check_state_flags(args, world: int = 1) -> None:
+    if args.resume_state and args.resume:
+        raise SystemExit("--resume-state restores everything --resume does: give one of them")
+    if args.save_state_interval < 0:
+        raise SystemExit("--save-state-interval must be >= 0")
+    if args.save_state_interval and not args.state_dir:
+        raise SystemExit("--save-state-interval needs --state-dir")
+    if world > 1 and (args.state_dir or args.resume_state):
+        raise SystemExit("--state-dir / --resume-state checkpoint the single-GPU engine: not available under "
+                         "torch.distributed with more than one rank")
+
+
+def resume_state(eng, path: str) -> int:
+    """``eng.load_state(path)`` for a CLI: a checkpoint that does not fit or is damaged ends the
+    run with its message (the engine's state is undefined then).  Returns the learner step."""
+    from .utils.engine_state import CheckpointError
+
+    try:
+        eng.load_state(path)
+    except CheckpointError as e:
+        raise SystemExit(f"--resume-state {path}: {e}")
+    print(f"resumed full state from {path} at step {eng.learn_steps}", flush=True)
+    return eng.learn_steps
 
 
 # ------------------------------------------------------------------ checkpoint
@@ -124,6 +172,7 @@ def main(argv=None) -> int:
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = 0 if args.same_device else int(os.environ.get("LOCAL_RANK", "0"))
+    check_state_flags(args, world)
     from .utils import trace
 
     if cfg.kernel.hip_debug:  # before the HIP runtime starts
@@ -222,6 +271,8 @@ def main(argv=None) -> int:
     eng.fill()
     if cfg.kernel.use_graphs:
         eng.capture()
+    if args.resume_state:  # everything fill() and capture() wrote is overwritten in place
+        start = resume_state(eng, args.resume_state)
     torch.cuda.synchronize(device)
     if rank == 0:
         print(f"replay warm ({time.perf_counter() - t_fill:.1f}s); training from step {start}", flush=True)
@@ -304,6 +355,7 @@ def main(argv=None) -> int:
     step = eng.learn_steps  # capture's warm-up steps are real training steps
     t_last, step_last = time.perf_counter(), step
     eval_rets, eval_lens = [], []
+    state_saved_at = None
     while not max_step or step < max_step:
         if eng.train_step() is False:  # central actor rank: the learner stopped this link
             break
@@ -365,6 +417,9 @@ def main(argv=None) -> int:
         if L.save_interval and step % L.save_interval == 0 and rank == 0 and learner is not None:
             print("Saving Model..", flush=True)
             save_engine(learner, args.save_path, {"learn_steps": step, "actor_steps": eng.actor_steps})
+        if args.state_dir and args.save_state_interval and step % args.save_state_interval == 0:
+            eng.save_state(args.state_dir)
+            state_saved_at = step
     if async_eval is not None:  # the last evaluation is logged
         line = {}
         res = async_eval.wait()
@@ -377,6 +432,8 @@ def main(argv=None) -> int:
     torch.cuda.synchronize(device)
     if rank == 0 and learner is not None:
         save_engine(learner, args.save_path, {"learn_steps": step, "actor_steps": eng.actor_steps})
+    if args.state_dir and state_saved_at != step:  # (a second save of the same step would only cost the .prev)
+        eng.save_state(args.state_dir)
     if writer is not None:
         writer.close()
     if topology == "central":  # async links: bounded stop handshake instead of a barrier

@@ -18,7 +18,9 @@ Reference cadences and artefacts kept:
   ``.train.pt`` sidecar (Adam moments, step counter, target net, iteration counters):
   ``--resume IT`` restores the optimizer state and counters, not weights only; the replay,
   the env states and the acting RNG counters are not saved, so training continues on a
-  freshly filled replay (it does not replay the uninterrupted run bit for bit);
+  freshly filled replay (it does not replay the uninterrupted run bit for bit -- the
+  full-state checkpoints of ``apex_amd.train`` / ``apex_amd.train_host``, ``utils/engine_state.py``,
+  do not cover the AQL engines yet: ``AQLReplay`` would only have to list its tensors);
 * tags ``learner/loss_q`` / ``learner/loss_proposal`` (means over the logging window, at
   the learner-step index; AQL_dis.py:123-124) and ``actor/episode_reward`` /
   ``actor/episode_length`` (batchrecoder_AQL.py:118-119), plus ``evaluator/episode_reward``

@@ -17,10 +17,18 @@ Flags: the reference's (``--env``, ``--episode_life``, ``--clip_rewards``, ``--r
 ``--threshold_size``, ``--batch_size``, intervals, ...) plus ``--envs``, ``--learner-steps`` (learner
 steps enqueued per env step), ``--workers``, ``--worker-timeout`` (seconds a worker may stay silent),
 ``--ingest {auto,whole,banked}``, ``--max-step`` (learner steps, 0 = forever), ``--save-path``,
-``--resume`` (model + ``.train.pt`` sidecar, as ``apex_amd.train``) and ``--log-dir``.  Logged every
+``--resume`` (model + ``.train.pt`` sidecar, as ``apex_amd.train``: the replay is filled afresh),
+``--state-dir`` / ``--save-state-interval`` / ``--resume-state`` (below) and ``--log-dir``.  Logged every
 ``--bps_interval`` learner steps: ``learner/loss``, ``learner/grad_norm``, ``learner/BPS``,
 ``actor/episode_reward`` (clipped return), ``actor/episode_length``, ``actor/episode_score``
 (unclipped game score), ``actor/frames_per_sec`` and ``replay/size``.
+
+``--state-dir D`` writes a full-state checkpoint -- the replay with its frame ring and priority tree,
+the learner, the acting weights and the counters -- as the directory ``D`` at the end of the run and
+every ``--save-state-interval`` learner steps (``utils/engine_state.py``).  ``--resume-state D`` is a
+replay-preserving resume: it restores all of that and starts the emulators afresh (host emulators
+cannot be restored, and the at most n * E transitions inside the n-step windows open at save time
+are lost), so training continues on the saved replay instead of refilling it.
 
 ``--eval-envs N`` (default 0 = off) adds the reference's evaluator (``eval.py``): ``N`` further
 emulators played greedily (epsilon 0, rewards unclipped, episodes capped at ``--max_episode_length``
@@ -35,6 +43,7 @@ finished since the last log line: ``evaluator/episode_reward`` (game score), ``e
 """
 from __future__ import annotations
 
+import os
 import sys
 import time
 
@@ -61,6 +70,9 @@ def parser():
                    help="fused: one-launch act (host_eval_act); step: the stepwise forward")
     p.add_argument("--save-path", default="model.pth")
     p.add_argument("--resume", default=None, help="model.pth (+ .train.pt sidecar) to resume from")
+    from .train import add_state_flags
+
+    add_state_flags(p)
     p.add_argument("--log-dir", default=None, help="event-file directory (default runs/<time>-<env>-host)")
     p.add_argument("--no-tb", action="store_true")
     return p
@@ -77,6 +89,9 @@ def main(argv=None) -> int:
     if args.eval_envs and (args.eval_interval < 1 or args.eval_steps < 1 or
                            not 1 <= args.eval_workers <= args.eval_envs):
         raise SystemExit("--eval-interval / --eval-steps must be >= 1 and --eval-workers in [1, --eval-envs]")
+    from .train import check_state_flags
+
+    check_state_flags(args, int(os.environ.get("WORLD_SIZE", "1")))
     cfg = args_to_config(args)
     if not torch.cuda.is_available():
         raise SystemExit("apex_amd.train_host runs the GPU engine; use apex_amd.roles.* on CPU")
@@ -164,7 +179,7 @@ def _make_evaluation(args, cfg, spec, eng, device):
 def _loop(args, cfg, eng, device, evaluation=None) -> int:
     import torch
 
-    from .train import load_engine, save_engine
+    from .train import load_engine, resume_state, save_engine
 
     L, vec = cfg.learner, eng.vec
     counters = {}
@@ -173,6 +188,8 @@ def _loop(args, cfg, eng, device, evaluation=None) -> int:
         eng.publish_params()
     start = int(counters.get("learn_steps", 0))
     eng.learn_steps = start
+    if args.resume_state:
+        start = resume_state(eng, args.resume_state)
     where = f" in {args.workers} worker processes ({eng.ingest} ingest)" if args.workers else ""
     print(f"{cfg.env.env}: {len(vec)} host envs{where}, {vec.n_actions} actions, raw {vec.raw_shape}; "
           f"training from step {start}", flush=True)
@@ -184,13 +201,15 @@ def _loop(args, cfg, eng, device, evaluation=None) -> int:
         writer = SummaryWriter(args.log_dir, comment=f"-{cfg.env.env}-host")
     max_step = int(L.max_step)
     bps_every = max(1, L.bps_interval)
-    t_last, step_last, act_last, next_log = time.perf_counter(), start, 0, start + bps_every
+    t_last, step_last, act_last, next_log = time.perf_counter(), start, eng.actor_steps, start + bps_every
+    next_state = (start // args.save_state_interval + 1) * args.save_state_interval if args.save_state_interval else None
     next_save = (start // L.save_interval + 1) * L.save_interval if L.save_interval else None
     next_refresh = start + args.eval_interval
     ev_core = getattr(evaluation, "ev", evaluation)   # the HostEvaluator (its ledger holds the totals)
     if evaluation is not None:
         print(f"evaluator: {args.eval_envs} greedy host envs, {args.eval_mode} mode, {args.eval_kernel} act kernel",
               flush=True)
+    state_saved_at = None
     while not max_step or eng.learn_steps < max_step:
         eng.iteration()
         step = eng.learn_steps
@@ -233,8 +252,14 @@ def _loop(args, cfg, eng, device, evaluation=None) -> int:
             next_save = (step // L.save_interval + 1) * L.save_interval
             print("Saving Model..", flush=True)
             save_engine(eng.learner, args.save_path, {"learn_steps": step, "actor_steps": eng.actor_steps})
+        if next_state is not None and step >= next_state:
+            next_state = (step // args.save_state_interval + 1) * args.save_state_interval
+            eng.save_state(args.state_dir)
+            state_saved_at = step
     torch.cuda.synchronize(device)
     save_engine(eng.learner, args.save_path, {"learn_steps": eng.learn_steps, "actor_steps": eng.actor_steps})
+    if args.state_dir and state_saved_at != eng.learn_steps:
+        eng.save_state(args.state_dir)
     if writer is not None:
         writer.close()
     return 0
