@@ -27,10 +27,13 @@ lag, as ``AQLEngineConfig.overlap`` has on the device envs).
 One staging block is enough: the host writes it again only after it has waited for the event
 recorded after the NEXT acting forward, which the same stream runs after the copy that read it.
 
-Greedy evaluation is the host one (``train_aql.greedy_eval`` on a separate env of the same id);
-``rollout_evaluate`` and :class:`~apex_amd.engine.aql.AQLEvaluator` play device envs and are
-refused.  Out of scope: emulator worker processes, the central (``--gpus N``) topology over host
-envs, double-banked env groups.
+Greedy evaluation: :meth:`AQLHostEngine.evaluate` is the blocking host one
+(``train_aql.greedy_eval`` on a separate env of the same id);
+:class:`~apex_amd.engine.aql_host_eval.AQLHostEvaluator` plays evaluator envs of its own in worker
+processes beside training (``train_aql --eval-envs``: a side stream, two weight sets, a pump that
+never waits).  ``rollout_evaluate`` and :class:`~apex_amd.engine.aql.AQLEvaluator` play device
+envs and are refused.  Out of scope: worker processes for the TRAINING envs, the central
+(``--gpus N``) topology over host envs, double-banked env groups.
 """
 from __future__ import annotations
 

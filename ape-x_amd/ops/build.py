@@ -47,6 +47,7 @@ HIP_SOURCES = [
     "aql_rollout_kernels.hip",
     "aql_frame_kernels.hip",
     "aql_host_kernels.hip",
+    "aql_host_eval_kernels.hip",
     "atari_rollout_kernels.hip",
     "conv1_kernels.hip",
     "fc_kernels.hip",

@@ -943,6 +943,26 @@ PYBIND11_MODULE(_apex_hip, m) {
     return r;
   });
   m.def("aql_rollout", [](const AqlRollout& r, uint64_t s) { aql_rollout(r, S(s)); });
+  // the act half of one host-env AQL evaluator step in one launch (aql_host_eval_kernels.hip)
+  py::class_<AqlHostEvalAct>(m, "AqlHostEvalAct");
+  // d: N, prop_seed, sel_seed, stage, low, high, var, env_act, act_idx, counter [+ amu, q] (a missing pointer is
+  // null: the launcher throws); the step k is the launch's argument
+  m.def("make_aql_host_eval_act", [](const AQLNet& net, py::dict d) {
+    auto opt = [&](const char* k) { return d.contains(k) ? d[k].cast<uint64_t>() : (uint64_t)0; };
+    AqlHostEvalAct r{};
+    r.net = net;
+    r.N = d["N"].cast<int>();
+    r.prop_seed = d["prop_seed"].cast<uint64_t>(); r.sel_seed = d["sel_seed"].cast<uint64_t>();
+    r.stage = P<const float>(opt("stage"));
+    r.low = P<const float>(opt("low")); r.high = P<const float>(opt("high")); r.var = P<const float>(opt("var"));
+    r.env_act = P<float>(opt("env_act")); r.act_idx = P<int>(opt("act_idx")); r.counter = P<int64_t>(opt("counter"));
+    r.amu = P<float>(opt("amu")); r.q = P<float>(opt("q"));
+    return r;
+  });
+  m.def("aql_host_eval_act", [](AqlHostEvalAct r, int64_t k, uint64_t s) {
+    r.k = k;
+    aql_host_eval_act(r, S(s));
+  }, py::arg("r"), py::arg("k"), py::arg("s"));
   // n_steps greedy steps of every Atari evaluator env in one launch (atari_rollout_kernels.hip)
   py::class_<AtariRollout>(m, "AtariRollout");
   // d: w1, b1, w2p, b2, w3p, b3, wfc1p, ba1, bv1, wa2, ba2, wv2, bv2, n_steps, env_seed, act_seed, eps, counter,

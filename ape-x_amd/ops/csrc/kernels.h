@@ -824,6 +824,27 @@ struct AqlRollout {
   int trace_T;
 };
 void aql_rollout(const AqlRollout& r, hipStream_t s);
+// The act half of one greedy evaluator step over HOST envs in one launch
+// (aql_host_eval_kernels.hip; one 512-thread workgroup per evaluator env, N <= 64): the loop body
+// of aql_rollout without the env.  Env b's observation is row b of the `reset_obs` rows of
+// `stage`, the device copy of the vector env's staging block (AqlHostTail::stage's layout over N
+// envs); the step is aql_propose -> aql_candidate_q -> aql_select (eps 0) at step counter k with
+// the same Philox keys and arithmetic.  counter[0] = k + 1 is stored (what the stepwise form's
+// counter add leaves).  The trace (both pointers or none) receives the candidate sets and Q rows.
+struct AqlHostEvalAct {
+  AQLNet net;
+  int N;               // evaluator envs
+  int64_t k;           // the evaluator step (the Philox counter), by value
+  uint64_t prop_seed, sel_seed;            // aql_propose's and aql_select's seeds
+  const float* stage;  // next_obs [N][obs] | reset_obs [N][obs] | reward [N] | done [N] | ended [N]
+  const float *low, *high, *var;           // action bounds / proposal variance [adim] (continuous)
+  float* env_act;      // [N][adim] the chosen candidate's action
+  int* act_idx;        // [N] the chosen candidate
+  int64_t* counter;    // [1]
+  float* amu;          // optional [N][T][adim]
+  float* q;            // optional [N][T]
+};
+void aql_host_eval_act(const AqlHostEvalAct& r, hipStream_t s);
 // One env's whole acting frame of the single-process AQL trainer (AQL.py) in one launch
 // (aql_frame_kernels.hip, one 512-thread workgroup): proposal -> candidate set -> critic with the
 // online net in train mode -> this frame's epsilon -> epsilon-greedy selection -> env step ->

@@ -43,7 +43,14 @@ them once per ``--log-interval`` iterations.
 checkpoints, tags and cadences (``apex_amd.engine.aql_host``): any id with flat observations,
 not only the three GPU envs.  The K learner steps of an iteration are queued before the host steps
 the envs (``--host-serial``: after); ``actor/env_steps_per_sec`` counts host env steps.  Single
-GPU, host evaluator.
+GPU.  The evaluator is the host one (``--eval-mode host``, the default: ``greedy_eval`` while the
+loop waits) or, with ``--eval-envs N`` (``--eval-workers W``, ``--eval-kernel fused|step``), N
+greedy evaluator envs in W worker processes beside training (``apex_amd.engine.aql_host_eval``):
+their weights are refreshed every ``--eval-interval`` iterations, the evaluator is pumped once per
+iteration without ever blocking, and each log line carries the episodes finished since the last
+one (``evaluator/episode_reward`` / ``evaluator/episode_length``, one scalar per episode at the
+learner step it ended at; record keys ``evaluator_episodes`` / ``evaluator_mean_return`` /
+``evaluator_steps``).  ``greedy_eval`` is then not called.
 
 ``--gpus N`` (N > 1; or any launch with WORLD_SIZE > 1): the distributed form of AQL_dis
 across GPUs (``apex_amd.engine.central_aql``): rank 0 trains and checkpoints, ranks 1..N-1
@@ -86,6 +93,23 @@ class _Parser(argparse.ArgumentParser):
             if a.overlap:
                 self.error("--overlap is the GPU envs' acting stream: --host-envs overlaps the host step with the "
                            "learner by default (--host-serial turns that off)")
+        if a.eval_envs:
+            if not 0 < a.eval_envs <= 64:
+                self.error(f"--eval-envs {a.eval_envs}: the host-env evaluator runs 1..64 envs (0 = off)")
+            if a.gpus > 1:
+                self.error(f"--eval-envs is the single-GPU host-env engine's evaluator: --gpus {a.gpus} has none")
+            if not a.host_envs:
+                self.error("--eval-envs evaluates on host envs beside --host-envs training (the GPU envs have "
+                           "--eval-mode rollout / async)")
+            if a.eval_interval < 1:
+                self.error("--eval-envs refreshes the evaluator's weights every --eval-interval iterations: it must "
+                           "be >= 1")
+            if a.eval_workers is None:
+                a.eval_workers = min(2, a.eval_envs)
+            if not 1 <= a.eval_workers <= a.eval_envs:
+                self.error(f"--eval-workers {a.eval_workers} must be in 1..--eval-envs ({a.eval_envs})")
+        elif a.eval_workers is not None:
+            self.error("--eval-workers is the worker count of --eval-envs")
         if a.n_envs is None:
             a.n_envs = 10 if a.host_envs else 256
         return a
@@ -130,6 +154,14 @@ def parser() -> argparse.ArgumentParser:
                    help="host: a CPU copy of the online net on a host env (greedy_eval); rollout: one aql_rollout "
                         "launch on the GPU; async: that launch on a weight snapshot beside training, reported by "
                         "the next log line (single-GPU engine only)")
+    p.add_argument("--eval-envs", type=int, default=0,
+                   help="--host-envs: this many (at most 64) greedy evaluator envs in worker processes beside "
+                        "training (engine.aql_host_eval); their weights are refreshed every --eval-interval "
+                        "iterations and greedy_eval is not called (0 = off)")
+    p.add_argument("--eval-workers", type=int, default=None,
+                   help="--eval-envs: worker processes, 1..--eval-envs (default min(2, --eval-envs))")
+    p.add_argument("--eval-kernel", default="fused", choices=["fused", "step"],
+                   help="--eval-envs: the evaluator's act, one aql_host_eval_act launch or the three stepwise kernels")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--device", default="cuda:0")
     p.add_argument("--no-graphs", action="store_true")
@@ -269,9 +301,21 @@ def train(a) -> dict:
     eng.fill()
     if not a.no_graphs:
         eng.capture()
+    hev = None
     try:
-        return _loop(a, eng, eng.iteration, eng.E, eng.finished_episodes, start, writer)
+        if a.eval_envs:
+            from .engine.aql_host_eval import AQLHostEvaluation, AQLHostEvaluator, make_pool
+
+            pool = make_pool(a.env, a.eval_envs, a.eval_workers, seed=a.seed, max_episode_length=a.max_episode_length)
+            try:
+                hev = AQLHostEvaluation(AQLHostEvaluator(eng, pool, kernel=a.eval_kernel, seed=a.seed), pool)
+            except BaseException:
+                pool.close()
+                raise
+        return _loop(a, eng, eng.iteration, eng.E, eng.finished_episodes, start, writer, hev=hev)
     finally:
+        if hev is not None:
+            hev.close()
         if a.host_envs:
             eng.close()
 
@@ -329,14 +373,19 @@ def _crossed(lo: int, hi: int, every: int, offset: int = 0) -> bool:
     return (hi + offset) // every * every >= lo + offset
 
 
-def _loop(a, eng: AQLEngine, iterate, envs_per_iter: int, episodes, start: int, writer, central=None) -> dict:
+def _loop(a, eng: AQLEngine, iterate, envs_per_iter: int, episodes, start: int, writer, central=None,
+          hev=None) -> dict:
     """The training loop: ``iterate()`` per iteration (act + K SGD steps + publish + target
     cadence, or its central form), checkpoints, metrics and greedy evaluations.
 
     Central: one ``iterate()`` is a learner SPIN (ingest + the SGD steps the applied rows
     pay for); the iteration count, checkpoint / log / eval cadences and ``max_step`` follow
     the recorded batches that reached the replay (CentralAQLEngine.data_iterations), and the
-    logged step counts / rates read the device SGD counter (one sync per log window)."""
+    logged step counts / rates read the device SGD counter (one sync per log window).
+
+    ``hev`` (``--eval-envs``): an :class:`~apex_amd.engine.aql_host_eval.AQLHostEvaluation`; it is
+    refreshed at the evaluation cadence, pumped once per iteration, and its finished episodes ride
+    in the log lines.  ``greedy_eval`` is then not called."""
     ep_idx, last = 0, {}
     mode = getattr(a, "eval_mode", "host")
     if central is not None and mode != "host":
@@ -357,13 +406,17 @@ def _loop(a, eng: AQLEngine, iterate, envs_per_iter: int, episodes, start: int, 
             else:
                 lo = hi = it
             it = hi + 1
+            if hev is not None:
+                if _crossed(lo, hi, a.eval_interval, 1):
+                    hev.refresh(eng.learner.flat)   # (conflates while the target set is still read)
+                hev.pump(eng.learner_steps)
             if _crossed(lo, hi, a.save_interval) or hi == a.max_step - 1:
                 if central is not None:
                     central.refresh_steps()
                 save_engine(eng, model_path(a.save_dir, hi))
             log_now = _crossed(lo, hi, a.log_interval, 1 - start) or hi == a.max_step - 1
             final = hi == a.max_step - 1
-            ev = a.eval_interval > 0 and (_crossed(lo, hi, a.eval_interval, 1) or final)
+            ev = hev is None and a.eval_interval > 0 and (_crossed(lo, hi, a.eval_interval, 1) or final)
             # async: snapshot + side-stream rollout, no log line and no sync of its own.  A record
             # reports what landed BEFORE this iteration's launch, so its greedy_iteration (the
             # iterations completed when the snapshot was taken) never runs ahead of the record
@@ -402,6 +455,14 @@ def _loop(a, eng: AQLEngine, iterate, envs_per_iter: int, episodes, start: int, 
                 for k, r in enumerate(ret):
                     writer.add_scalar("evaluator/episode_reward", r, eng.learner_steps)
                 last["greedy_mean_return"] = float(np.mean(ret))
+            if hev is not None:
+                done_eps = hev.poll()
+                for r, length, _, at in done_eps:   # one scalar per episode, at its learn_step_at_end
+                    writer.add_scalar("evaluator/episode_reward", r, at)
+                    writer.add_scalar("evaluator/episode_length", length, at)
+                last["evaluator_episodes"] = len(done_eps)
+                last["evaluator_mean_return"] = float(np.mean([e[0] for e in done_eps])) if done_eps else None
+                last["evaluator_steps"] = hev.ev.ledger.steps
             if asyn is not None:
                 # the newest evaluation that has landed (last iteration: wait out the one in flight)
                 if (res := asyn.latest(block=final)) is not None:
