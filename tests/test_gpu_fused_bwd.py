@@ -1,6 +1,9 @@
-"""Fused learner backward pieces vs the separate reference kernels / torch fp32:
-dqn_heads_bwd (loss + heads backward + head-gradient partials), the priority mix in the
-tree write, and grad_finalize (one launch for all batch-sliced reductions)."""
+"""Fused learner backward pieces vs their separate sibling kernels / torch fp32:
+dqn_heads_bwd (loss + heads backward + head-gradient partials) against dqn_loss + heads_bwd +
+heads_wgrad, the priority mix in the tree write, and grad_finalize (one launch for all
+batch-sliced reductions).  The siblings share dqn_heads_bwd's algebra: this file shows that the
+fused launch computes what the three launches did, not that either is right.  The independent
+reference (fp64 autograd, conditioned bounds, ragged shapes) is tests/test_gpu_step_tail_fp64.py."""
 import math
 
 import pytest
