@@ -331,7 +331,10 @@ class CentralApexEngine:
         slots, prio = apply_packets(self.tables, frames, meta, self._fbase.index_select(0, idx),
                                     self._sbase.index_select(0, idx))
         # the fill counter advances by the real transition rows (filler rows, e.g. the
-        # reset-frame packet's, carry frames only -- as the IPC ingest counts them)
+        # reset-frame packet's, carry frames only -- as the IPC ingest counts them).  With one
+        # counter over all regions, slot filled - 1 -- the one exclude_last leaves out -- lies
+        # inside an early region with live rows behind it: the sampler removes its mass at every
+        # level of the descent, not only from the total (tree_sample_leaf)
         self.replay.filled.add_((slots >= 0).sum())
         self.replay.write_priorities(slots, prio, dedup=False)
 

@@ -230,7 +230,10 @@ __device__ __forceinline__ double uniform_double(uint64_t seed, uint64_t stream,
 // One wave draws stratified proportional sample i of B from a fanout-64 sum tree (TreeDesc of
 // kernels.h): mass (u_i + i) * total / B with u_i from Philox (seed, i, counter), descended with
 // a wave-wide inclusive scan of the 64 child sums per level; returns the leaf.  ``length``
-// live slots; ``exclude_last``: the newest slot's leaf is left out of the mass (reference Q5).
+// live slots; ``exclude_last``: the newest slot's leaf is left out of the mass (reference Q5) --
+// out of the total and, at every level, out of the child that holds it, so the descent stays
+// consistent when live leaves lie behind slot length - 1 (the central learner's regions).  Each
+// subtraction is exact in fp64 while the node sums are.
 // Shared by per_sample_k (replay_kernels.hip) and the AQL learner forward, which samples its
 // own row (aql_engine_kernels.hip).
 template <class TD>
@@ -239,8 +242,9 @@ __device__ __forceinline__ int tree_sample_leaf(const TD& t, int i, int B, int l
   // leaf_p: the drawn leaf's stored value (leaf_sum[node]), taken from the last level's
   // children instead of a dependent re-read after the descent
   const int L = t.levels;
-  double total = t.node_sum[L - 1][0];
-  if (exclude_last && length > 0 && length <= t.size[0]) total -= (double)t.leaf_sum[length - 1];
+  const bool excl = exclude_last && length > 0 && length <= t.size[0];
+  const double xv = excl ? (double)t.leaf_sum[length - 1] : 0.0;
+  const double total = t.node_sum[L - 1][0] - xv;
   const double u = uniform_double(seed, (uint64_t)i, ctr);
   double mass = (u + (double)i) * total / (double)B;
   int node = 0;
@@ -257,7 +261,7 @@ __device__ __forceinline__ int tree_sample_leaf(const TD& t, int i, int B, int l
         v = t.node_sum[level - 2][child];
       }
     }
-    if (exclude_last && level == 1 && child == length - 1) v = 0.0;
+    if (excl && child == ((length - 1) >> (6 * (level - 1)))) v = fmax(v - xv, 0.0);
     const double incl = wave_inclusive_scan(v, lane);
     unsigned long long hit = __ballot(incl > mass);
     int k;
