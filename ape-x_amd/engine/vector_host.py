@@ -41,10 +41,13 @@ only after it has waited for the event recorded after the NEXT acting forward, w
 stream runs after the copy that read the block.  The host reads the action buffer inside
 ``vec.step`` and enqueues the next action copy only after that call has returned.
 
-Greedy evaluation is the host one (:meth:`VectorHostEngine.evaluate`: a CPU copy of the online net
-on a separate env); ``rollout_evaluate`` and :class:`~apex_amd.engine.vector.VectorEvaluator` play
-device envs and are refused.  Out of scope: env worker processes, wider nets than
-``kVecMaxObs`` / ``kVecMaxA``, the central topology, an evaluator beside training.
+Greedy evaluation is the host one: :meth:`VectorHostEngine.evaluate` (blocking: a CPU copy of the
+online net on a separate env), or beside training :mod:`apex_amd.engine.vector_host_eval`
+(evaluator envs in worker processes, ``vec_host_eval_act`` on a side stream, two weight sets, a
+pump that never waits; ``train_vector --host-envs --eval-envs N``).  ``rollout_evaluate`` and
+:class:`~apex_amd.engine.vector.VectorEvaluator` play device envs and are refused.  Out of scope:
+worker processes for the TRAINING envs, wider nets than ``kVecMaxObs`` / ``kVecMaxA``, the central
+topology.
 """
 from __future__ import annotations
 

@@ -1150,6 +1150,24 @@ PYBIND11_MODULE(_apex_hip, m) {
                   P<const int64_t>(counter), P<float>(q), P<int>(actions)};
   });
   m.def("vec_act", [](const VecAct& a, uint64_t s) { vec_act(a, S(s)); });
+  // the act half of one host-env vector evaluator step in one launch (vector_kernels.hip)
+  py::class_<VecHostEvalAct>(m, "VecHostEvalAct");
+  // d: N, seed, stage, q, actions (a missing pointer is null: the launcher throws); the step k is the launch's
+  // argument
+  m.def("make_vec_host_eval_act", [](const VecNet& net, py::dict d) {
+    auto opt = [&](const char* k) { return d.contains(k) ? d[k].cast<uint64_t>() : (uint64_t)0; };
+    VecHostEvalAct a{};
+    a.net = net;
+    a.N = d["N"].cast<int>();
+    a.seed = d["seed"].cast<uint64_t>();
+    a.stage = P<const float>(opt("stage"));
+    a.q = P<float>(opt("q")); a.actions = P<int>(opt("actions"));
+    return a;
+  });
+  m.def("vec_host_eval_act", [](VecHostEvalAct a, int64_t k, uint64_t s) {
+    a.k = k;
+    vec_host_eval_act(a, S(s));
+  }, py::arg("a"), py::arg("k"), py::arg("s"));
   py::class_<DqnFrame>(m, "DqnFrame");
   // d: act_seed, hist, t, eps_start, eps_final, eps_decay, beta0, beta_horizon, eps_out, beta_out, q, actions,
   //    reward, done, new_frame, [ep_log], C, filled, slot, max_prio, alpha; tt: the replay tables

@@ -946,6 +946,21 @@ struct VecAct {
   int* actions;            // [E]
 };
 void vec_act(const VecAct& a, hipStream_t s);
+// The act half of one greedy evaluator step over HOST envs in one launch (vector_kernels.hip
+// vec_host_eval_act_k; vec_act's geometry, N <= 64): env e's observation is row e of the
+// `reset_obs` rows of `stage`, the device copy of the vector env's staging block
+// (VecHostTail::stage's layout over N envs); Q is vec_act's forward and the action its draw at
+// epsilon 0 with the Philox key (seed, e, k).  No ring, no hist, no counter in memory.
+struct VecHostEvalAct {
+  VecNet net;
+  int N;               // evaluator envs
+  int64_t k;           // the evaluator step (the Philox counter), by value
+  uint64_t seed;       // Philox seed of the draw
+  const float* stage;  // next_obs [N][obs] | reset_obs [N][obs] | reward [N] | done [N] | ended [N]
+  float* q;            // [N][A]
+  int* actions;        // [N]
+};
+void vec_host_eval_act(const VecHostEvalAct& a, hipStream_t s);
 // N greedy episodes from reset to their first done in one launch (one workgroup per 8 episodes,
 // the heads staged once): episode e starts at the reset draw of vec_classic_reset at step
 // counter 0 and takes the first argmax of Q each step (vec_forward's and vec_classic_step's

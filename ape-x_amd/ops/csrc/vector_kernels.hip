@@ -13,6 +13,8 @@
 //                                         envs/classic.py in fp32)
 //   vec_act      one workgroup per 8 envs: both heads' 128x128 weights staged (transposed) in LDS,
 //                Q[E, A], then select_actions_k's draw in the same launch
+//   vec_host_eval_act  vec_act for the host-env evaluator: the observations straight from the staging
+//                block's reset_obs rows, the step by value, epsilon 0 (engine/vector_host_eval.py)
 //   dqn_frame    one workgroup, <= 8 envs: the actor side of one DQN.py frame (eps(t) / beta(t), vec_act's
 //                forward and draw on the online net, the env step, the FrameStack advance, the replay
 //                insert at the running max priority and its tree walk) in one launch (engine/dqn.py)
@@ -291,6 +293,45 @@ __global__ __launch_bounds__(kThreads) void vec_act_k(VecAct a) {
     float u[4];
     uniform4(a.seed, (uint64_t)e, a.counter ? (uint64_t)a.counter[0] : 0ull, u);
     if (!(u[0] > a.eps[e])) {
+      const int r = (int)(u[1] * (float)A);
+      best = r < A ? r : A - 1;
+    }
+    a.actions[e] = best;
+  }
+}
+
+// ------------------------------------------------------------------ greedy act over host envs
+// The act half of one evaluator step over HOST envs (engine/vector_host_eval.py): vec_act_k with
+// the observation read straight from the staging block's reset_obs rows and the step k by value --
+// no ring, no hist, no counter in memory.  The observation load is issued before stage_heads and
+// lands in L.x behind it: it is in flight under the head staging.  Same forward, same draw at
+// epsilon 0 (explore iff !(u0 > 0)): Q and the actions are vec_act_k's bit for bit.
+__global__ __launch_bounds__(kThreads) void vec_host_eval_act_k(VecHostEvalAct a) {
+  __shared__ FwdLds L;
+  const int t = threadIdx.x;
+  const int e0 = blockIdx.x * kRows;
+  float x = 0.f;
+  if (t < kRows * kVecMaxObs) {
+    const int r = t / kVecMaxObs, k = t % kVecMaxObs;
+    const int e = min(e0 + r, a.N - 1);  // rows past N repeat the last env (never written)
+    if (k < a.net.obs) x = a.stage[(size_t)(a.N + e) * a.net.obs + k];
+  }
+  stage_heads(a.net, L.W);
+  if (t < kRows * kVecMaxObs) L.x[t] = x;
+  vec_forward(a.net, L);
+  const int e = e0 + t;
+  if (t < kRows && e < a.N) {
+    const int A = a.net.A;
+    const float* row = L.q + t * 8;
+    // vec_act_k's draw at eps = 0: first argmax; explore iff !(u0 > 0); min(int(u1 A), A - 1)
+    int best = 0;
+    float bv = row[0];
+    for (int k = 1; k < A; ++k)
+      if (row[k] > bv) { bv = row[k]; best = k; }
+    for (int k = 0; k < A; ++k) a.q[(size_t)e * A + k] = row[k];
+    float u[4];
+    uniform4(a.seed, (uint64_t)e, (uint64_t)a.k, u);
+    if (!(u[0] > 0.f)) {
       const int r = (int)(u[1] * (float)A);
       best = r < A ? r : A - 1;
     }
@@ -707,6 +748,16 @@ void vec_act(const VecAct& a, hipStream_t s) {
   if (a.E < 1 || !a.ring || !a.hist || !a.eps || !a.q || !a.actions)
     throw std::invalid_argument("vec_act: E >= 1 with ring, hist, eps, q and actions");
   vec_act_k<<<(a.E + kRows - 1) / kRows, kThreads, 0, s>>>(a);
+  LAUNCH_CHECK();
+}
+
+void vec_host_eval_act(const VecHostEvalAct& a, hipStream_t s) {
+  check_net(a.net, "vec_host_eval_act");
+  if (a.N < 1 || a.N > 64) throw std::invalid_argument("vec_host_eval_act: 1 <= N <= 64 evaluator envs");
+  if (a.k < 0) throw std::invalid_argument("vec_host_eval_act: step k >= 0");
+  if (!a.stage) throw std::invalid_argument("vec_host_eval_act: the staging block's device copy");
+  if (!a.q || !a.actions) throw std::invalid_argument("vec_host_eval_act: q and actions");
+  vec_host_eval_act_k<<<(a.N + kRows - 1) / kRows, kThreads, 0, s>>>(a);
   LAUNCH_CHECK();
 }
 

@@ -23,7 +23,14 @@ stream at a log line, and reports a finished evaluation in the next record as
 with a flat observation (<= 8 floats) and a discrete action space (<= 7 actions), one *step* of
 the loop is one step of all E host envs + ``--learner-steps`` SGD steps, overlapped unless
 ``--host-serial``, and ``--eval-mode`` must be ``step`` (the host evaluator).  Same log tags,
-checkpoints and JSON log.
+checkpoints and JSON log.  ``step`` mode there is the blocking ``VectorHostEngine.evaluate`` (a
+device synchronize, then whole episodes on a CPU copy of the net inside the training loop).
+``--eval-envs N`` (with ``--eval-workers W``, ``--eval-kernel``) evaluates beside training instead:
+N (at most 64) greedy evaluator envs in W worker processes (:mod:`apex_amd.engine.vector_host_eval`),
+their weights refreshed whenever ``learn_steps`` crosses a multiple of ``--eval-interval``, the
+evaluator pumped once per iteration.  ``evaluate`` is then not called and no ``greedy_mean_return``
+is written; each record carries ``evaluator_episodes`` (episodes finished since the last record),
+``evaluator_mean_return`` (their mean, None without one) and ``evaluator_steps`` instead.
 """
 from __future__ import annotations
 
@@ -50,12 +57,27 @@ class _Parser(argparse.ArgumentParser):
                 self.error("--host-envs evaluates on the host: --eval-mode must be 'step'")
             if a.learner_steps < 1:
                 self.error("--learner-steps must be >= 1")
+            if a.eval_envs:
+                if not 0 < a.eval_envs <= 64:
+                    self.error(f"--eval-envs {a.eval_envs}: the host-env evaluator runs 1..64 envs (0 = off)")
+                if a.eval_interval < 1:
+                    self.error("--eval-envs refreshes the evaluator's weights every --eval-interval learner steps: "
+                               "it must be >= 1")
+                if a.eval_workers is None:
+                    a.eval_workers = min(2, a.eval_envs)
+                if not 1 <= a.eval_workers <= a.eval_envs:
+                    self.error(f"--eval-workers {a.eval_workers} must be in 1..--eval-envs ({a.eval_envs})")
+            elif a.eval_workers is not None:
+                self.error("--eval-workers is the worker count of --eval-envs")
         else:
             if a.env not in VECTOR_ENVS:
                 self.error(f"argument --env: invalid choice: {a.env!r} (choose from "
                            f"{', '.join(map(repr, sorted(VECTOR_ENVS)))}; any envs.make id with --host-envs)")
             if a.learner_steps != 1 or a.host_serial:
                 self.error("--learner-steps and --host-serial belong to --host-envs")
+            if a.eval_envs or a.eval_workers is not None:
+                self.error("--eval-envs and --eval-workers evaluate on host envs beside --host-envs training (the "
+                           "GPU envs have --eval-mode rollout / async)")
         return a
 
 
@@ -91,6 +113,14 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--eval-mode", default="step", choices=EVAL_MODES,
                    help="step: the stepwise evaluator; rollout: one vec_rollout launch; async: the rollout on a "
                         "weight snapshot beside training, reported by the next log line")
+    p.add_argument("--eval-envs", type=int, default=0,
+                   help="(--host-envs) this many (at most 64) greedy evaluator envs in worker processes beside "
+                        "training (engine.vector_host_eval); their weights are refreshed every --eval-interval "
+                        "learner steps and the blocking evaluate is not called (0 = off)")
+    p.add_argument("--eval-workers", type=int, default=None,
+                   help="(--eval-envs) worker processes, 1..--eval-envs (default min(2, --eval-envs))")
+    p.add_argument("--eval-kernel", default="fused", choices=["fused", "step"],
+                   help="(--eval-envs) the evaluator's act: one vec_host_eval_act launch or the stepwise kernels")
     p.add_argument("--json-log", default=None, help="append one JSON record per log interval to this file")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--device", default="cuda:0")
@@ -124,16 +154,46 @@ def make_engine(a, cfg: VectorEngineConfig):
     return VectorHostEngine(cfg, vec, a.device, learner_steps=a.learner_steps, host_overlap=not a.host_serial)
 
 
+def make_host_evaluation(a, eng):
+    """``--eval-envs``: the worker pool and the non-blocking evaluator over it."""
+    from .engine.vector_host_eval import VectorHostEvaluation, VectorHostEvaluator, make_pool
+
+    pool = make_pool(a.env, a.eval_envs, a.eval_workers, seed=a.seed, max_episode_length=a.max_episode_length)
+    try:
+        return VectorHostEvaluation(VectorHostEvaluator(eng, pool, kernel=a.eval_kernel, seed=a.seed), pool)
+    except BaseException:
+        pool.close()
+        raise
+
+
 def train(a) -> dict:
     cfg = config_from_args(a)
     if not torch.cuda.is_available():
         raise RuntimeError("train_vector needs a GPU (the host-side trainer is apex_amd.trainers.apex_single)")
     eng = make_engine(a, cfg)
-    eng.fill()
+    hev = None
+    try:
+        eng.fill()
+        asyn = VectorEvaluator(eng, a.eval_episodes) if a.eval_mode == "async" and a.eval_interval > 0 else None
+        if not a.no_graphs:
+            eng.capture()
+        if a.host_envs and a.eval_envs:
+            hev = make_host_evaluation(a, eng)
+        return _loop(a, cfg, eng, asyn, hev)
+    finally:
+        if hev is not None:
+            hev.close()
+        if a.host_envs:
+            eng.close()
+
+
+def _loop(a, cfg: VectorEngineConfig, eng, asyn=None, hev=None) -> dict:
+    """The training loop after fill and capture.  ``asyn`` (``--eval-mode async``): the
+    :class:`VectorEvaluator`.  ``hev`` (``--eval-envs``): a
+    :class:`~apex_amd.engine.vector_host_eval.VectorHostEvaluation`; it is refreshed at the
+    evaluation cadence, pumped once per iteration, and its finished episodes ride in the log
+    records.  The blocking ``evaluate`` is then not called."""
     mode = a.eval_mode
-    asyn = VectorEvaluator(eng, a.eval_episodes) if mode == "async" and a.eval_interval > 0 else None
-    if not a.no_graphs:
-        eng.capture()
     jl = open(a.json_log, "a") if a.json_log else None
     last = {}
     t_win, s_win, a_win = time.perf_counter(), eng.learn_steps, eng.actor_steps
@@ -144,9 +204,13 @@ def train(a) -> dict:
             eng.train_step()
             t = eng.learn_steps   # (prev + 1; prev + --learner-steps on host envs)
             final = t >= a.max_step
+            if hev is not None:
+                if _crossed(t, prev, a.eval_interval):
+                    hev.refresh()   # (conflates while the target set is still read)
+                hev.pump(t)
             if _crossed(t, prev, a.save_interval) or final:
                 eng.save(model_path(a.save_dir, t))
-            ev = a.eval_interval > 0 and (_crossed(t, prev, a.eval_interval) or final)
+            ev = hev is None and a.eval_interval > 0 and (_crossed(t, prev, a.eval_interval) or final)
             if ev and asyn is not None:
                 # snapshot + side-stream rollout; no log line and no sync of its own.  The last step's
                 # evaluation must run: wait out (and drop, they are superseded) earlier ones
@@ -174,6 +238,11 @@ def train(a) -> dict:
             if ev:
                 g = eng.rollout_evaluate(a.eval_episodes) if mode == "rollout" else eng.evaluate(a.eval_episodes)
                 last["greedy_mean_return"] = sum(g) / len(g)
+            if hev is not None:
+                done_eps = hev.poll()
+                last["evaluator_episodes"] = len(done_eps)
+                last["evaluator_mean_return"] = sum(e[0] for e in done_eps) / len(done_eps) if done_eps else None
+                last["evaluator_steps"] = hev.ev.ledger.steps
             if asyn is not None:
                 # the newest evaluation that has landed (after the last step: the final one)
                 if (res := asyn.latest(block=final)) is not None:
@@ -187,8 +256,6 @@ def train(a) -> dict:
     finally:
         if jl:
             jl.close()
-        if a.host_envs:
-            eng.close()
     return last
 
 
