@@ -12,7 +12,7 @@ candidate critic, selection (same seeds, same counter), checkpoints and cadences
 
 One acting step: ``aql_propose`` -> ``aql_act_q`` -> ``aql_select`` -> the actions D2H into a
 pinned buffer + an event | the host waits for the event and steps the envs | one
-``memcpy_h2d_async`` of the staging block (registered with HIP, read in place) ->
+``memcpy_h2d_async`` of the staging block (out of its pinned twin) ->
 ``aql_host_tail``: 4 kernel launches, 2 copies, 1 host wait.
 
 Iteration order.  ``host_overlap=False``: the acting step, then the K learner steps -- the
@@ -37,14 +37,13 @@ envs and are refused.  Out of scope: worker processes for the TRAINING envs, the
 """
 from __future__ import annotations
 
-import weakref
 
 import numpy as np
 import torch
 
 from ..envs import spaces
 from .aql import AQLEngineConfig, AQLEngineCore
-from .host_env import _unregister
+from .host_env import PinnedMirror
 
 
 class _Spaces:
@@ -79,14 +78,13 @@ class AQLHostEngine(AQLEngineCore):
         if int(vec.obs_dim) != self.obs or int(vec.action_dim) != self.adim:
             raise ValueError("the vector env's obs_dim / action_dim differ from the model's")
         self.learner.set_publish(self.actor_flat, self.actor_eps)
-        # the staging block, registered with HIP and read in place, and its device copy
+        # the staging block, shipped through its pinned twin, and its device copy
         st = vec.staging
         n = E * (2 * self.obs + 3)
         if not isinstance(st, np.ndarray) or st.dtype != np.float32 or st.shape != (n,) or not st.flags.c_contiguous:
             raise ValueError(f"staging must be a contiguous float32 array of {n} elements")
-        self._stage_ptr, self._stage_bytes = int(st.ctypes.data), int(st.nbytes)
-        h.host_register(self._stage_ptr, self._stage_bytes)
-        self._registered = weakref.finalize(self, _unregister, h, self._stage_ptr, st)
+        self._stage_bytes = int(st.nbytes)
+        self._mirror = PinnedMirror(st)
         self.stage_dev = torch.zeros(n, dtype=torch.float32, device=dev)
         self.act_host = torch.zeros(E, self.adim, dtype=torch.float32).pin_memory()
         self._act_np = self.act_host.numpy()
@@ -139,7 +137,7 @@ class AQLHostEngine(AQLEngineCore):
         self.event.synchronize()
         self.vec.step(self._act_np)
         self.env_steps += self.E
-        h.memcpy_h2d_async(self.stage_dev.data_ptr(), self._stage_ptr, self._stage_bytes, s)
+        h.memcpy_h2d_async(self.stage_dev.data_ptr(), self._mirror.stage(), self._stage_bytes, s)
         self._enqueued()
         h.aql_host_tail(self._tail, s)
         self._enqueued()
@@ -206,9 +204,9 @@ class AQLHostEngine(AQLEngineCore):
 
     def close(self) -> None:
         """Finish the queued work, release the staging block, close the vector env.  Idempotent."""
-        if self._registered.alive:
+        if self._mirror.alive:
             torch.cuda.synchronize(self.device)
-            self._registered()
+            self._mirror.release()
         close = getattr(self.vec, "close", None)
         if close is not None:
             close()

@@ -3,7 +3,7 @@
 
 :class:`AQLHostEvaluator` is the evaluator over any object of the
 :class:`~apex_amd.envs.host_vector.HostVectorEnv` protocol: ``N <= 64`` extra envs, its own device
-copy of their staging block (the host block is registered with HIP and read in place, as
+copy of their staging block (the host block is shipped through its pinned twin, as
 :class:`~apex_amd.engine.aql_host.AQLHostEngine` does), ``env_act`` / ``act_idx`` / counter
 buffers, a pinned action buffer, a side stream with an ``acted`` event, and TWO weight sets -- each
 an ``AQL`` module over flat parameters with an eval-mode handle (``FusedAQL(...)._net(noisy=False)``:
@@ -46,12 +46,12 @@ blocking, deterministic form (in-process envs).
 """
 from __future__ import annotations
 
-import weakref
 
 import numpy as np
 
 from ..envs.host_vector import staging_views
-from .host_eval import KERNELS, EpisodeLedger, WeightSets, _unregister, eval_seed
+from .host_env import PinnedMirror
+from .host_eval import KERNELS, EpisodeLedger, WeightSets, eval_seed
 
 MAX_ENVS = 64   # one workgroup per evaluator env and CU (aql_host_eval_act)
 
@@ -110,16 +110,15 @@ class AQLHostEvaluator:
         self.seed = int(seed)
         self.sd = eval_seed(self.seed) & 0xFFFFFFFFFFFF
         self.prop_seed, self.sel_seed = self.sd ^ 0x9909, self.sd ^ 0xA9C1
-        # the staging block, registered with HIP and read in place, and its device copy
+        # the staging block, shipped through its pinned twin, and its device copy
         st = vec.staging
         n = N * (2 * self.obs + 3)
         if not isinstance(st, np.ndarray) or st.dtype != np.float32 or st.shape != (n,) or not st.flags.c_contiguous:
             raise ValueError(f"staging must be a contiguous float32 array of {n} elements")
         self._stage_np = st
         self._views = staging_views(st, N, self.obs)
-        self._stage_ptr, self._stage_bytes = int(st.ctypes.data), int(st.nbytes)
-        self.hip.host_register(self._stage_ptr, self._stage_bytes)
-        self._registered = weakref.finalize(self, _unregister, self.hip, self._stage_ptr, st)
+        self._stage_bytes = int(st.nbytes)
+        self._mirror = PinnedMirror(st)
         f32 = dict(dtype=torch.float32, device=dev)
         i32 = dict(dtype=torch.int32, device=dev)
         self.stage_dev = torch.zeros(n, **f32)
@@ -180,7 +179,7 @@ class AQLHostEvaluator:
     # ------------------------------------------------------------------ device half (current stream)
     def ship(self) -> None:
         """H2D of the staging block on the current stream."""
-        self.hip.memcpy_h2d_async(self.stage_dev.data_ptr(), self._stage_ptr, self._stage_bytes,
+        self.hip.memcpy_h2d_async(self.stage_dev.data_ptr(), self._mirror.stage(), self._stage_bytes,
                                   self.torch.cuda.current_stream().cuda_stream)
 
     def act(self) -> None:
@@ -236,10 +235,10 @@ class AQLHostEvaluator:
         return self.ledger.poll()
 
     def close(self) -> None:
-        """Wait for the side stream, let go of the registered staging block.  Idempotent."""
-        if self._registered.alive:
+        """Wait for the side stream, let go of the staging block.  Idempotent."""
+        if self._mirror.alive:
             self.stream.synchronize()
-            self._registered()
+            self._mirror.release()
         self._stage_np = self._views = None
 
 
@@ -301,7 +300,7 @@ class AQLHostEvaluation:
         return self.ev.poll()
 
     def close(self) -> None:
-        """Synchronise the side stream, unregister the staging block, close the pool.  Idempotent."""
+        """Synchronise the side stream, let go of the staging block, close the pool.  Idempotent."""
         if self._closed:
             return
         self._closed = True

@@ -250,11 +250,11 @@ class CentralAQLEngine:
             self.links.ingest(None if drain or not self._paced else 1)
 
     def _packets_consumed(self) -> int:
-        """Packets that reached the replay so far, without a device sync: the host-visible
-        per-link consumed words the IPC ingest publishes (a lower bound while the GPU runs
-        behind the host), or the host's own applied counts (p2p)."""
+        """Packets that reached the replay so far, without waiting for the queued work: the
+        per-link consumed words the IPC ingest publishes, read on the control words' own stream
+        (a lower bound while the GPU runs behind the host), or the host's own applied counts (p2p)."""
         if self.transport == "ipc":
-            return int(sum(int(c) for c in self.links.ctrl.view("consumed")))
+            return int(sum(int(c) for c in self.links.dctl.view("consumed")))
         return int(sum(self.links.applied.values()))
 
     def _learner_body(self) -> None:

@@ -18,9 +18,10 @@ emulators on the host -- the GPU trains while the CPU emulates.
 Emulator worker processes live behind the vector-env protocol
 (:class:`apex_amd.envs.proc_vector.ProcRawAtariVector`); what this module adds for them is the
 device side of a pool.  A vector env that exposes ``staging`` (its shared ``[N, 2, H, W, 3]``
-block) is read in place: the shard registers the block with HIP and copies out of it with
-``memcpy_h2d_async`` on the engine's stream, so no host memcpy moves the pairs into a second
-pinned buffer.  A vector env that exposes ``banks`` and ``step_async`` / ``wait_bank`` is ingested
+block) is shipped from a pinned twin of that block (:class:`PinnedMirror`): the env ranges about
+to be copied are moved into memory that was allocated pinned, and ``memcpy_h2d_async`` reads
+those on the engine's stream.  (The block itself is shared memory the workers map; memory a
+process already has cannot be pinned on every machine.)  A vector env that exposes ``banks`` and ``step_async`` / ``wait_bank`` is ingested
 bank by bank (``HostEnvConfig.ingest``): each worker's env range gets its own H2D copies and one
 ranged ``host_env_ingest_range`` launch as soon as that worker is done, while the other workers
 are still emulating.  A range launch writes exactly what the whole launch writes for its envs, so
@@ -36,7 +37,6 @@ from __future__ import annotations
 
 import copy
 import time
-import weakref
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -61,12 +61,32 @@ def has_banks(vec) -> bool:
     return all(hasattr(vec, a) for a in ("banks", "step_async", "wait_bank"))
 
 
-def _unregister(hip, ptr: int, keep) -> None:
-    """Finalizer of a registered staging block (``keep`` holds the mapping until here)."""
-    try:
-        hip.host_unregister(ptr)
-    except RuntimeError:
-        pass
+class PinnedMirror:
+    """A pinned twin of a host staging block (a contiguous numpy array, often shared memory that
+    worker processes write).  :meth:`stage` copies a byte range of the block into the twin and
+    returns the twin's address of that range, for an asynchronous H2D copy.  Call it once the
+    writers are done with the range; the twin is rewritten only then, so whatever kept the block
+    from being written under a copy in flight keeps the twin from it as well."""
+
+    def __init__(self, block: np.ndarray):
+        self.src = block.reshape(-1).view(np.uint8)
+        self.pinned = torch.empty(self.src.size, dtype=torch.uint8).pin_memory()
+        self.dst = self.pinned.numpy()
+        self.ptr = self.pinned.data_ptr()
+        self.nbytes = int(self.src.size)
+
+    @property
+    def alive(self) -> bool:
+        return self.src is not None
+
+    def stage(self, off: int = 0, nbytes: int | None = None) -> int:
+        n = self.nbytes - off if nbytes is None else int(nbytes)
+        self.dst[off:off + n] = self.src[off:off + n]
+        return self.ptr + off
+
+    def release(self) -> None:
+        """Drop the view of the block (before its owner unmaps it)."""
+        self.src = None
 
 
 # ---------------------------------------------------------------------------- tap tables
@@ -157,19 +177,17 @@ class HostEnvShard(NStepShard):
         self.acc = torch.zeros(E, 4, **f32)      # running (return, raw return, length, -) per env
         self.obs = torch.zeros(E, 4, 84, 84, dtype=torch.uint8, device=dev)
         # host staging (pinned: the copies below are truly asynchronous) and the device twins
-        self._registered = None
+        self._mirror = None
         if staging is None:
             self.raw_host = torch.zeros(E, 2, H, W, 3, dtype=torch.uint8).pin_memory()
             self.raw_np = self.raw_host.numpy()
         else:
-            # the vector env's own shared block, registered with HIP and read in place
+            # the vector env's own shared block, shipped through its pinned twin
             if tuple(staging.shape) != (E, 2, H, W, 3) or staging.dtype != np.uint8 or not staging.flags.c_contiguous:
                 raise ValueError(f"staging must be a contiguous uint8 {(E, 2, H, W, 3)} array")
             self.raw_host = None
             self.raw_np = staging
-            self.raw_ptr = int(staging.ctypes.data)
-            self.hip.host_register(self.raw_ptr, int(staging.nbytes))
-            self._registered = weakref.finalize(self, _unregister, self.hip, self.raw_ptr, staging)
+            self._mirror = PinnedMirror(staging)
         self.pair_bytes = 2 * H * W * 3
         self.raw_dev = torch.zeros(E, 2, H, W, 3, dtype=torch.uint8, device=dev)
         self.reward_host = torch.zeros(E, dtype=torch.float32).pin_memory()
@@ -186,16 +204,17 @@ class HostEnvShard(NStepShard):
 
     def _banked(self, vec) -> bool:
         """Ingest bank by bank?  ``auto`` says yes whenever ``vec`` offers banks."""
-        if self.ingest_mode == "whole" or self._registered is None:
+        if self.ingest_mode == "whole" or self._mirror is None:
             return False
         return has_banks(vec)
 
     def _ship(self, e0: int, e1: int, reset: bool) -> None:
-        """Envs ``[e0, e1)`` of the registered staging block: their H2D copies (pairs; reward and
+        """Envs ``[e0, e1)`` of the staging block: their H2D copies (pairs; reward and
         done slices on a step) and one ingest launch over the range, on the current stream."""
         s = torch.cuda.current_stream().cuda_stream
         off = e0 * self.pair_bytes
-        self.hip.memcpy_h2d_async(self.raw_dev.data_ptr() + off, self.raw_ptr + off, (e1 - e0) * self.pair_bytes, s)
+        n = (e1 - e0) * self.pair_bytes
+        self.hip.memcpy_h2d_async(self.raw_dev.data_ptr() + off, self._mirror.stage(off, n), n, s)
         if not reset:
             self.reward_in[e0:e1].copy_(self.reward_host[e0:e1], non_blocking=True)
             self.done_in[e0:e1].copy_(self.done_host[e0:e1], non_blocking=True)
@@ -209,9 +228,9 @@ class HostEnvShard(NStepShard):
     def reset(self, vec) -> None:
         """Start every env; the start frames fill the stacks (``vec_env_reset``'s outputs).  The
         copy out of the pinned buffer is ordered like a step's (see :meth:`finish`).  With a
-        registered staging block the pairs take a step's path: per bank, or as one range."""
+        staging block the pairs take a step's path: per bank, or as one range."""
         vec.reset(self.raw_np)
-        if self._registered is None:
+        if self._mirror is None:
             self.raw_dev.copy_(self.raw_host, non_blocking=True)
             self._ingest(True)
             return
@@ -239,15 +258,15 @@ class HostEnvShard(NStepShard):
         that read them has completed.  (The same holds for the pinned reward / done / actions
         buffers, and for the copy :meth:`reset` starts.)
 
-        The invariant keeps holding with worker processes and a registered shared staging block:
-        the workers are told to step (``step_async``) only after the host has waited for the event
-        recorded after the next forward, and by then every copy that read the staging block has
-        completed.  Within a step, a bank's copy reads only that bank's env range, which its
-        worker has finished writing; it may run while the other workers still write their own,
-        disjoint ranges.  Banked ingest: for each bank, in completion order, its H2D copies and
+        The invariant keeps holding with worker processes and a shared staging block, whose pinned
+        twin is what the copies read: the workers are told to step (``step_async``) only after the
+        host has waited for the event recorded after the next forward, the twin is rewritten after
+        they have stepped, and by then every copy that read it has completed.  Within a step, a
+        bank's range is moved into the twin and copied once its worker has finished writing it; that
+        may run while the other workers still write their own, disjoint ranges.  Banked ingest: for each bank, in completion order, its H2D copies and
         one ranged ingest launch; ``nstep_emit`` and ``write_batch`` follow once all banks are in."""
         self.event.synchronize()
-        if self._registered is None:
+        if self._mirror is None:
             r, d = vec.step(self.actions_host.numpy(), self.raw_np)
             self.reward_host.numpy()[:] = r
             self.done_host.numpy()[:] = d
@@ -273,11 +292,11 @@ class HostEnvShard(NStepShard):
         self.replay.write_batch(pre=(self.slot, self.prio, self.replay.filled), bump=self.step_counter)
 
     def close(self) -> None:
-        """Let go of a registered staging block: wait for the copies that read it, unregister
-        it, drop the view.  Call before the vector env unlinks the block; idempotent."""
-        if self._registered is not None and self._registered.alive:
+        """Let go of a staging block: wait for the copies queued out of its pinned twin, drop the
+        views.  Call before the vector env unlinks the block; idempotent."""
+        if self._mirror is not None and self._mirror.alive:
             torch.cuda.synchronize(self.device)
-            self._registered()
+            self._mirror.release()
         self.raw_np = None
 
     def step_host(self, vec) -> None:

@@ -42,7 +42,6 @@ fewer than a million envs.
 from __future__ import annotations
 
 import collections
-import weakref
 
 import numpy as np
 
@@ -127,13 +126,6 @@ class WeightSets:
         self._used[self.cur] = True
 
 
-def _unregister(hip, ptr: int, keep) -> None:
-    try:
-        hip.host_unregister(ptr)
-    except RuntimeError:
-        pass
-
-
 class HostEvaluator:
     """``len(vec)`` (at most 64) greedy evaluator emulators: the device state, both act forms, the
     weight sets and the blocking ``run``; see the module docstring.  ``epsilon`` 1 is the uniform
@@ -147,7 +139,7 @@ class HostEvaluator:
         from .. import ops
         from ..models.dqn import DuelingDQN
         from ..models.fused import make_hip_net, make_workspace
-        from .host_env import Ingest
+        from .host_env import Ingest, PinnedMirror
 
         if kernel not in KERNELS:
             raise ValueError(f"kernel must be one of {KERNELS}, got {kernel!r}")
@@ -195,8 +187,8 @@ class HostEvaluator:
             self.ws = make_workspace(N, A, dev, "fp32")
             self.ws.q = self.q   # the heads kernel writes Q in place
         self._act_args = [self._fused_args(i) for i in range(2)]
-        # host staging: pinned, or the vector env's own shared block registered and read in place
-        self._registered = None
+        # host staging: pinned, or the vector env's own shared block shipped through its pinned twin
+        self._mirror = None
         staging = getattr(vec, "staging", None)
         if staging is None:
             self.raw_host = torch.zeros(N, 2, H, W, 3, dtype=torch.uint8).pin_memory()
@@ -206,9 +198,7 @@ class HostEvaluator:
                 raise ValueError(f"staging must be a contiguous uint8 {(N, 2, H, W, 3)} array")
             self.raw_host = None
             self.raw_np = staging
-            self.raw_ptr = int(staging.ctypes.data)
-            self.hip.host_register(self.raw_ptr, int(staging.nbytes))
-            self._registered = weakref.finalize(self, _unregister, self.hip, self.raw_ptr, staging)
+            self._mirror = PinnedMirror(staging)
         self.raw_dev = torch.zeros(N, 2, H, W, 3, dtype=torch.uint8, device=dev)
         self.reward_host = torch.zeros(N, dtype=torch.float32).pin_memory()
         self.done_host = torch.zeros(N, dtype=torch.float32).pin_memory()
@@ -249,10 +239,10 @@ class HostEvaluator:
     # ------------------------------------------------------------------ device half (current stream)
     def ship(self, reset: bool) -> None:
         """H2D of the pairs (and of reward / done on a step) + the ingest, on the current stream."""
-        if self._registered is None:
+        if self._mirror is None:
             self.raw_dev.copy_(self.raw_host, non_blocking=True)
         else:
-            self.hip.memcpy_h2d_async(self.raw_dev.data_ptr(), self.raw_ptr, self.raw_dev.numel(),
+            self.hip.memcpy_h2d_async(self.raw_dev.data_ptr(), self._mirror.stage(), self.raw_dev.numel(),
                                       self.torch.cuda.current_stream().cuda_stream)
         if not reset:
             self.reward_in.copy_(self.reward_host, non_blocking=True)
@@ -315,10 +305,10 @@ class HostEvaluator:
         return self.ledger.poll()
 
     def close(self) -> None:
-        """Wait for the side stream, let go of a registered staging block.  Idempotent."""
-        if self._registered is not None and self._registered.alive:
+        """Wait for the side stream, let go of a staging block.  Idempotent."""
+        if self._mirror is not None and self._mirror.alive:
             self.stream.synchronize()
-            self._registered()
+            self._mirror.release()
         self.raw_np = None
 
 
@@ -384,7 +374,7 @@ class HostEnvEvaluation:
         return self.ev.poll()
 
     def close(self) -> None:
-        """Synchronise the side stream, unregister the staging block, close the pool.  Idempotent."""
+        """Synchronise the side stream, let go of the staging block, close the pool.  Idempotent."""
         if self._closed:
             return
         self._closed = True

@@ -13,8 +13,8 @@ n-step batcher, the tree write, ``vec_act`` (same seeds, same counter), the repl
 the cadences and the checkpoints are shared.
 
 One acting step: ``vec_act`` -> the actions D2H into a pinned buffer + an event | the host waits
-for the event and steps the envs | one ``memcpy_h2d_async`` of the staging block (registered with
-HIP, read in place) -> ``vec_host_tail`` -> ``nstep_emit`` -> ``per_write_leaves``: 4 kernel
+for the event and steps the envs | one ``memcpy_h2d_async`` of the staging block (out of its
+pinned twin) -> ``vec_host_tail`` -> ``nstep_emit`` -> ``per_write_leaves``: 4 kernel
 launches, 2 copies, 1 host wait.
 
 ``done`` is the env's own flag.  A length-cap reset (``ended`` set, ``done`` clear: the episode
@@ -53,7 +53,6 @@ from __future__ import annotations
 
 import dataclasses
 import time
-import weakref
 
 import numpy as np
 import torch
@@ -62,7 +61,7 @@ from .. import ops
 from ..models.dqn import DuelingDQN
 from .graphs import capture_graph
 from .hbm_replay import HBMReplay
-from .host_env import _unregister
+from .host_env import PinnedMirror
 from .shard import NStepShard
 from .vector import MLPDQNLearner, VectorEngineConfig, save_state_dict, vec_net
 
@@ -107,15 +106,14 @@ class VectorHostShard(NStepShard):
         self.ring = replay.frames.view(torch.float32)  # [F, obs_dim]
         self.ep_ret = torch.zeros(E, dtype=torch.float32, device=dev)
         self.ep_len = torch.zeros(E, dtype=torch.float32, device=dev)
-        # the staging block, registered with HIP and read in place, and its device copy
+        # the staging block, shipped through its pinned twin, and its device copy
         st = vec.staging
         n = E * (2 * self.obs_dim + 3)
         if not isinstance(st, np.ndarray) or st.dtype != np.float32 or st.shape != (n,) or not st.flags.c_contiguous:
             raise ValueError(f"staging must be a contiguous float32 array of {n} elements")
         self._staging = st
-        self._stage_ptr, self._stage_bytes = int(st.ctypes.data), int(st.nbytes)
-        h.host_register(self._stage_ptr, self._stage_bytes)
-        self._registered = weakref.finalize(self, _unregister, h, self._stage_ptr, st)
+        self._stage_bytes = int(st.nbytes)
+        self._mirror = PinnedMirror(st)
         self.stage_dev = torch.zeros(n, dtype=torch.float32, device=dev)
         self.act_host = torch.zeros(E, dtype=torch.int32).pin_memory()
         self._act_np = self.act_host.numpy()
@@ -176,7 +174,7 @@ class VectorHostShard(NStepShard):
         self.vec.step(self._act_np)
         self.host_seconds += time.perf_counter() - t0
         self.env_steps += self.E
-        h.memcpy_h2d_async(self.stage_dev.data_ptr(), self._stage_ptr, self._stage_bytes, s)
+        h.memcpy_h2d_async(self.stage_dev.data_ptr(), self._mirror.stage(), self._stage_bytes, s)
         self._enqueued()
         h.vec_host_tail(self._tail, False, s)
         self._enqueued()
@@ -191,9 +189,9 @@ class VectorHostShard(NStepShard):
 
     def close(self) -> None:
         """Finish the queued work, release the staging block, close the vector env.  Idempotent."""
-        if self._registered.alive:
+        if self._mirror.alive:
             torch.cuda.synchronize(self.device)
-            self._registered()
+            self._mirror.release()
         close = getattr(self.vec, "close", None)
         if close is not None:
             close()

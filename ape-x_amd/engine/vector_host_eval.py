@@ -3,7 +3,7 @@ origin_repo/eval.py -- epsilon 0, a process of its own that never holds up the l
 
 :class:`VectorHostEvaluator` is the evaluator over any object of the
 :class:`~apex_amd.envs.host_vector.HostVectorEnv` protocol: ``N <= 64`` extra envs, its own device
-copy of their staging block (the host block is registered with HIP and read in place, as
+copy of their staging block (the host block is shipped through its pinned twin, as
 :class:`~apex_amd.engine.vector_host.VectorHostShard` does), ``q`` / ``actions`` buffers, a pinned
 action buffer, a side stream with an ``acted`` event, and TWO weight sets -- each a ``DuelingDQN``
 (MLP form) over flat parameters with its ``VecNet`` handle.  Step ``k`` is
@@ -46,13 +46,13 @@ deterministic form (in-process envs).
 """
 from __future__ import annotations
 
-import weakref
 
 import numpy as np
 
 from ..envs.host_vector import staging_views
 from .aql_host_eval import MAX_ENVS, AQLHostEvaluation, _Ledger, make_pool
-from .host_eval import KERNELS, WeightSets, _unregister, eval_seed
+from .host_env import PinnedMirror
+from .host_eval import KERNELS, WeightSets, eval_seed
 
 __all__ = ["MAX_ENVS", "VectorHostEvaluation", "VectorHostEvaluator", "make_pool"]
 
@@ -87,16 +87,15 @@ class VectorHostEvaluator:
         self.seed = int(seed)
         self.sd = eval_seed(self.seed) & 0xFFFFFFFFFFFF
         self.act_seed = self.sd ^ ACT_XOR
-        # the staging block, registered with HIP and read in place, and its device copy
+        # the staging block, shipped through its pinned twin, and its device copy
         st = vec.staging
         n = N * (2 * self.obs + 3)
         if not isinstance(st, np.ndarray) or st.dtype != np.float32 or st.shape != (n,) or not st.flags.c_contiguous:
             raise ValueError(f"staging must be a contiguous float32 array of {n} elements")
         self._stage_np = st
         self._views = staging_views(st, N, self.obs)
-        self._stage_ptr, self._stage_bytes = int(st.ctypes.data), int(st.nbytes)
-        self.hip.host_register(self._stage_ptr, self._stage_bytes)
-        self._registered = weakref.finalize(self, _unregister, self.hip, self._stage_ptr, st)
+        self._stage_bytes = int(st.nbytes)
+        self._mirror = PinnedMirror(st)
         f32 = dict(dtype=torch.float32, device=dev)
         i32 = dict(dtype=torch.int32, device=dev)
         self.stage_dev = torch.zeros(n, **f32)
@@ -175,7 +174,7 @@ class VectorHostEvaluator:
     # ------------------------------------------------------------------ device half (current stream)
     def ship(self) -> None:
         """H2D of the staging block on the current stream."""
-        self.hip.memcpy_h2d_async(self.stage_dev.data_ptr(), self._stage_ptr, self._stage_bytes,
+        self.hip.memcpy_h2d_async(self.stage_dev.data_ptr(), self._mirror.stage(), self._stage_bytes,
                                   self.torch.cuda.current_stream().cuda_stream)
 
     def act(self) -> None:
@@ -229,10 +228,10 @@ class VectorHostEvaluator:
         return self.ledger.poll()
 
     def close(self) -> None:
-        """Wait for the side stream, let go of the registered staging block.  Idempotent."""
-        if self._registered.alive:
+        """Wait for the side stream, let go of the staging block.  Idempotent."""
+        if self._mirror.alive:
             self.stream.synchronize()
-            self._registered()
+            self._mirror.release()
         self._stage_np = self._views = None
 
 

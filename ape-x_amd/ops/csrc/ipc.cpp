@@ -7,9 +7,12 @@
 #include <pybind11/stl.h>
 
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <stdexcept>
 #include <string>
+#include <unordered_set>
 #include <vector>
 
 #include "common.h"
@@ -33,6 +36,9 @@ T* P_(uint64_t v) {  // (P names a parameter count in some bindings)
 uint64_t U(const void* p) { return (uint64_t)reinterpret_cast<uintptr_t>(p); }
 hipStream_t S(uint64_t v) { return reinterpret_cast<hipStream_t>(static_cast<uintptr_t>(v)); }
 
+std::mutex uncached_mutex;
+std::unordered_set<void*> uncached;  // live hipDeviceMallocUncached arenas (see ipc_free)
+
 struct IpcIngestHandle {
   apex::IpcIngest g{};
 };
@@ -47,7 +53,11 @@ void register_ipc(py::module_& m) {
     void* p = nullptr;
     if (mode == 0) hip_ok(hipMalloc(&p, (size_t)bytes), "hipMalloc");
     else if (mode == 1) hip_ok(hipExtMallocWithFlags(&p, (size_t)bytes, hipDeviceMallocFinegrained), "hipExtMallocWithFlags(fine)");
-    else if (mode == 2) hip_ok(hipExtMallocWithFlags(&p, (size_t)bytes, hipDeviceMallocUncached), "hipExtMallocWithFlags(uncached)");
+    else if (mode == 2) {
+      hip_ok(hipExtMallocWithFlags(&p, (size_t)bytes, hipDeviceMallocUncached), "hipExtMallocWithFlags(uncached)");
+      std::lock_guard<std::mutex> lock(uncached_mutex);
+      uncached.insert(p);
+    }
     else throw std::invalid_argument("ipc_alloc: mode must be 0 (default), 1 (fine-grained) or 2 (uncached)");
     hip_ok(hipMemset(p, 0, (size_t)bytes), "hipMemset");
     hip_ok(hipDeviceSynchronize(), "hipDeviceSynchronize");
@@ -64,8 +74,16 @@ void register_ipc(py::module_& m) {
     hip_ok(hipGetDeviceCount(&n), "hipGetDeviceCount");
     return n;
   });
+  // An uncached arena stays allocated until the process ends: kernels have read it, and freeing
+  // uncached memory that kernels have read is not safe on every driver.  Arenas are few (one per
+  // set of links), so nothing accumulates in a training run.
   m.def("ipc_free", [](uint64_t p) {
-    if (p) hip_ok(hipFree(P<void>(p)), "hipFree");
+    if (!p) return;
+    {
+      std::lock_guard<std::mutex> lock(uncached_mutex);
+      if (uncached.count(P<void>(p))) return;
+    }
+    hip_ok(hipFree(P<void>(p)), "hipFree");
   });
   m.def("ipc_handle", [](uint64_t p) {
     hipIpcMemHandle_t h;
@@ -104,14 +122,28 @@ void register_ipc(py::module_& m) {
   // pin + map a host range (a /dev/shm control block) for GPU access; returns the device pointer
   m.def("host_register", [](uint64_t host, int64_t bytes) {
     if (!host || bytes <= 0) throw std::invalid_argument("host_register: needs a pointer and bytes > 0");
-    hip_ok(hipHostRegister(P<void>(host), (size_t)bytes, hipHostRegisterMapped | hipHostRegisterPortable),
-           "hipHostRegister");
+    hipError_t e = hipHostRegister(P<void>(host), (size_t)bytes, hipHostRegisterMapped | hipHostRegisterPortable);
+    if (e != hipSuccess) (void)hipGetLastError();  // (not left behind for the next launch to report)
+    hip_ok(e, "hipHostRegister");
     void* d = nullptr;
     hip_ok(hipHostGetDevicePointer(&d, P<void>(host), 0), "hipHostGetDevicePointer");
     return U(d);
   });
   m.def("host_unregister", [](uint64_t host) {
     if (host) hip_ok(hipHostUnregister(P<void>(host)), "hipHostUnregister");
+  });
+  // Can this machine pin host memory a program already has?  (Not every virtual machine can; the
+  // engines do not depend on it: they stage through memory that is allocated pinned.)
+  m.def("host_register_supported", []() {
+    const size_t n = 4096;
+    void* p = std::aligned_alloc(n, n);
+    if (!p) return false;
+    std::memset(p, 0, n);
+    hipError_t e = hipHostRegister(p, n, hipHostRegisterMapped | hipHostRegisterPortable);
+    if (e == hipSuccess) (void)hipHostUnregister(p);
+    else (void)hipGetLastError();
+    std::free(p);
+    return e == hipSuccess;
   });
 
   py::class_<IpcIngestHandle>(m, "IpcIngestHandle");
@@ -165,6 +197,9 @@ void register_ipc(py::module_& m) {
   });
   m.def("ipc_ingest", [](const IpcIngestHandle& h, uint64_t s) { apex::ipc_ingest(h.g, S(s)); });
   m.def("ipc_flag", [](uint64_t p, int64_t v, uint64_t s) { apex::ipc_flag(P<int64_t>(p), v, S(s)); });
+  m.def("ipc_pin_word", [](uint64_t word, uint64_t pin, uint64_t s) {
+    apex::ipc_pin_word(P<const int64_t>(word), P<int64_t>(pin), S(s));
+  });
   m.def("ipc_param_publish", [](uint64_t ctrl, int pin_off, int R, int begin_off, int K, uint64_t params,
                                 int64_t stride_f, uint64_t src, int64_t P, int64_t v, uint64_t pick, uint64_t s) {
     apex::ipc_param_publish(P_<int64_t>(ctrl), pin_off, R, begin_off, K, P_<float>(params), stride_f,

@@ -19,9 +19,9 @@
 //                       of the HBM replay, emits (global slot | -1, priority) pairs for
 //                       the tree write (per_write_* skip slot -1) and advances the replay's
 //                       fill counter by the real rows (filler rows, slot -1, carry frames only);
-//       ipc_release_k : consumed[r] += ready[r], published to the host control block
-//                       (system-scope store into hipHostRegister'ed /dev/shm, which the actor
-//                       processes read as their credit).
+//       ipc_release_k : consumed[r] += ready[r], published to the control words
+//                       (system-scope store into the control block's twin inside the arena,
+//                       which the actor processes read as their credit).
 //     No host polling and no host sync: the whole ingest is four captured launches.
 //   * AQL packets (kind 1, parallel/ipc.py AQL_PACKET): rows appended in (link, packet) order to
 //     the ONE replay ring at its cursor, then a max-priority leaf write (AQL_dis.py:120-123).
@@ -306,6 +306,11 @@ __global__ void ipc_flag_k(int64_t* p, int64_t v) {
   if (threadIdx.x == 0 && blockIdx.x == 0) store_release_sys(p, v);
 }
 
+__global__ void ipc_pin_word_k(const int64_t* word, int64_t* pin) {
+  if (threadIdx.x == 0 && blockIdx.x == 0)
+    store_release_sys(pin, __hip_atomic_load(word, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM));
+}
+
 }  // namespace
 
 void ipc_ingest(const IpcIngest& g, hipStream_t s) {
@@ -384,6 +389,12 @@ void ipc_param_publish(int64_t* ctrl, int pin_off, int R, int begin_off, int K, 
 void ipc_flag(int64_t* p, int64_t v, hipStream_t s) {
   if (!p) throw std::invalid_argument("ipc_flag: null pointer");
   ipc_flag_k<<<1, 64, 0, s>>>(p, v);
+  LAUNCH_CHECK();
+}
+
+void ipc_pin_word(const int64_t* word, int64_t* pin, hipStream_t s) {
+  if (!word || !pin) throw std::invalid_argument("ipc_pin_word: null pointer");
+  ipc_pin_word_k<<<1, 64, 0, s>>>(word, pin);
   LAUNCH_CHECK();
 }
 

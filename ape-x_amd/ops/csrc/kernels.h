@@ -1149,6 +1149,9 @@ struct IpcEmu {
 };
 void ipc_emu_push(const IpcEmu& e, hipStream_t s);
 void ipc_flag(int64_t* p, int64_t v, hipStream_t s);  // system-scope release store of v (one thread)
+// A reader's pin (parallel/ipc.py): *pin = the word at *word as it reads when the kernel runs
+// (system-scope acquire load, release store; one thread).  The reader learns the word from *pin.
+void ipc_pin_word(const int64_t* word, int64_t* pin, hipStream_t s);
 // The pinned parameter publish (parallel/ipc.py): at execution time pick buffer b of K -- not
 // the current word's (word & 0xFF), not any reader's pinned word's -- store begin[b] = v, copy
 // src [P] into params + b stride_f, then release word = v << 8 | b.  ctrl: the control block's

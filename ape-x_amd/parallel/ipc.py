@@ -16,12 +16,16 @@ parameter publish, for actor GPUs on the same node (xGMI):
   sequence words with system-scope acquires, scatter every ready packet into the link's
   replay region, release the slots), followed by one masked tree write -- no Python
   polling, no receive left posted, no host sync per step.
-* **Control plane (host memory).**  A small ``/dev/shm`` control block, mapped into every
-  process (rank 0 also registers it with ``hipHostRegister`` so its kernels can store
-  into it): per-link *consumed* counters written by rank 0's release kernel (the actors'
-  credit window, actor.py:105-115: at most ``D`` packets in flight), the published
-  parameter version, per-link heartbeat counters, drop flags, the stop flag and stop
-  acknowledgements.  The actors read and write it with plain CPU loads / stores.
+* **Control plane.**  A small ``/dev/shm`` control block, mapped into every process, holds
+  the words that only CPUs touch: per-link heartbeat counters, drop flags, sent counts, the
+  stop flag and stop acknowledgements, read and written with plain CPU loads / stores.  The
+  words that rank 0's kernels touch live in a twin of that block inside the arena
+  (:class:`DeviceControl`, same word layout): per-link *consumed* counters written by rank
+  0's release kernel (the actors' credit window, actor.py:105-115: at most ``D`` packets in
+  flight), the published parameter word, the readers' pins and the buffers' begin words.
+  Kernels address them directly; hosts -- rank 0's and, through their mapping of the arena,
+  the actors' -- move single words with small copies on a stream of their own, so no host
+  range ever has to be pinned after the fact.
 * **Parameters** (conflated, learner.py:57-68 PUB/SUB CONFLATE=1): ``K = R + 2`` parameter
   buffers.  The published word in the control block is ``v << 8 | b``: version ``v`` lives in
   buffer ``b``.  A reader *pins* the word it is about to pull (its pin slot), pulls buffer ``b``
@@ -46,7 +50,6 @@ the same device), which is how the 1-GPU box exercises it.
 """
 from __future__ import annotations
 
-import ctypes
 import json
 import mmap
 import os
@@ -93,23 +96,20 @@ def pinned_pull(ctrl: "ControlBlock", i: int, have: int, pull, retries: int = 8)
     """Reader side of the pinned protocol for reader ``i``: pin the newest published word,
     ``pull(buffer)`` it (synchronously), keep it if the buffer's begin word still reads that
     version.  Returns (installed version or None, failed pulls)."""
-    w = ctrl.param_word
-    if (w >> 8) <= have:
+    if ctrl.param_version <= have:
         return None, 0
-    pin = ctrl.view("pin")
     failed = 0
     try:
         for _ in range(retries):
-            pin[i] = w  # from here on the writer leaves this buffer alone
+            w = ctrl.pin_newest(i)  # from here on the writer leaves this buffer alone
             v, b = w >> 8, w & 0xFF
             pull(b)
-            if int(ctrl.w[ctrl.begin_off(b)]) == v:  # nobody began rewriting it during the pull: clean
+            if ctrl.begin(b) == v:  # nobody began rewriting it during the pull: clean
                 return v, failed
             failed += 1
-            w = ctrl.param_word
         return None, failed
     finally:
-        pin[i] = 0
+        ctrl.set_pin(i, 0)
 
 
 class ControlBlock:
@@ -139,9 +139,6 @@ class ControlBlock:
             self.w[0] = _MAGIC
         elif self.w[0] != _MAGIC or self.w[1] != self.R:
             raise RuntimeError(f"{self.path}: not an apex control block for {R} links")
-        self.host_ptr = ctypes.addressof(ctypes.c_char.from_buffer(self.mm))
-        self.dev_ptr = None
-        self._hip = None
 
     def off(self, field: str) -> int:
         """Word offset of ``field[0]``."""
@@ -162,7 +159,21 @@ class ControlBlock:
 
     @property
     def param_version(self) -> int:
-        return int(self.w[2]) >> 8
+        return self.param_word >> 8
+
+    def set_pin(self, i: int, word: int) -> None:
+        """Reader ``i`` pins ``word`` (0: unpins)."""
+        self.w[self.off("pin") + int(i)] = word
+
+    def pin_newest(self, i: int) -> int:
+        """Reader ``i`` pins the published word as it reads now; returns that word."""
+        w = self.param_word
+        self.set_pin(i, w)
+        return w
+
+    def begin(self, b: int) -> int:
+        """The version parameter buffer ``b`` last began."""
+        return int(self.w[self.begin_off(b)])
 
     @property
     def stop(self) -> bool:
@@ -171,22 +182,71 @@ class ControlBlock:
     def set_stop(self) -> None:
         self.w[3] = 1
 
-    def register(self, hip) -> int:
-        """Pin + map for kernels of this process; returns the device address of word 0."""
-        self._hip = hip
-        self.dev_ptr = hip.host_register(self.host_ptr, self.nbytes)
-        return self.dev_ptr
-
     def unlink(self) -> None:
         try:
             os.unlink(self.path)
         except FileNotFoundError:
             pass
 
-    def close(self) -> None:
-        if self._hip is not None and self.dev_ptr is not None:
-            self._hip.host_unregister(self.host_ptr)
-            self.dev_ptr = None
+
+class DeviceControl:
+    """The control words that rank 0's kernels touch -- consumed[R], the parameter word, pin[R],
+    begin[K] -- in a twin of ``layout`` (same word offsets) at ``dev_ptr`` inside the arena, so
+    the kernels load and store them as device memory.  A host reads or writes them with small
+    copies through a pinned scratch buffer on a stream of its own: the copies never wait for,
+    or hold up, the work queued on the caller's streams.  Rank 0 builds it over its arena, an
+    actor over its mapping of the arena; the accessors are :class:`ControlBlock`'s."""
+
+    def __init__(self, hip, dev_ptr: int, layout: ControlBlock, device):
+        self.hip, self.dev_ptr, self.c = hip, int(dev_ptr), layout
+        self.R, self.K = layout.R, layout.K
+        self.stream = torch.cuda.Stream(device=device)
+        self._buf = torch.zeros(max(self.R, 1), dtype=torch.int64).pin_memory()
+        self._np = self._buf.numpy()
+
+    def off(self, field: str) -> int:
+        return self.c.off(field)
+
+    def begin_off(self, b: int) -> int:
+        return self.c.begin_off(b)
+
+    def _read(self, word: int, n: int = 1) -> np.ndarray:
+        self.hip.memcpy_async(self._buf.data_ptr(), self.dev_ptr + 8 * int(word), 8 * n, self.stream.cuda_stream)
+        self.stream.synchronize()
+        return self._np[:n].copy()
+
+    def _write(self, word: int, value: int) -> None:
+        self._np[0] = value
+        self.hip.memcpy_async(self.dev_ptr + 8 * int(word), self._buf.data_ptr(), 8, self.stream.cuda_stream)
+        self.stream.synchronize()  # landed: the kernels see it from here on
+
+    def view(self, field: str) -> np.ndarray:
+        """A snapshot of ``field[0 .. R)``."""
+        return self._read(self.off(field), self.R)
+
+    @property
+    def param_word(self) -> int:
+        return int(self._read(2)[0])
+
+    @property
+    def param_version(self) -> int:
+        return self.param_word >> 8
+
+    def set_pin(self, i: int, word: int) -> None:
+        self._write(self.off("pin") + int(i), word)
+
+    def pin_newest(self, i: int) -> int:
+        """One thread on the GPU loads the word and stores it as the pin, back to back: the
+        word can move on between the two only for as long as a store takes to follow a load."""
+        pin = self.off("pin") + int(i)
+        self.hip.ipc_pin_word(self.dev_ptr + 8 * 2, self.dev_ptr + 8 * pin, self.stream.cuda_stream)
+        return int(self._read(pin)[0])
+
+    def begin(self, b: int) -> int:
+        return int(self._read(self.begin_off(b))[0])
+
+    def consumed(self, i: int) -> int:
+        return int(self._read(self.off("consumed") + int(i))[0])
 
 
 def aql_packet_floats(E: int, obs: int, TA: int) -> int:
@@ -233,11 +293,12 @@ class IpcLearnerLinks:
         self.seq_off = _align(self.R * self.D * self.pkt)
         self.par_off = _align(self.seq_off + 8 * self.R * self.D)
         self.PS = _align(4 * self.P) // 4  # parameter buffer stride (floats; 256-byte aligned buffers)
-        self.nbytes = self.par_off + self.K * 4 * self.PS
-        self._pick = torch.zeros(1, dtype=torch.int32, device=device)  # the publish's buffer (scratch)
-        self.arena = h.ipc_alloc(self.nbytes, mode)
         self.ctrl = ControlBlock(f"apex_ipc_{prefix.replace('/', '_')}_{os.getpid()}", R, create=True)
-        self.ctrl.register(h)
+        self.ctl_off = _align(self.par_off + self.K * 4 * self.PS)  # the control block's device twin
+        self.nbytes = self.ctl_off + self.ctrl.nbytes
+        self._pick = torch.zeros(1, dtype=torch.int32, device=device)  # the publish's buffer (scratch)
+        self.arena = h.ipc_alloc(self.nbytes, mode)  # (zeroed)
+        self.dctl = DeviceControl(h, self.arena + self.ctl_off, self.ctrl, self.device)
         dev = self.device
         i64 = dict(dtype=torch.int64, device=dev)
         self.consumed = torch.zeros(R, **i64)
@@ -252,7 +313,7 @@ class IpcLearnerLinks:
         mk = lambda cap: h.make_ipc_ingest(dict(  # noqa: E731
             tables, R=R, D=D, E=E, cap=cap, packet_bytes=self.pkt, ring=self.arena, seq=self.arena + self.seq_off,
             consumed=self.consumed.data_ptr(), ready=self.ready.data_ptr(), live=self.live_dev.data_ptr(),
-            prefix=self.prefix_dev.data_ptr(), host_consumed=self.ctrl.dev_ptr + 8 * self.ctrl.off("consumed"),
+            prefix=self.prefix_dev.data_ptr(), host_consumed=self.dctl.dev_ptr + 8 * self.ctrl.off("consumed"),
             applied=self.applied_dev.data_ptr(), slots_out=self.slots_out.data_ptr(),
             prio_out=self.prio_out.data_ptr()))
         self.ingest_handle = mk(self.cap)
@@ -264,7 +325,7 @@ class IpcLearnerLinks:
         self._hb_t = time.monotonic()
         self.closed = False
         geo = dict(R=R, D=D, E=E, P=P, PS=self.PS, pkt=self.pkt, packet_nbytes=self.packet_nbytes, seq_off=self.seq_off,
-                   par_off=self.par_off, shm=self.ctrl.name, device=self.device.index or 0)
+                   par_off=self.par_off, ctl_off=self.ctl_off, shm=self.ctrl.name, device=self.device.index or 0)
         store.set(f"{prefix}/ipc/handle", h.ipc_handle(self.arena))
         store.set(f"{prefix}/ipc/geometry", json.dumps(geo))
         # every actor has mapped the control block -> remove its name (nothing lingers in /dev/shm)
@@ -348,7 +409,7 @@ class IpcLearnerLinks:
         stream: the GPU picks a buffer neither current nor pinned when the publish executes,
         marks it begun, copies ``flat`` into it and releases the new word.  Returns the version."""
         self.version += 1
-        c = self.ctrl
+        c = self.dctl
         self.hip.ipc_param_publish(c.dev_ptr, c.off("pin"), self.R, c.begin_off(0), self.K,
                                    self.arena + self.par_off, self.PS, flat.data_ptr(), self.P, self.version,
                                    self._pick.data_ptr(), self._s())
@@ -416,7 +477,7 @@ class IpcLearnerLinks:
             torch.cuda.synchronize(self.device)
         st = self.stats()
         self.ctrl.unlink()
-        self.ctrl.close()
+        self.dctl.stream.synchronize()
         self.hip.ipc_free(self.arena)
         self.arena = 0
         return st
@@ -451,9 +512,10 @@ class IpcActorLink:
             raise ValueError(f"parameter count {flat.numel()} != the learner's {self.P}")
         self.remote = h.ipc_open(store.get(f"{prefix}/ipc/handle"), self.device.index or 0)
         self.ctrl = ControlBlock(geo["shm"], self.R, create=False)
+        self.dctl = DeviceControl(h, self.remote + geo["ctl_off"], self.ctrl, self.device)
         store.set(f"{prefix}/ipc/opened/{rank}", "1")
         self.i = rank - 1
-        self.consumed = self.ctrl.view("consumed")
+        self._consumed = 0
         self.hb = self.ctrl.view("heartbeat")
         self.period = float(heartbeat_every)
         self._hb_t = 0.0
@@ -504,14 +566,18 @@ class IpcActorLink:
         n = self.sent
         timeout = self.credit_timeout if timeout is None else float(timeout)
         deadline = time.monotonic() + timeout
-        while n - int(self.consumed[self.i]) >= self.D:
+        # (consumed only grows: the last value read is re-read only when it leaves no credit)
+        while n - self._consumed >= self.D:
+            self._consumed = self.dctl.consumed(self.i)
+            if n - self._consumed < self.D:
+                break
             self.beat()
             if self.stopped or self.ctrl.view("drop")[self.i]:
                 self.check_stop()  # a drop: acknowledge and abandon the staged packet
                 return False
             if time.monotonic() > deadline:
                 raise TimeoutError(f"actor rank {self.rank}: no credit for {timeout:.0f}s "
-                                   f"(sent {n}, consumed {int(self.consumed[self.i])}, stop {self.ctrl.stop})")
+                                   f"(sent {n}, consumed {self._consumed}, stop {self.ctrl.stop})")
             time.sleep(0.0001)
         k, s = n % self.D, self._s()
         slot = self.remote + (self.i * self.D + k) * self.pkt
@@ -533,7 +599,7 @@ class IpcActorLink:
             self._ev.record(torch.cuda.current_stream(self.device))
             self._ev.synchronize()
 
-        v, failed = pinned_pull(self.ctrl, self.i, self.version, pull, retries)
+        v, failed = pinned_pull(self.dctl, self.i, self.version, pull, retries)
         self.pulls_retried += failed
         if v is not None:
             self.version = v

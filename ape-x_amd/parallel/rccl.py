@@ -33,7 +33,9 @@ class RcclComm:
         self.rank = dist.get_rank(group)
         root = dist.get_global_rank(group, 0) if group is not None else 0
         box = [self.hip.rccl_unique_id() if self.rank == 0 else None]
-        dist.broadcast_object_list(box, src=root, group=group, device=self.device)
+        # (the pickled id travels in a tensor: on the GPU for nccl, on the host for any other backend)
+        on = self.device if dist.get_backend(group) == "nccl" else torch.device("cpu")
+        dist.broadcast_object_list(box, src=root, group=group, device=on)
         self.handle = self.hip.rccl_comm_init(box[0], self.world, self.rank, self.device.index or 0)
 
     def count(self) -> int:

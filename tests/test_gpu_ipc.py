@@ -1,8 +1,8 @@
 """HIP IPC primitives of the central transport (parallel/ipc.py, ops/csrc/ipc.cpp) between
 two processes on ONE MI355X: an uncached arena exported with hipIpcGetMemHandle, a peer
 process writing into it with hipMemcpyAsync + a system-scope sequence store, the owner's
-kernels storing into a hipHostRegister'ed /dev/shm control block that the other process
-reads with plain CPU loads."""
+kernels storing into the control words inside the arena (DeviceControl) that the other process
+reads through its mapping of the arena."""
 import os
 import socket
 
@@ -29,7 +29,7 @@ def _body(rank, port, q):
         import torch.distributed as dist
 
         from apex_amd import ops
-        from apex_amd.parallel.ipc import ControlBlock
+        from apex_amd.parallel.ipc import ControlBlock, DeviceControl
 
         torch.cuda.set_device(0)
         store = dist.TCPStore("127.0.0.1", port, 2, rank == 0, timedelta(seconds=60))
@@ -37,9 +37,9 @@ def _body(rank, port, q):
         N = 1 << 20
         s = torch.cuda.current_stream().cuda_stream
         if rank == 0:
-            arena = h.ipc_alloc(N + 4096, 2)
             ctrl = ControlBlock(f"apex_ipc_test_{os.getpid()}", 2, create=True)
-            dev = ctrl.register(h)
+            arena = h.ipc_alloc(N + 4096 + ctrl.nbytes, 2)
+            dev = DeviceControl(h, arena + N + 4096, ctrl, "cuda").dev_ptr
             store.set("handle", h.ipc_handle(arena))
             store.set("shm", ctrl.name)
             host = torch.zeros(N // 4 + 2, dtype=torch.int32)
@@ -53,17 +53,17 @@ def _body(rank, port, q):
                 time.sleep(0.001)
             h.memcpy_sync(host.data_ptr(), arena, N)
             ok = bool(seen) and torch.equal(host[:N // 4], torch.arange(N // 4, dtype=torch.int32) * 3)
-            h.ipc_flag(dev + 8 * ctrl.off("consumed"), 1234, s)  # kernel store into shm
+            h.ipc_flag(dev + 8 * ctrl.off("consumed"), 1234, s)  # kernel store into the control words
             torch.cuda.synchronize()
             store.wait(["done"], timedelta(seconds=60))
             ctrl.unlink()
-            ctrl.close()
             h.ipc_free(arena)
             q.put((0, ok))
         else:
             store.wait(["handle", "shm"], timedelta(seconds=60))
             remote = h.ipc_open(store.get("handle"), 0)
             ctrl = ControlBlock(store.get("shm").decode(), 2, create=False)
+            dctl = DeviceControl(h, remote + N + 4096, ctrl, "cuda")
             src = (torch.arange(N // 4, dtype=torch.int32, device="cuda") * 3)
             h.memcpy_async(remote, src.data_ptr(), N, s)
             h.ipc_flag(remote + N, 7, s)
@@ -71,7 +71,7 @@ def _body(rank, port, q):
             deadline = time.monotonic() + 60
             got = None
             while time.monotonic() < deadline:
-                v = int(ctrl.view("consumed")[0])
+                v = int(dctl.view("consumed")[0])
                 if v == 1234:
                     got = v
                     break
@@ -104,7 +104,7 @@ def test_ipc_arena_peer_copy_and_shm_control(cuda):
         if p.is_alive():
             p.kill()
     assert out[0] is True, out[0]   # the peer's bytes landed before its sequence word
-    assert out[1] is True, out[1]   # the owner's kernel store reached the other process's CPU
+    assert out[1] is True, out[1]   # the owner's kernel store reached the other process's host
 
 
 def _params_body(rank, port, q, seconds, delay_cycles):

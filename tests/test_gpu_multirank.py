@@ -281,7 +281,7 @@ def _stop_while_credit_blocked_body(rank, world, killed):
             assert time.monotonic() < deadline, f"dead actor {r} never dropped"
             L.check_heartbeats(every=0.0)
             time.sleep(0.05)
-    consumed_before = {r: int(L.ctrl.view("consumed")[r - 1]) for r in blocked}
+    consumed_before = {r: int(L.dctl.view("consumed")[r - 1]) for r in blocked}
     links = eng.close()
     rp = eng.replay
     mism = {}
