@@ -29,6 +29,12 @@ Launch budget (kernel launches per step, all on the caller's stream, no host syn
   evaluation (``copy_f32`` snapshot on the training stream, ``vec_rollout`` on a side stream) +
   three async copies to pinned memory; eager, between graph replays.
 
+``wide_net=True`` runs the same net and the same launch sequence through the fp32-MFMA kernels of
+``ops/csrc/vector_wide_kernels.hip`` (``vecw_act`` / ``vecw_learn`` / ``vecw_grad``: observations to
+128 floats, 32 actions, a workgroup per 32 rows); the narrow kernels stop at 8 / 7 and stay the
+default.  Evaluation (``evaluate``, ``vec_rollout``) keeps the narrow forward over the same
+parameter storage, so it is offered for the device envs only.
+
 Serial actor-then-learner on one stream; overlap and multi-GPU topologies are the Atari
 engine's and are not offered here.  Envs other than ``VECTOR_ENVS`` -- any gym-API env with a
 flat observation and a discrete action space, stepped on the CPU -- train under the same
@@ -107,8 +113,9 @@ class VectorActorShard(NStepShard):
     def __init__(self, replay: HBMReplay, n_envs: int, env_id: str, n_step: int = 3, gamma: float = 0.99,
                  eps_base: float = 0.4, eps_alpha: float = 7.0, actor_offset: int = 0,
                  total_actors: int | None = None, seed: int = 0, mode: str = "reference",
-                 max_episode_steps: int | None = None):
+                 max_episode_steps: int | None = None, wide: bool = False):
         self.env_id = env_id
+        self.wide = bool(wide)   # act with vecw_act (the MFMA forward) instead of vec_act
         self.kind, self.obs_dim, n_actions, limit = env_spec(env_id)
         self.max_episode_steps = int(limit if max_episode_steps is None else max_episode_steps)
         if replay.frame_bytes != 4 * self.obs_dim:
@@ -129,9 +136,10 @@ class VectorActorShard(NStepShard):
         if model.input_shape != (self.obs_dim,) or model.num_actions != self.A:
             raise ValueError("policy shape does not match the env")
         self._policy = model
-        self._act = self.hip.make_vec_act(vec_net(self.hip, model), self.ring.data_ptr(), self.st["hist"].data_ptr(),
-                                          self.E, self.eps.data_ptr(), self.act_seed,
-                                          self.step_counter.data_ptr(), self.q.data_ptr(), self.actions.data_ptr())
+        make = self.hip.make_vecw_act if self.wide else self.hip.make_vec_act
+        self._act = make(vec_net(self.hip, model), self.ring.data_ptr(), self.st["hist"].data_ptr(), self.E,
+                         self.eps.data_ptr(), self.act_seed, self.step_counter.data_ptr(), self.q.data_ptr(),
+                         self.actions.data_ptr())
 
     def reset(self) -> None:
         self.hip.vec_classic_reset(self.env, self.step_counter.data_ptr(), self.new_frame.data_ptr(),
@@ -145,7 +153,7 @@ class VectorActorShard(NStepShard):
         """Q of the current observations into ``self.q`` and the epsilon-greedy actions."""
         if self._act is None:
             raise RuntimeError("set_policy() first: acting needs the HIP forward's weights")
-        self.hip.vec_act(self._act, self._stream())
+        (self.hip.vecw_act if self.wide else self.hip.vec_act)(self._act, self._stream())
 
     def env_step(self) -> None:
         self.hip.vec_classic_step(self.env, self.actions.data_ptr(), self.step_counter.data_ptr(),
@@ -191,6 +199,7 @@ class VectorEngineConfig:
     eps_base: float = 0.4
     eps_alpha: float = 7.0
     fused_norm: bool = True          # grad-norm partials from the gradient launch (5 launches per SGD step)
+    wide_net: bool = False           # the MFMA kernels (vecw_*): obs <= 128, A <= 32; same launch sequence
     seed: int = 0
 
     def validate(self, device_env: bool = True) -> "VectorEngineConfig":
@@ -255,7 +264,8 @@ class MLPDQNLearner:
         self.q_s = torch.zeros(B, A, **f32)
         self.q_s2 = torch.zeros(B, A, **f32)
         self.qt_s2 = torch.zeros(B, A, **f32)
-        self.lay = h.vec_layout()
+        wide = bool(cfg.wide_net)
+        self.lay = h.vecw_layout() if wide else h.vec_layout()
         self.vec = torch.zeros(B, self.lay["STRIDE"], **f32)
         self.delta = torch.zeros(B, **f32)
         self.lw = torch.zeros(B, **f32)
@@ -265,20 +275,21 @@ class MLPDQNLearner:
         self.step_counter = torch.zeros(1, dtype=torch.int64, device=dev)
         # PER beta, annealed on the device: vec_learn writes beta_by_frame(step + 1) for the next draw
         self.beta = torch.full((1,), float(cfg.beta), **f32)
-        self.nblk = h.vec_grad_blocks(self.P)
+        self.nblk = h.vecw_grad_blocks(self.obs_dim, A) if wide else h.vec_grad_blocks(self.P)
         self.part = torch.zeros(self.nblk, dtype=torch.float64, device=dev)
         self.partials = torch.zeros(h.grad_norm_partials(), dtype=torch.float64, device=dev)
         self.ring = replay.frames.view(torch.float32)
         self.net = vec_net(h, self.model)
         self.tnet = vec_net(h, self.target)
-        self.L = h.make_vec_learn(self.net, self.tnet, dict(
+        self._learn, self._grad = (h.vecw_learn, h.vecw_grad) if wide else (h.vec_learn, h.vec_grad)
+        self.L = (h.make_vecw_learn if wide else h.make_vec_learn)(self.net, self.tnet, dict(
             replay.trans_ptrs(), ring=self.ring.data_ptr(), idx=self.idx.data_ptr(), w=self.w.data_ptr(), B=B,
             gamma_n=float(cfg.gamma ** cfg.n_step), q_s=self.q_s.data_ptr(), q_s2=self.q_s2.data_ptr(),
             qt_s2=self.qt_s2.data_ptr(), vec=self.vec.data_ptr(), delta=self.delta.data_ptr(),
             lw=self.lw.data_ptr(), step=self.step_counter.data_ptr(), beta_out=self.beta.data_ptr(),
             beta0=float(cfg.beta), beta_horizon=float(cfg.beta_horizon)))
-        self.G = h.make_vec_grad(self.vec.data_ptr(), B, self.obs_dim, A, self.P, self.flat_grad.data_ptr(),
-                                 self.part.data_ptr())
+        self.G = (h.make_vecw_grad if wide else h.make_vec_grad)(
+            self.vec.data_ptr(), B, self.obs_dim, A, self.P, self.flat_grad.data_ptr(), self.part.data_ptr())
 
     @staticmethod
     def _stream() -> int:
@@ -290,8 +301,8 @@ class MLPDQNLearner:
     def forward_backward(self) -> None:
         """Q(s), Q(s'), Q_target(s'), loss terms and the flat gradient of the rows in ``idx``."""
         s = self._stream()
-        self.hip.vec_learn(self.L, s)
-        self.hip.vec_grad(self.G, s)
+        self._learn(self.L, s)
+        self._grad(self.G, s)
 
     def optimize(self) -> None:
         h, s = self.hip, self._stream()
@@ -348,7 +359,8 @@ class VectorApexEngine(GreedyRollouts):
         self.actor_model = make_model(cfg.env_id).to(dev)
         self.actor_flat = self.actor_model.flatten_parameters()
         self.shard = VectorActorShard(self.replay, cfg.n_envs, cfg.env_id, cfg.n_step, cfg.gamma, cfg.eps_base,
-                                      cfg.eps_alpha, seed=cfg.seed * 0x2545F491 + 0xAC7, mode=cfg.nstep_mode)
+                                      cfg.eps_alpha, seed=cfg.seed * 0x2545F491 + 0xAC7, mode=cfg.nstep_mode,
+                                      wide=cfg.wide_net)
         self.shard.set_policy(self.actor_model)
         self.publish_params()
         self.learn_steps = 0

@@ -46,8 +46,13 @@ online net on a separate env), or beside training :mod:`apex_amd.engine.vector_h
 (evaluator envs in worker processes, ``vec_host_eval_act`` on a side stream, two weight sets, a
 pump that never waits; ``train_vector --host-envs --eval-envs N``).  ``rollout_evaluate`` and
 :class:`~apex_amd.engine.vector.VectorEvaluator` play device envs and are refused.  Out of scope:
-worker processes for the TRAINING envs, wider nets than ``kVecMaxObs`` / ``kVecMaxA``, the central
-topology.
+worker processes for the TRAINING envs, the central topology, and a wide side-stream evaluator.
+
+Shapes: observations to 8 floats and 7 actions (``kVecMaxObs`` / ``kVecMaxA``) by default; with
+``VectorEngineConfig.wide_net`` the acting forward and the learner are the MFMA kernels of
+``ops/csrc/vector_wide_kernels.hip`` and the limits are 128 / 32 (``kVecWideMaxObs`` /
+``kVecWideMaxA``).  ``vec_host_eval_act`` is narrow only: a wide engine evaluates with the blocking
+:meth:`VectorHostEngine.evaluate`.
 """
 from __future__ import annotations
 
@@ -67,19 +72,23 @@ from .vector import MLPDQNLearner, VectorEngineConfig, save_state_dict, vec_net
 
 MAX_OBS = 8       # kVecMaxObs: the MLP kernels' widest observation
 MAX_ACTIONS = 7   # kVecMaxA: their widest action set
+WIDE_MAX_OBS = 128      # kVecWideMaxObs: the wide (MFMA) kernels' widest observation
+WIDE_MAX_ACTIONS = 32   # kVecWideMaxA: their widest action set
 
 
-def host_env_spec(vec) -> tuple[int, int, int | None]:
+def host_env_spec(vec, wide: bool = False) -> tuple[int, int, int | None]:
     """``(obs_dim, n_actions, max_episode_steps)`` of a vector env the MLP kernels can play
-    (``max_episode_steps``: its registered TimeLimit, None if it has none).  No GPU needed."""
+    (``max_episode_steps``: its registered TimeLimit, None if it has none); ``wide``: the limits
+    of the wide kernels (``VectorEngineConfig.wide_net``).  No GPU needed."""
     if getattr(vec, "continuous", False):
         raise ValueError("the vector Ape-X engine takes a discrete action space; a continuous (Box) one is AQL's "
                          "(engine/aql_host.py)")
     obs, n_actions = int(vec.obs_dim), int(vec.n_actions)
-    if not 1 <= obs <= MAX_OBS:
-        raise ValueError(f"observation dim {obs} is outside the MLP kernels' limit of {MAX_OBS} (kVecMaxObs)")
-    if not 1 <= n_actions <= MAX_ACTIONS:
-        raise ValueError(f"{n_actions} actions are outside the MLP kernels' limit of {MAX_ACTIONS} (kVecMaxA)")
+    max_obs, max_a, tag = (WIDE_MAX_OBS, WIDE_MAX_ACTIONS, "kVecWideMax") if wide else (MAX_OBS, MAX_ACTIONS, "kVecMax")
+    if not 1 <= obs <= max_obs:
+        raise ValueError(f"observation dim {obs} is outside the MLP kernels' limit of {max_obs} ({tag}Obs)")
+    if not 1 <= n_actions <= max_a:
+        raise ValueError(f"{n_actions} actions are outside the MLP kernels' limit of {max_a} ({tag}A)")
     lim = getattr(vec, "max_episode_steps", None)
     return obs, n_actions, None if lim is None else int(lim)
 
@@ -92,9 +101,10 @@ class VectorHostShard(NStepShard):
 
     def __init__(self, replay: HBMReplay, vec, n_step: int = 3, gamma: float = 0.99, eps_base: float = 0.4,
                  eps_alpha: float = 7.0, actor_offset: int = 0, total_actors: int | None = None, seed: int = 0,
-                 mode: str = "reference"):
+                 mode: str = "reference", wide: bool = False):
         self.vec = vec
-        self.obs_dim, n_actions, self.max_episode_steps = host_env_spec(vec)
+        self.wide = bool(wide)   # act with vecw_act; the tail takes the wide observation limit
+        self.obs_dim, n_actions, self.max_episode_steps = host_env_spec(vec, self.wide)
         E = len(vec)
         if not 1 <= E <= 4096:
             raise ValueError("VectorHostShard: 1 <= envs <= 4096 (the actor step's one-launch tree write)")
@@ -122,7 +132,8 @@ class VectorHostShard(NStepShard):
             E=E, obs=self.obs_dim, F=replay.frame_capacity, stage=self.stage_dev.data_ptr(),
             ring=self.ring.data_ptr(), step=self.step_counter.data_ptr(), reward=self.reward.data_ptr(),
             done=self.done.data_ptr(), new_frame=self.new_frame.data_ptr(), hist=self.st["hist"].data_ptr(),
-            ep_log=self.ep_log.data_ptr(), ep_ret=self.ep_ret.data_ptr(), ep_len=self.ep_len.data_ptr()))
+            ep_log=self.ep_log.data_ptr(), ep_ret=self.ep_ret.data_ptr(), ep_len=self.ep_len.data_ptr(),
+            wide=self.wide))
         self._act = None
         self.env_steps = 0    # host env steps taken (all envs)
         self.host_seconds = 0.0   # wall time inside vec.step
@@ -136,9 +147,10 @@ class VectorHostShard(NStepShard):
         if model.input_shape != (self.obs_dim,) or model.num_actions != self.A:
             raise ValueError("policy shape does not match the env")
         self._policy = model
-        self._act = self.hip.make_vec_act(vec_net(self.hip, model), self.ring.data_ptr(), self.st["hist"].data_ptr(),
-                                          self.E, self.eps.data_ptr(), self.act_seed,
-                                          self.step_counter.data_ptr(), self.q.data_ptr(), self.actions.data_ptr())
+        make = self.hip.make_vecw_act if self.wide else self.hip.make_vec_act
+        self._act = make(vec_net(self.hip, model), self.ring.data_ptr(), self.st["hist"].data_ptr(), self.E,
+                         self.eps.data_ptr(), self.act_seed, self.step_counter.data_ptr(), self.q.data_ptr(),
+                         self.actions.data_ptr())
 
     def reset(self) -> None:
         """Start every host env; their first observations into the ring (the reset form of
@@ -155,7 +167,7 @@ class VectorHostShard(NStepShard):
         """Q of the current observations into ``self.q`` and the epsilon-greedy actions."""
         if self._act is None:
             raise RuntimeError("set_policy() first: acting needs the HIP forward's weights")
-        self.hip.vec_act(self._act, self._stream())
+        (self.hip.vecw_act if self.wide else self.hip.vec_act)(self._act, self._stream())
 
     def act_begin(self) -> None:
         """The acting forward, the actions on their way to the host, the event the host waits for."""
@@ -211,7 +223,7 @@ class VectorHostEngine:
         if cfg.actor_steps_per_learner_step != 1:
             raise ValueError("a host-env engine takes one env step per iteration: set learner_steps, not "
                              "actor_steps_per_learner_step")
-        self.obs_dim, self.A, self.limit = host_env_spec(vec)
+        self.obs_dim, self.A, self.limit = host_env_spec(vec, cfg.wide_net)
         self.cfg = cfg = dataclasses.replace(cfg, n_envs=len(vec)).validate(device_env=False)
         self.vec = vec
         self.K = int(learner_steps)
@@ -227,7 +239,7 @@ class VectorHostEngine:
         self.actor_model = DuelingDQN.from_shapes((self.obs_dim,), self.A).to(dev)
         self.actor_flat = self.actor_model.flatten_parameters()
         self.shard = VectorHostShard(self.replay, vec, cfg.n_step, cfg.gamma, cfg.eps_base, cfg.eps_alpha,
-                                     seed=cfg.seed * 0x2545F491 + 0xAC7, mode=cfg.nstep_mode)
+                                     seed=cfg.seed * 0x2545F491 + 0xAC7, mode=cfg.nstep_mode, wide=cfg.wide_net)
         self.shard._enqueued = lambda: self._enqueued()
         self.shard.set_policy(self.actor_model)
         self.publish_params()

@@ -72,6 +72,9 @@ class VectorHostEvaluator:
 
         if kernel not in KERNELS:
             raise ValueError(f"kernel must be one of {KERNELS}, got {kernel!r}")
+        if getattr(getattr(engine, "cfg", None), "wide_net", False):
+            raise ValueError("the vector host evaluator's act kernels (vec_host_eval_act, vec_act) are narrow only; "
+                             "a wide_net engine evaluates with the blocking VectorHostEngine.evaluate")
         N = len(vec)
         if not 1 <= N <= MAX_ENVS:
             raise ValueError(f"the vector host evaluator runs 1..{MAX_ENVS} envs, got {N}")

@@ -42,7 +42,9 @@ def staging_views(block: np.ndarray, n: int, obs: int) -> dict:
 
 class HostVectorEnv:
     def __init__(self, env_fns: str | Sequence[Callable], n: int | None = None, seed: int = 0,
-                 max_episode_length: int = 50000):
+                 max_episode_length: int = 50000, max_obs: int = MAX_OBS):
+        """``max_obs``: the widest observation the consumer's acting kernel takes (default: the AQL
+        acting kernels' 64; the wide vector Ape-X net passes 128)."""
         if isinstance(env_fns, str):
             from .core import make
 
@@ -78,8 +80,8 @@ class HostVectorEnv:
             self.low = self.high = np.zeros(1, dtype=np.float32)
         else:
             raise ValueError(f"HostVectorEnv takes Box or Discrete actions, got {sp!r}")
-        if self.obs_dim > MAX_OBS:
-            raise ValueError(f"observation dim {self.obs_dim} exceeds the acting kernels' limit of {MAX_OBS}")
+        if self.obs_dim > int(max_obs):
+            raise ValueError(f"observation dim {self.obs_dim} exceeds the acting kernels' limit of {int(max_obs)}")
         if self.action_dim > MAX_ACTION_DIM:
             raise ValueError(f"action dim {self.action_dim} exceeds the candidate critic's limit of {MAX_ACTION_DIM}")
         if not self.continuous and self.n_actions > MAX_ACTIONS:

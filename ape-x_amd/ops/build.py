@@ -55,6 +55,7 @@ HIP_SOURCES = [
     "f32_kernels.hip",
     "ipc_kernels.hip",
     "vector_kernels.hip",
+    "vector_wide_kernels.hip",
     "vector_host_kernels.hip",
     "host_env_kernels.hip",
     "host_eval_kernels.hip",
@@ -178,6 +179,13 @@ HIP_FLAGS = [
 ]
 
 
+# Per-source flags.  The wide MLP kernels are built without the packed fp32 VALU ops
+# (v_pk_add/mul/fma_f32): their epilogues and reductions stay on the scalar fp32 forms.
+EXTRA_HIP_FLAGS = {
+    "vector_wide_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+}
+
+
 def build_hip(force: bool = False, jobs: int | None = None) -> Path:
     """Every object is keyed by the sha256 of its source, all headers and its full
     compile line (sidecar ``<obj>.sha256``); the library by the hashes of its objects and
@@ -193,7 +201,8 @@ def build_hip(force: bool = False, jobs: int | None = None) -> Path:
         o = BUILD / (s.name + ".o")
         objs.append(o)
         if s.suffix == ".hip":
-            cmd = [_hipcc(), *HIP_FLAGS, "-x", "hip", *_py_includes(), "-c", str(s), "-o", str(o)]
+            cmd = [_hipcc(), *HIP_FLAGS, *EXTRA_HIP_FLAGS.get(s.name, []), "-x", "hip", *_py_includes(), "-c", str(s),
+                   "-o", str(o)]
         else:
             # host-only translation unit (pybind11 glue); still compiled by hipcc so
             # hip_runtime types resolve, but with no device code of its own.

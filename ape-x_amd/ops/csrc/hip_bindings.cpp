@@ -1129,7 +1129,7 @@ PYBIND11_MODULE(_apex_hip, m) {
                      P<int>(new_frame), P<float>(ep_log), S(s));
   });
   // the acting step's env half over host envs (vector_host_kernels.hip); d: E, obs, F, stage, ring, step,
-  // reward, done, new_frame, hist, ep_log, ep_ret, ep_len
+  // reward, done, new_frame, hist, ep_log, ep_ret, ep_len [+ wide: the wide net's observation limit]
   py::class_<VecHostTail>(m, "VecHostTail");
   m.def("make_vec_host_tail", [](py::dict d) {
     auto g = [&](const char* k) { return d[k].cast<uint64_t>(); };
@@ -1139,6 +1139,7 @@ PYBIND11_MODULE(_apex_hip, m) {
     a.reward = P<float>(g("reward")); a.done = P<float>(g("done")); a.new_frame = P<int>(g("new_frame"));
     a.hist = P<int>(g("hist")); a.ep_log = P<float>(g("ep_log")); a.ep_ret = P<float>(g("ep_ret"));
     a.ep_len = P<float>(g("ep_len"));
+    a.wide = d.contains("wide") && d["wide"].cast<bool>();
     return a;
   });
   m.def("vec_host_tail", [](const VecHostTail& a, bool reset, uint64_t s) { vec_host_tail(a, reset, S(s)); },
@@ -1205,7 +1206,8 @@ PYBIND11_MODULE(_apex_hip, m) {
   });
   m.def("vec_rollout", [](const VecRollout& r, uint64_t s) { vec_rollout(r, S(s)); });
   py::class_<VecLearn>(m, "VecLearn");
-  m.def("make_vec_learn", [](const VecNet& on, const VecNet& tg, py::dict d) {
+  // (make_vec_learn and make_vecw_learn: the launchers check the shapes against their own limits)
+  auto make_learn = [](const VecNet& on, const VecNet& tg, py::dict d) {
     auto g = [&](const char* k) { return d[k].cast<uint64_t>(); };
     auto opt = [&](const char* k) { return d.contains(k) ? d[k].cast<uint64_t>() : (uint64_t)0; };
     VecLearn p{};
@@ -1221,7 +1223,8 @@ PYBIND11_MODULE(_apex_hip, m) {
     p.beta0 = d.contains("beta0") ? d["beta0"].cast<double>() : 0.4;
     p.beta_horizon = d.contains("beta_horizon") ? d["beta_horizon"].cast<double>() : 1000.0;
     return p;
-  });
+  };
+  m.def("make_vec_learn", make_learn);
   m.def("vec_learn", [](const VecLearn& p, uint64_t s) { vec_learn(p, S(s)); });
   m.def("vec_layout", []() {
     py::dict d;
@@ -1236,6 +1239,27 @@ PYBIND11_MODULE(_apex_hip, m) {
   m.def("vec_param_count", &vec_param_count);
   m.def("vec_grad_blocks", &vec_grad_blocks);
   m.def("vec_grad", [](const VecGrad& g, uint64_t s) { vec_grad(g, S(s)); });
+  // the wide (MFMA) path of the same net (vector_wide_kernels.hip): make_vecw_* build vec_act's / vec_learn's /
+  // vec_grad's handles, whose shapes the vecw launchers check against the wide limits
+  m.def("make_vecw_act", [](const VecNet& net, uint64_t ring, uint64_t hist, int E, uint64_t eps, uint64_t seed,
+                            uint64_t counter, uint64_t q, uint64_t actions) {
+    return VecAct{net, P<const float>(ring), P<const int>(hist), E, P<const float>(eps), seed,
+                  P<const int64_t>(counter), P<float>(q), P<int>(actions)};
+  });
+  m.def("vecw_act", [](const VecAct& a, uint64_t s) { vecw_act(a, S(s)); });
+  m.def("make_vecw_learn", make_learn);
+  m.def("vecw_learn", [](const VecLearn& p, uint64_t s) { vecw_learn(p, S(s)); });
+  m.def("vecw_layout", []() {
+    py::dict d;
+    d["X"] = vecw::X; d["F"] = vecw::F; d["DF"] = vecw::DF; d["H"] = vecw::H; d["DH"] = vecw::DH;
+    d["DA"] = vecw::DA; d["DV"] = vecw::DV; d["STRIDE"] = vecw::STRIDE;
+    return d;
+  });
+  m.def("make_vecw_grad", [](uint64_t vec, int B, int obs, int A, int64_t n, uint64_t grad, uint64_t part) {
+    return VecGrad{P<const float>(vec), B, obs, A, n, P<float>(grad), P<double>(part)};
+  });
+  m.def("vecw_grad_blocks", &vecw_grad_blocks);
+  m.def("vecw_grad", [](const VecGrad& g, uint64_t s) { vecw_grad(g, S(s)); });
 
   // ---- host gym-API envs (engine/host_env.py)
   py::class_<HostEnvTaps>(m, "HostEnvTaps").def_readonly("max_count", &HostEnvTaps::max_count);

@@ -881,6 +881,8 @@ void aql_apply_staged(const AqlInsert& src, const AqlInsert& dst, int E, int obs
 
 // ---- vector_kernels.hip (vector-observation Ape-X: classic-control envs, MLP dueling DQN)
 constexpr int kVecHidden = 128, kVecMaxObs = 8, kVecMaxA = 7;
+// the wide (MFMA) path of the same net, vector_wide_kernels.hip
+constexpr int kVecWideMaxObs = 128, kVecWideMaxA = 32;
 // the ten tensors of DuelingDQN.parameters() (MLP form), reference layouts
 struct VecNet {
   const float *w0, *b0;      // features.0   [128][obs], [128]
@@ -931,6 +933,7 @@ struct VecHostTail {
   float* ep_log;         // [E][4]
   float* ep_ret;         // [E] running return
   float* ep_len;         // [E] running length
+  bool wide;             // obs up to kVecWideMaxObs (the wide net's shard) instead of kVecMaxObs
 };
 void vec_host_tail(const VecHostTail& a, bool reset, hipStream_t s);
 // Q[E][A] of the observations at ring row hist[e][3] + select_actions_k's epsilon-greedy draw
@@ -1014,6 +1017,19 @@ struct VecGrad {
 int64_t vec_param_count(int obs, int A);
 int vec_grad_blocks(int64_t n);
 void vec_grad(const VecGrad& g, hipStream_t s);
+// ---- vector_wide_kernels.hip: the same net for obs <= kVecWideMaxObs, A <= kVecWideMaxA on fp32
+// MFMA, a workgroup per 32 rows.  vecw_act / vecw_learn take vec_act's / vec_learn's arguments
+// (vecw_act's draw is vec_act's arithmetic); vecw_learn writes its per-sample rows in the vecw
+// layout (offsets in floats): input at 128 slots, features, their gradient, both hidden layers,
+// their gradient, dL/dA at 32 slots, dL/dV.  vecw_grad contracts them over the batch, one
+// workgroup per 32x32 output tile (VecGrad::part holds vecw_grad_blocks(obs, A) partials).
+namespace vecw {
+constexpr int X = 0, F = 128, DF = 256, H = 384, DH = 640, DA = 896, DV = 928, STRIDE = 960;
+}
+void vecw_act(const VecAct& a, hipStream_t s);
+void vecw_learn(const VecLearn& p, hipStream_t s);
+int vecw_grad_blocks(int obs, int A);
+void vecw_grad(const VecGrad& g, hipStream_t s);
 // The actor side of one frame of the single-process prioritized DQN (reference DQN.py) in ONE
 // launch of one workgroup, E <= 8 envs: epsilon(t) / beta(t) in fp64, vec_act's forward and
 // draw on the online net, vec_classic_step's env step, frame_hist_step's FrameStack advance,

@@ -25,6 +25,10 @@ the loop is one step of all E host envs + ``--learner-steps`` SGD steps, overlap
 ``--host-serial``, and ``--eval-mode`` must be ``step`` (the host evaluator).  Same log tags,
 checkpoints and JSON log.  ``step`` mode there is the blocking ``VectorHostEngine.evaluate`` (a
 device synchronize, then whole episodes on a CPU copy of the net inside the training loop).
+``--wide`` (either kind of env) runs the acting forward and the learner through the fp32-MFMA
+kernels (``VectorEngineConfig.wide_net``): a host env may then have up to 128 observation floats
+and 32 actions.  It is refused with ``--eval-envs`` (that evaluator's act kernel is narrow only);
+the blocking evaluator and the reference-format checkpoints work as they are.
 ``--eval-envs N`` (with ``--eval-workers W``, ``--eval-kernel``) evaluates beside training instead:
 N (at most 64) greedy evaluator envs in W worker processes (:mod:`apex_amd.engine.vector_host_eval`),
 their weights refreshed whenever ``learn_steps`` crosses a multiple of ``--eval-interval``, the
@@ -57,6 +61,9 @@ class _Parser(argparse.ArgumentParser):
                 self.error("--host-envs evaluates on the host: --eval-mode must be 'step'")
             if a.learner_steps < 1:
                 self.error("--learner-steps must be >= 1")
+            if a.eval_envs and a.wide:
+                self.error("--wide with --eval-envs: the side-stream evaluator's act (vec_host_eval_act) is narrow "
+                           "only; evaluate a wide net with --eval-interval (the blocking host evaluator)")
             if a.eval_envs:
                 if not 0 < a.eval_envs <= 64:
                     self.error(f"--eval-envs {a.eval_envs}: the host-env evaluator runs 1..64 envs (0 = off)")
@@ -87,7 +94,10 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--env", default=d.env_id,
                    help=f"one of {sorted(VECTOR_ENVS)}; with --host-envs any envs.make id")
     p.add_argument("--host-envs", action="store_true",
-                   help="step gym-API envs on the CPU (flat observation <= 8, discrete actions <= 7)")
+                   help="step gym-API envs on the CPU (flat observation <= 8, discrete actions <= 7; 128 / 32 "
+                        "with --wide)")
+    p.add_argument("--wide", action="store_true",
+                   help="the fp32-MFMA kernels (vecw_*): flat observation <= 128, discrete actions <= 32")
     p.add_argument("--learner-steps", type=int, default=1, help="(--host-envs) SGD steps per env step")
     p.add_argument("--host-serial", action="store_true",
                    help="(--host-envs) learner steps, then the acting step: no overlap with the host's env step")
@@ -136,7 +146,8 @@ def config_from_args(a) -> VectorEngineConfig:
     return VectorEngineConfig(env_id=a.env, n_envs=a.envs, batch_size=a.batch_size, n_step=a.n_step, gamma=a.gamma,
                               lr=a.lr, replay_capacity=a.capacity, actor_steps_per_learner_step=a.actor_steps,
                               nstep_mode=a.nstep_mode, target_update_interval=a.target_update_interval,
-                              publish_param_interval=a.publish_interval, seed=a.seed).validate(not a.host_envs)
+                              publish_param_interval=a.publish_interval, seed=a.seed,
+                              wide_net=a.wide).validate(not a.host_envs)
 
 
 def _crossed(t: int, prev: int, interval: int) -> bool:
@@ -147,10 +158,11 @@ def _crossed(t: int, prev: int, interval: int) -> bool:
 def make_engine(a, cfg: VectorEngineConfig):
     if not a.host_envs:
         return VectorApexEngine(cfg, a.device)
-    from .engine.vector_host import VectorHostEngine
+    from .engine.vector_host import WIDE_MAX_OBS, VectorHostEngine
     from .envs.host_vector import HostVectorEnv
 
-    vec = HostVectorEnv(a.env, a.envs, seed=a.seed, max_episode_length=a.max_episode_length)
+    kw = dict(max_obs=WIDE_MAX_OBS) if a.wide else {}
+    vec = HostVectorEnv(a.env, a.envs, seed=a.seed, max_episode_length=a.max_episode_length, **kw)
     return VectorHostEngine(cfg, vec, a.device, learner_steps=a.learner_steps, host_overlap=not a.host_serial)
 
 
