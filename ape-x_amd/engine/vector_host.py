@@ -46,13 +46,15 @@ online net on a separate env), or beside training :mod:`apex_amd.engine.vector_h
 (evaluator envs in worker processes, ``vec_host_eval_act`` on a side stream, two weight sets, a
 pump that never waits; ``train_vector --host-envs --eval-envs N``).  ``rollout_evaluate`` and
 :class:`~apex_amd.engine.vector.VectorEvaluator` play device envs and are refused.  Out of scope:
-worker processes for the TRAINING envs, the central topology, and a wide side-stream evaluator.
+worker processes for the TRAINING envs and the central topology.
 
 Shapes: observations to 8 floats and 7 actions (``kVecMaxObs`` / ``kVecMaxA``) by default; with
 ``VectorEngineConfig.wide_net`` the acting forward and the learner are the MFMA kernels of
 ``ops/csrc/vector_wide_kernels.hip`` and the limits are 128 / 32 (``kVecWideMaxObs`` /
-``kVecWideMaxA``).  ``vec_host_eval_act`` is narrow only: a wide engine evaluates with the blocking
-:meth:`VectorHostEngine.evaluate`.
+``kVecWideMaxA``).  The side-stream evaluator follows the engine: over a wide engine its act is
+``vecw_host_eval_act`` (:mod:`apex_amd.engine.vector_host_eval`, through the API; ``train_vector
+--wide --eval-envs`` is still refused, the CLI's switch-over is a follow-up, so on the command line a
+wide engine evaluates with the blocking :meth:`VectorHostEngine.evaluate`).
 """
 from __future__ import annotations
 

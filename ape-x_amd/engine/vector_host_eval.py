@@ -22,6 +22,13 @@ where the act is, by ``kernel``:
              geometry, the observations straight from the staged ``reset_obs`` rows, the step
              ``k`` by value.  Bit-equal to the step form on ``q`` and ``actions``.
 
+An engine with ``cfg.wide_net`` (observations to 128 floats, 32 actions) gets the same two forms on
+the fp32-MFMA forward of ops/csrc/vector_wide_kernels.hip: ``"fused"`` is ``vecw_host_eval_act``
+(one launch, one workgroup per 32 envs), ``"step"`` is ``vec_host_tail`` with its wide observation
+limit -> ``frame_hist_step`` -> ``vecw_act``; everything else is shared.  :func:`make_pool` takes
+``wide=True`` to let the workers' envs have that many observation floats.  The command line does not
+reach this yet: ``train_vector --wide --eval-envs`` is still refused, its switch-over is a follow-up.
+
 Draw seed: ``(eval_seed(seed) & (2^48 - 1)) ^ ACT_XOR``.  Evaluator env ``j`` is seeded
 ``eval_seed(seed) + j``: the caller builds the vector env with ``seed=eval_seed(seed)``
 (:func:`make_pool` does).
@@ -50,13 +57,25 @@ from __future__ import annotations
 import numpy as np
 
 from ..envs.host_vector import staging_views
-from .aql_host_eval import MAX_ENVS, AQLHostEvaluation, _Ledger, make_pool
+from . import aql_host_eval as _aql
+from .aql_host_eval import MAX_ENVS, AQLHostEvaluation, _Ledger
 from .host_env import PinnedMirror
 from .host_eval import KERNELS, WeightSets, eval_seed
 
 __all__ = ["MAX_ENVS", "VectorHostEvaluation", "VectorHostEvaluator", "make_pool"]
 
 ACT_XOR = 0x5EC7   # the evaluator's action-draw seed = (eval_seed(seed) & (2^48 - 1)) ^ ACT_XOR
+
+
+def make_pool(env_id: str, n: int, workers: int, seed: int = 0, max_episode_length: int = 50000, wide: bool = False,
+              **kw):
+    """:func:`apex_amd.engine.aql_host_eval.make_pool`; ``wide``: the evaluator of a ``wide_net``
+    engine, whose envs may have up to 128 observation floats."""
+    if wide:
+        from .vector_host import WIDE_MAX_OBS
+
+        kw.setdefault("max_obs", WIDE_MAX_OBS)
+    return _aql.make_pool(env_id, n, workers, seed=seed, max_episode_length=max_episode_length, **kw)
 
 
 class VectorHostEvaluator:
@@ -72,9 +91,6 @@ class VectorHostEvaluator:
 
         if kernel not in KERNELS:
             raise ValueError(f"kernel must be one of {KERNELS}, got {kernel!r}")
-        if getattr(getattr(engine, "cfg", None), "wide_net", False):
-            raise ValueError("the vector host evaluator's act kernels (vec_host_eval_act, vec_act) are narrow only; "
-                             "a wide_net engine evaluates with the blocking VectorHostEngine.evaluate")
         N = len(vec)
         if not 1 <= N <= MAX_ENVS:
             raise ValueError(f"the vector host evaluator runs 1..{MAX_ENVS} envs, got {N}")
@@ -87,6 +103,7 @@ class VectorHostEvaluator:
         self.engine, self.vec, self.kernel = engine, vec, kernel
         self.device = dev = engine.device
         self.N, self.obs, self.A = N, engine.obs_dim, engine.A
+        self.wide = bool(getattr(getattr(engine, "cfg", None), "wide_net", False))   # the vecw_* act kernels
         self.seed = int(seed)
         self.sd = eval_seed(self.seed) & 0xFFFFFFFFFFFF
         self.act_seed = self.sd ^ ACT_XOR
@@ -152,21 +169,25 @@ class VectorHostEvaluator:
     def _bind(self) -> None:
         """The launch descriptors over the buffers as they are now (``q`` and ``actions`` are read
         here: a test re-seats them inside guarded buffers and binds again)."""
-        h, N = self.hip, self.N
+        h, N, w = self.hip, self.N, self.wide
         self._acts = self._tail = self._step_acts = None
         if self.kernel == "fused":
             d = dict(N=N, seed=self.act_seed, stage=self.stage_dev.data_ptr(), q=self.q.data_ptr(),
                      actions=self.actions.data_ptr())
-            self._acts = [h.make_vec_host_eval_act(net, d) for net in self.nets]
+            make = h.make_vecw_host_eval_act if w else h.make_vec_host_eval_act
+            self._acts = [make(net, d) for net in self.nets]
+            self._fused_act = h.vecw_host_eval_act if w else h.vec_host_eval_act
             return
         self._tail = h.make_vec_host_tail(dict(
             E=N, obs=self.obs, F=self.F, stage=self.stage_dev.data_ptr(), ring=self.ring.data_ptr(),
             step=self.counter.data_ptr(), reward=self.reward.data_ptr(), done=self.done.data_ptr(),
             new_frame=self.new_frame.data_ptr(), hist=self.hist.data_ptr(), ep_log=self.ep_log.data_ptr(),
-            ep_ret=self.ep_ret.data_ptr(), ep_len=self.ep_len.data_ptr()))
-        self._step_acts = [h.make_vec_act(net, self.ring.data_ptr(), self.hist.data_ptr(), N, self.eps.data_ptr(),
-                                          self.act_seed, self.counter.data_ptr(), self.q.data_ptr(),
-                                          self.actions.data_ptr()) for net in self.nets]
+            ep_ret=self.ep_ret.data_ptr(), ep_len=self.ep_len.data_ptr(), wide=w))
+        make = h.make_vecw_act if w else h.make_vec_act
+        self._step_acts = [make(net, self.ring.data_ptr(), self.hist.data_ptr(), N, self.eps.data_ptr(),
+                                self.act_seed, self.counter.data_ptr(), self.q.data_ptr(),
+                                self.actions.data_ptr()) for net in self.nets]
+        self._step_act = h.vecw_act if w else h.vec_act
 
     # ------------------------------------------------------------------ weights
     def refresh(self) -> bool:
@@ -186,13 +207,13 @@ class VectorHostEvaluator:
         s = st.cuda_stream
         i = self.weights.acquire(st)
         if self.kernel == "fused":
-            h.vec_host_eval_act(self._acts[i], self.k, s)
+            self._fused_act(self._acts[i], self.k, s)
         else:
             h.vec_host_tail(self._tail, self.k == 0, s)
             if self.k > 0:
                 h.frame_hist_step(self.hist.data_ptr(), self.new_frame.data_ptr(), self.done.data_ptr(), self.N,
                                   self.counter.data_ptr(), s)
-            h.vec_act(self._step_acts[i], s)
+            self._step_act(self._step_acts[i], s)
         self.weights.release()
         self.act_host.copy_(self.actions, non_blocking=True)
         self.acted.record()

@@ -45,7 +45,7 @@ from multiprocessing import shared_memory
 import numpy as np
 
 from . import proc_vector as _pv
-from .host_vector import HostVectorEnv, staging_views
+from .host_vector import MAX_OBS, HostVectorEnv, staging_views
 from .proc_vector import (_START_TIMEOUT, _THREAD_VARS, ProcRawAtariVector, _cleanup, _env_lock, _resolve,
                           bank_ranges)
 
@@ -59,7 +59,7 @@ def _block_views(buf, n: int, obs: int, adim: int):
 
 
 # ---------------------------------------------------------------------------- child
-def _worker_main(conn, w, e0, e1, env_id, seed, factory, max_episode_length):
+def _worker_main(conn, w, e0, e1, env_id, seed, factory, max_episode_length, max_obs=MAX_OBS):
     """One worker: build the bank's ``HostVectorEnv``, report its geometry, attach the shared block
     (the vector's five views move onto its rows), then serve reset / step until a stop message or
     the parent's end of the pipe closes."""
@@ -72,7 +72,7 @@ def _worker_main(conn, w, e0, e1, env_id, seed, factory, max_episode_length):
         try:
             make_fn = _resolve(factory)
             vec = HostVectorEnv([lambda: make_fn(env_id)] * (e1 - e0), seed=int(seed) + e0,
-                                max_episode_length=max_episode_length)
+                                max_episode_length=max_episode_length, max_obs=max_obs)
             conn.send(("ready", vec.obs_dim, vec.action_dim, vec.n_actions, vec.continuous,
                        tuple(float(x) for x in vec.low), tuple(float(x) for x in vec.high), vec.max_episode_steps))
         except BaseException:
@@ -120,8 +120,11 @@ def _worker_main(conn, w, e0, e1, env_id, seed, factory, max_episode_length):
 # ---------------------------------------------------------------------------- parent
 class ProcHostVectorEnv:
     def __init__(self, env_id: str, n: int, workers: int = 2, seed: int = 0, max_episode_length: int = 50000,
-                 factory: str | None = None, timeout: float = 60.0):
+                 factory: str | None = None, timeout: float = 60.0, max_obs: int = MAX_OBS):
+        """``max_obs``: ``HostVectorEnv``'s, handed to every worker's bank (the wide vector Ape-X net
+        passes 128)."""
         n, workers = int(n), int(workers)
+        self.max_obs = int(max_obs)
         self.banks = bank_ranges(n, workers)        # (ValueError before any process starts)
         if factory is not None and (":" not in factory or not all(factory.partition(":")[::2])):
             raise ValueError(f"factory must be 'module:function', got {factory!r}")
@@ -150,7 +153,7 @@ class ProcHostVectorEnv:
                     ours, theirs = ctx.Pipe(duplex=True)
                     p = ctx.Process(target=_worker_main, name=f"apex-host-env-worker-{w}", daemon=True,
                                     args=(theirs, w, e0, e1, self.env_id, self.seed, factory,
-                                          self.max_episode_length))
+                                          self.max_episode_length, self.max_obs))
                     p.start()
                     theirs.close()
                     self._procs.append(p)

@@ -1155,7 +1155,8 @@ PYBIND11_MODULE(_apex_hip, m) {
   py::class_<VecHostEvalAct>(m, "VecHostEvalAct");
   // d: N, seed, stage, q, actions (a missing pointer is null: the launcher throws); the step k is the launch's
   // argument
-  m.def("make_vec_host_eval_act", [](const VecNet& net, py::dict d) {
+  // (make_vec_host_eval_act and make_vecw_host_eval_act: the launchers check the net against their own limits)
+  auto make_eval_act = [](const VecNet& net, py::dict d) {
     auto opt = [&](const char* k) { return d.contains(k) ? d[k].cast<uint64_t>() : (uint64_t)0; };
     VecHostEvalAct a{};
     a.net = net;
@@ -1164,10 +1165,17 @@ PYBIND11_MODULE(_apex_hip, m) {
     a.stage = P<const float>(opt("stage"));
     a.q = P<float>(opt("q")); a.actions = P<int>(opt("actions"));
     return a;
-  });
+  };
+  m.def("make_vec_host_eval_act", make_eval_act);
   m.def("vec_host_eval_act", [](VecHostEvalAct a, int64_t k, uint64_t s) {
     a.k = k;
     vec_host_eval_act(a, S(s));
+  }, py::arg("a"), py::arg("k"), py::arg("s"));
+  // the same step of a wide_net engine in one launch (vector_wide_kernels.hip)
+  m.def("make_vecw_host_eval_act", make_eval_act);
+  m.def("vecw_host_eval_act", [](VecHostEvalAct a, int64_t k, uint64_t s) {
+    a.k = k;
+    vecw_host_eval_act(a, S(s));
   }, py::arg("a"), py::arg("k"), py::arg("s"));
   py::class_<DqnFrame>(m, "DqnFrame");
   // d: act_seed, hist, t, eps_start, eps_final, eps_decay, beta0, beta_horizon, eps_out, beta_out, q, actions,

@@ -1027,6 +1027,9 @@ namespace vecw {
 constexpr int X = 0, F = 128, DF = 256, H = 384, DH = 640, DA = 896, DV = 928, STRIDE = 960;
 }
 void vecw_act(const VecAct& a, hipStream_t s);
+// vec_host_eval_act on the wide forward (VecHostEvalAct as it is; N <= 64: one or two workgroups):
+// vecw_act's Q and draw at epsilon 0 on the staged reset_obs rows, the step k by value.
+void vecw_host_eval_act(const VecHostEvalAct& a, hipStream_t s);
 void vecw_learn(const VecLearn& p, hipStream_t s);
 int vecw_grad_blocks(int obs, int A);
 void vecw_grad(const VecGrad& g, hipStream_t s);

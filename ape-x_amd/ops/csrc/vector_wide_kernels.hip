@@ -25,7 +25,11 @@
 //                 combine with vec_forward's order (sum of A in index order, V + A_k - mean).
 //   vecw_act      one workgroup per 32 envs: ring row hist[e][3] -> forward -> q[E][A] and
 //                 vec_act_k's epsilon-greedy draw, arithmetic for arithmetic.
-//   vecw_learn    one workgroup per 32 sampled rows: target(s'), online(s'), online(s) last so its
+//   vecw_host_eval_act  vecw_act for the host-env evaluator (N <= 64 envs, one or two workgroups):
+//                 the observations straight from the staging block's reset_obs rows into the x
+//                 image, the step k by value as the Philox counter, epsilon 0.  One launch per
+//                 evaluator step; Q and the actions are vecw_act's bit for bit.
+//   vecw_learn   one workgroup per 32 sampled rows: target(s'), online(s'), online(s) last so its
 //                 x / f / h stay in LDS; dqn_loss_k's per-row loss; the backward on MFMA in the
 //                 same launch: dH = (dA . Wa2 | dV wv2) * relu', dF = (dHa . Wa1 + dHv . Wv1) * relu'.
 //                 These use the weights untransposed: the B operand is W[u][n] with the lanes along
@@ -245,6 +249,46 @@ __global__ __launch_bounds__(kT) void vecw_act_k(VecAct a) {
   }
 }
 
+// ------------------------------------------------------------------ greedy act over host envs
+// The act half of one evaluator step over HOST envs (engine/vector_host_eval.py), the wide
+// vec_host_eval_act_k: vecw_act_k with the observations read straight from the staging block's
+// reset_obs rows and the step k by value -- no ring, no hist, no counter in memory.  The live rows of
+// a workgroup are one contiguous span of the block (rows N + e0 .. N + e0 + live - 1 of [2 N][obs]),
+// so the x image is filled with no index read in front of the observation loads, a row's floats on
+// consecutive lanes; a padding row repeats env N - 1 out of that span's last row.  Same forward, same
+// draw at epsilon 0 (explore iff !(u0 > 0)): Q and the actions are vecw_act_k's bit for bit.
+__global__ __launch_bounds__(kT) void vecw_host_eval_act_k(VecHostEvalAct a) {
+  __shared__ WideLds L;
+  const int t = threadIdx.x;
+  const int e0 = blockIdx.x * kRows;
+  const int obs = a.net.obs, kp = (obs + 7) & ~7;
+  const int live = min(kRows, a.N - e0);   // >= 1: the grid is ceil(N / 32)
+  const float* src = a.stage + (size_t)(a.N + e0) * obs;
+  for (int i = t; i < kRows * kp; i += kT) {
+    const int r = i / kp, k = i - r * kp;
+    L.x[r * kPX + k] = k < obs ? src[min(r, live - 1) * obs + k] : 0.f;
+  }
+  vecw_forward(a.net, L);
+  const int e = e0 + t;
+  if (t < live) {
+    const int A = a.net.A;
+    const float* row = L.q + t * kPQ;
+    // vecw_act_k's draw at eps = 0: first argmax; explore iff !(u0 > 0); min(int(u1 A), A - 1)
+    int best = 0;
+    float bv = row[0];
+    for (int k = 1; k < A; ++k)
+      if (row[k] > bv) { bv = row[k]; best = k; }
+    for (int k = 0; k < A; ++k) a.q[(size_t)e * A + k] = row[k];
+    float u[4];
+    uniform4(a.seed, (uint64_t)e, (uint64_t)a.k, u);
+    if (!(u[0] > 0.f)) {
+      const int rr = (int)(u[1] * (float)A);
+      best = rr < A ? rr : A - 1;
+    }
+    a.actions[e] = best;
+  }
+}
+
 // ------------------------------------------------------------------ learner
 __global__ __launch_bounds__(kT) void vecw_learn_k(VecLearn p) {
   __shared__ WideLds L;
@@ -451,6 +495,16 @@ void vecw_act(const VecAct& a, hipStream_t s) {
   if (a.E < 1 || a.E > 4096 || !a.ring || !a.hist || !a.eps || !a.q || !a.actions)
     throw std::invalid_argument("vecw_act: 1 <= E <= 4096 with ring, hist, eps, q and actions");
   vecw_act_k<<<(a.E + kRows - 1) / kRows, kT, 0, s>>>(a);
+  LAUNCH_CHECK();
+}
+
+void vecw_host_eval_act(const VecHostEvalAct& a, hipStream_t s) {
+  check_wide_net(a.net, "vecw_host_eval_act");
+  if (a.N < 1 || a.N > 64) throw std::invalid_argument("vecw_host_eval_act: 1 <= N <= 64 evaluator envs");
+  if (a.k < 0) throw std::invalid_argument("vecw_host_eval_act: step k >= 0");
+  if (!a.stage) throw std::invalid_argument("vecw_host_eval_act: the staging block's device copy");
+  if (!a.q || !a.actions) throw std::invalid_argument("vecw_host_eval_act: q and actions");
+  vecw_host_eval_act_k<<<(a.N + kRows - 1) / kRows, kT, 0, s>>>(a);
   LAUNCH_CHECK();
 }
 

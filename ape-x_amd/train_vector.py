@@ -27,8 +27,9 @@ checkpoints and JSON log.  ``step`` mode there is the blocking ``VectorHostEngin
 device synchronize, then whole episodes on a CPU copy of the net inside the training loop).
 ``--wide`` (either kind of env) runs the acting forward and the learner through the fp32-MFMA
 kernels (``VectorEngineConfig.wide_net``): a host env may then have up to 128 observation floats
-and 32 actions.  It is refused with ``--eval-envs`` (that evaluator's act kernel is narrow only);
-the blocking evaluator and the reference-format checkpoints work as they are.
+and 32 actions.  It is still refused with ``--eval-envs``: the evaluator itself takes a wide engine
+(``vecw_host_eval_act``, :mod:`apex_amd.engine.vector_host_eval`), this command line's switch-over is
+a follow-up; the blocking evaluator and the reference-format checkpoints work as they are.
 ``--eval-envs N`` (with ``--eval-workers W``, ``--eval-kernel``) evaluates beside training instead:
 N (at most 64) greedy evaluator envs in W worker processes (:mod:`apex_amd.engine.vector_host_eval`),
 their weights refreshed whenever ``learn_steps`` crosses a multiple of ``--eval-interval``, the

@@ -16,6 +16,9 @@
                             crosses a multiple of ``--eval-interval``;
                   ``pool``  ``--eval-envs`` evaluator envs in ``--eval-workers`` processes, refreshed
                             at that cadence and pumped every iteration.
+``--wide OBSxA``  (both modes above) a ``wide_net`` engine on the synthetic env :func:`wide_env` of that
+                  shape instead of ``--env``: the acts are ``vecw_host_eval_act`` / ``vec_host_tail`` +
+                  ``frame_hist_step`` + ``vecw_act`` (profiles/vector_wide_eval.md).
 ``--mode ab``     runs ``--variants`` (``mode:flag=value,...`` items; see the profile) as child
                   processes, alternated, ``--repeat`` rounds: the form for A/Bs and their noise pairs.
 
@@ -28,6 +31,42 @@ import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def wide_env(env_id):
+    """``--wide OBSxA`` (profiles/vector_wide_eval.md): a seeded synthetic env of OBS observation floats
+    and A discrete actions (``env_id`` = ``wide-OBSxA``; also the worker pool's ``factory``): the state
+    rotates and decays, the action pushes one component, an episode lasts 200 steps."""
+    import numpy as np
+
+    from apex_amd.envs import spaces
+    from apex_amd.envs.core import Env
+
+    obs, A = map(int, env_id.rpartition("-")[2].split("x"))
+
+    class WideEnv(Env):
+        def __init__(self):
+            super().__init__()
+            big = np.full(obs, np.finfo(np.float32).max, dtype=np.float32)
+            self.observation_space, self.action_space = spaces.Box(-big, big, dtype=np.float32), spaces.Discrete(A)
+
+        def reset(self):
+            self.x, self.t = self.np_random.uniform(-0.1, 0.1, size=obs).astype(np.float32), 0
+            return self.x.copy()
+
+        def step(self, action):
+            self.x = np.roll(self.x, 1) * np.float32(0.9)
+            self.x[int(action) % obs] += np.float32(0.25)
+            self.t += 1
+            return self.x.copy(), float(int(action) == self.t % A), self.t >= 200, {}
+
+    return WideEnv()
+
+
+def _wide_vec(a, n, seed):
+    from apex_amd.envs.host_vector import HostVectorEnv
+
+    return HostVectorEnv([lambda: wide_env("wide-" + a.wide)] * n, seed=seed, max_obs=128)
 
 
 def _args(a, envs):
@@ -43,6 +82,14 @@ def _engine(a, envs):
     from apex_amd import train_vector
 
     ta = _args(a, envs)
+    if a.wide:   # (the CLI refuses --wide --eval-envs: the engine is built through the API)
+        import dataclasses
+
+        from apex_amd.engine.vector_host import VectorHostEngine
+
+        cfg = dataclasses.replace(train_vector.config_from_args(ta), env_id="wide-" + a.wide, wide_net=True)
+        return VectorHostEngine(cfg, _wide_vec(a, envs, a.seed), ta.device, learner_steps=a.k,
+                                eval_env=lambda: wide_env("wide-" + a.wide))
     return train_vector.make_engine(ta, train_vector.config_from_args(ta))
 
 
@@ -54,7 +101,8 @@ def mode_step(a):
     from apex_amd.envs.host_vector import HostVectorEnv
 
     eng = _engine(a, 4)
-    vec = HostVectorEnv(a.env, a.eval_envs, seed=eval_seed(a.seed))
+    vec = _wide_vec(a, a.eval_envs, eval_seed(a.seed)) if a.wide else HostVectorEnv(a.env, a.eval_envs,
+                                                                                    seed=eval_seed(a.seed))
     ev = VectorHostEvaluator(eng, vec, kernel=a.kernel, seed=a.seed)
     ev.run(3)   # reset + first steps: every kernel's first launch is behind us
     dev_us, enq_us = [], []
@@ -94,7 +142,11 @@ def mode_train(a):
         eng.fill()
         eng.capture()
         if a.eval == "pool":
-            pool = make_pool(a.env, a.eval_envs, a.eval_workers, seed=a.seed)
+            if a.wide:
+                pool = make_pool("wide-" + a.wide, a.eval_envs, a.eval_workers, seed=a.seed, wide=True,
+                                 factory="bench_vector_host_eval:wide_env")
+            else:
+                pool = make_pool(a.env, a.eval_envs, a.eval_workers, seed=a.seed)
             try:
                 drv = VectorHostEvaluation(VectorHostEvaluator(eng, pool, kernel=a.kernel, seed=a.seed), pool)
             except BaseException:
@@ -174,6 +226,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", required=True, choices=["step", "train", "ab"])
     ap.add_argument("--env", default="CartPole-v0")
+    ap.add_argument("--wide", default="", metavar="OBSxA",
+                    help="a wide_net engine on the synthetic env of that shape (wide_env) instead of --env")
     ap.add_argument("--kernel", choices=["fused", "step"], default="fused")
     ap.add_argument("--eval", choices=["none", "host", "pool"], default="pool")
     ap.add_argument("--eval-envs", type=int, default=8)
