@@ -33,7 +33,11 @@ Launch budget (kernel launches per step, all on the caller's stream, no host syn
 ``ops/csrc/vector_wide_kernels.hip`` (``vecw_act`` / ``vecw_learn`` / ``vecw_grad``: observations to
 128 floats, 32 actions, a workgroup per 32 rows); the narrow kernels stop at 8 / 7 and stay the
 default.  Evaluation (``evaluate``, ``vec_rollout``) keeps the narrow forward over the same
-parameter storage, so it is offered for the device envs only.
+parameter storage, so it is offered for the device envs only.  ``wide_dtype="bf16"`` (with
+``wide_net``) takes the same launches from ``ops/csrc/vector_wide_bf16_kernels.hip`` instead
+(``vecwb_act`` / ``vecwb_learn`` / ``vecwb_grad``): bf16 matrix-core operands rounded from the fp32
+master weights and activations inside the kernels, fp32 accumulation, everything else -- parameters,
+target net, optimizer, checkpoints -- fp32 as before.
 
 Serial actor-then-learner on one stream; overlap and multi-GPU topologies are the Atari
 engine's and are not offered here.  Envs other than ``VECTOR_ENVS`` -- any gym-API env with a
@@ -92,6 +96,17 @@ def load_state_dict(path: str, env_id: str | None = None, model: DuelingDQN | No
     return load_model(model if model is not None else make_model(env_id), path)
 
 
+WIDE_DTYPES = ("fp32", "bf16")
+
+
+def wide_kernel(hip, name: str, dtype: str = "fp32"):
+    """The wide launch ``name`` (``act``, ``learn``, ``grad``, ``host_eval_act``) of ``wide_dtype``
+    ``dtype``: ``vecw_<name>`` (fp32 MFMA) or ``vecwb_<name>`` (bf16 operands)."""
+    if dtype not in WIDE_DTYPES:
+        raise ValueError(f"wide_dtype must be one of {WIDE_DTYPES}, got {dtype!r}")
+    return getattr(hip, ("vecwb_" if dtype == "bf16" else "vecw_") + name)
+
+
 def vec_net(hip, model: DuelingDQN):
     """``VecNet`` handle over the parameters of ``model`` (their storage must stay put)."""
     sd = dict(model.named_parameters())
@@ -113,7 +128,7 @@ class VectorActorShard(NStepShard):
     def __init__(self, replay: HBMReplay, n_envs: int, env_id: str, n_step: int = 3, gamma: float = 0.99,
                  eps_base: float = 0.4, eps_alpha: float = 7.0, actor_offset: int = 0,
                  total_actors: int | None = None, seed: int = 0, mode: str = "reference",
-                 max_episode_steps: int | None = None, wide: bool = False):
+                 max_episode_steps: int | None = None, wide: bool = False, wide_dtype: str = "fp32"):
         self.env_id = env_id
         self.wide = bool(wide)   # act with vecw_act (the MFMA forward) instead of vec_act
         self.kind, self.obs_dim, n_actions, limit = env_spec(env_id)
@@ -122,6 +137,7 @@ class VectorActorShard(NStepShard):
             raise ValueError(f"replay frame_bytes must be 4 * obs_dim = {4 * self.obs_dim}")
         super().__init__(replay, n_envs, n_actions, n_step, gamma, eps_base, eps_alpha, actor_offset, total_actors,
                          seed, mode)
+        self._wide_act = wide_kernel(self.hip, "act", wide_dtype) if self.wide else None   # (vecwb_act for bf16)
         E = self.E
         self.layout = self.hip.vec_env_state_layout()
         self.env_state = torch.zeros(E, self.layout["STRIDE"], dtype=torch.float32, device=self.device)
@@ -153,7 +169,7 @@ class VectorActorShard(NStepShard):
         """Q of the current observations into ``self.q`` and the epsilon-greedy actions."""
         if self._act is None:
             raise RuntimeError("set_policy() first: acting needs the HIP forward's weights")
-        (self.hip.vecw_act if self.wide else self.hip.vec_act)(self._act, self._stream())
+        (self._wide_act or self.hip.vec_act)(self._act, self._stream())
 
     def env_step(self) -> None:
         self.hip.vec_classic_step(self.env, self.actions.data_ptr(), self.step_counter.data_ptr(),
@@ -200,6 +216,7 @@ class VectorEngineConfig:
     eps_alpha: float = 7.0
     fused_norm: bool = True          # grad-norm partials from the gradient launch (5 launches per SGD step)
     wide_net: bool = False           # the MFMA kernels (vecw_*): obs <= 128, A <= 32; same launch sequence
+    wide_dtype: str = "fp32"         # (wide_net) "bf16": bf16 matrix-core operands, fp32 accumulation (vecwb_*)
     seed: int = 0
 
     def validate(self, device_env: bool = True) -> "VectorEngineConfig":
@@ -219,6 +236,10 @@ class VectorEngineConfig:
             raise ValueError("replay_capacity must hold at least two actor steps")
         if self.actor_steps_per_learner_step < 1:
             raise ValueError("actor_steps_per_learner_step >= 1")
+        if self.wide_dtype not in WIDE_DTYPES:
+            raise ValueError(f"wide_dtype must be one of {WIDE_DTYPES}, got {self.wide_dtype!r}")
+        if self.wide_dtype != "fp32" and not self.wide_net:
+            raise ValueError("wide_dtype='bf16' is a mode of the wide kernels: set wide_net")
         return self
 
 
@@ -281,7 +302,8 @@ class MLPDQNLearner:
         self.ring = replay.frames.view(torch.float32)
         self.net = vec_net(h, self.model)
         self.tnet = vec_net(h, self.target)
-        self._learn, self._grad = (h.vecw_learn, h.vecw_grad) if wide else (h.vec_learn, h.vec_grad)
+        self._learn, self._grad = ((wide_kernel(h, "learn", cfg.wide_dtype), wide_kernel(h, "grad", cfg.wide_dtype))
+                                   if wide else (h.vec_learn, h.vec_grad))
         self.L = (h.make_vecw_learn if wide else h.make_vec_learn)(self.net, self.tnet, dict(
             replay.trans_ptrs(), ring=self.ring.data_ptr(), idx=self.idx.data_ptr(), w=self.w.data_ptr(), B=B,
             gamma_n=float(cfg.gamma ** cfg.n_step), q_s=self.q_s.data_ptr(), q_s2=self.q_s2.data_ptr(),
@@ -360,7 +382,7 @@ class VectorApexEngine(GreedyRollouts):
         self.actor_flat = self.actor_model.flatten_parameters()
         self.shard = VectorActorShard(self.replay, cfg.n_envs, cfg.env_id, cfg.n_step, cfg.gamma, cfg.eps_base,
                                       cfg.eps_alpha, seed=cfg.seed * 0x2545F491 + 0xAC7, mode=cfg.nstep_mode,
-                                      wide=cfg.wide_net)
+                                      wide=cfg.wide_net, wide_dtype=cfg.wide_dtype)
         self.shard.set_policy(self.actor_model)
         self.publish_params()
         self.learn_steps = 0

@@ -51,8 +51,10 @@ worker processes for the TRAINING envs and the central topology.
 Shapes: observations to 8 floats and 7 actions (``kVecMaxObs`` / ``kVecMaxA``) by default; with
 ``VectorEngineConfig.wide_net`` the acting forward and the learner are the MFMA kernels of
 ``ops/csrc/vector_wide_kernels.hip`` and the limits are 128 / 32 (``kVecWideMaxObs`` /
-``kVecWideMaxA``).  The side-stream evaluator follows the engine: over a wide engine its act is
-``vecw_host_eval_act`` (:mod:`apex_amd.engine.vector_host_eval`, through the API; ``train_vector
+``kVecWideMaxA``); ``wide_dtype="bf16"`` takes them from ``ops/csrc/vector_wide_bf16_kernels.hip``
+(``vecwb_*``: bf16 matrix-core operands, fp32 accumulation and master weights).  The side-stream
+evaluator follows the engine: over a wide engine its act is ``vecw_host_eval_act`` / ``vecwb_host_eval_act``
+(:mod:`apex_amd.engine.vector_host_eval`, through the API; ``train_vector
 --wide --eval-envs`` is still refused, the CLI's switch-over is a follow-up, so on the command line a
 wide engine evaluates with the blocking :meth:`VectorHostEngine.evaluate`).
 """
@@ -70,7 +72,7 @@ from .graphs import capture_graph
 from .hbm_replay import HBMReplay
 from .host_env import PinnedMirror
 from .shard import NStepShard
-from .vector import MLPDQNLearner, VectorEngineConfig, save_state_dict, vec_net
+from .vector import MLPDQNLearner, VectorEngineConfig, save_state_dict, vec_net, wide_kernel
 
 MAX_OBS = 8       # kVecMaxObs: the MLP kernels' widest observation
 MAX_ACTIONS = 7   # kVecMaxA: their widest action set
@@ -103,7 +105,7 @@ class VectorHostShard(NStepShard):
 
     def __init__(self, replay: HBMReplay, vec, n_step: int = 3, gamma: float = 0.99, eps_base: float = 0.4,
                  eps_alpha: float = 7.0, actor_offset: int = 0, total_actors: int | None = None, seed: int = 0,
-                 mode: str = "reference", wide: bool = False):
+                 mode: str = "reference", wide: bool = False, wide_dtype: str = "fp32"):
         self.vec = vec
         self.wide = bool(wide)   # act with vecw_act; the tail takes the wide observation limit
         self.obs_dim, n_actions, self.max_episode_steps = host_env_spec(vec, self.wide)
@@ -114,6 +116,7 @@ class VectorHostShard(NStepShard):
             raise ValueError(f"replay frame_bytes must be 4 * obs_dim = {4 * self.obs_dim}")
         super().__init__(replay, E, n_actions, n_step, gamma, eps_base, eps_alpha, actor_offset, total_actors, seed,
                          mode)
+        self._wide_act = wide_kernel(self.hip, "act", wide_dtype) if self.wide else None   # (vecwb_act for bf16)
         h, dev = self.hip, self.device
         self.ring = replay.frames.view(torch.float32)  # [F, obs_dim]
         self.ep_ret = torch.zeros(E, dtype=torch.float32, device=dev)
@@ -169,7 +172,7 @@ class VectorHostShard(NStepShard):
         """Q of the current observations into ``self.q`` and the epsilon-greedy actions."""
         if self._act is None:
             raise RuntimeError("set_policy() first: acting needs the HIP forward's weights")
-        (self.hip.vecw_act if self.wide else self.hip.vec_act)(self._act, self._stream())
+        (self._wide_act or self.hip.vec_act)(self._act, self._stream())
 
     def act_begin(self) -> None:
         """The acting forward, the actions on their way to the host, the event the host waits for."""
@@ -241,7 +244,8 @@ class VectorHostEngine:
         self.actor_model = DuelingDQN.from_shapes((self.obs_dim,), self.A).to(dev)
         self.actor_flat = self.actor_model.flatten_parameters()
         self.shard = VectorHostShard(self.replay, vec, cfg.n_step, cfg.gamma, cfg.eps_base, cfg.eps_alpha,
-                                     seed=cfg.seed * 0x2545F491 + 0xAC7, mode=cfg.nstep_mode, wide=cfg.wide_net)
+                                     seed=cfg.seed * 0x2545F491 + 0xAC7, mode=cfg.nstep_mode, wide=cfg.wide_net,
+                                     wide_dtype=cfg.wide_dtype)
         self.shard._enqueued = lambda: self._enqueued()
         self.shard.set_policy(self.actor_model)
         self.publish_params()

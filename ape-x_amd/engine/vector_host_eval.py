@@ -25,7 +25,9 @@ where the act is, by ``kernel``:
 An engine with ``cfg.wide_net`` (observations to 128 floats, 32 actions) gets the same two forms on
 the fp32-MFMA forward of ops/csrc/vector_wide_kernels.hip: ``"fused"`` is ``vecw_host_eval_act``
 (one launch, one workgroup per 32 envs), ``"step"`` is ``vec_host_tail`` with its wide observation
-limit -> ``frame_hist_step`` -> ``vecw_act``; everything else is shared.  :func:`make_pool` takes
+limit -> ``frame_hist_step`` -> ``vecw_act``; everything else is shared.  With ``cfg.wide_dtype ==
+"bf16"`` the two acts are ``vecwb_host_eval_act`` / ``vecwb_act`` (ops/csrc/vector_wide_bf16_kernels.hip)
+over the same descriptors.  :func:`make_pool` takes
 ``wide=True`` to let the workers' envs have that many observation floats.  The command line does not
 reach this yet: ``train_vector --wide --eval-envs`` is still refused, its switch-over is a follow-up.
 
@@ -104,6 +106,7 @@ class VectorHostEvaluator:
         self.device = dev = engine.device
         self.N, self.obs, self.A = N, engine.obs_dim, engine.A
         self.wide = bool(getattr(getattr(engine, "cfg", None), "wide_net", False))   # the vecw_* act kernels
+        self.wide_dtype = getattr(getattr(engine, "cfg", None), "wide_dtype", "fp32")     # "bf16": the vecwb_* ones
         self.seed = int(seed)
         self.sd = eval_seed(self.seed) & 0xFFFFFFFFFFFF
         self.act_seed = self.sd ^ ACT_XOR
@@ -169,6 +172,8 @@ class VectorHostEvaluator:
     def _bind(self) -> None:
         """The launch descriptors over the buffers as they are now (``q`` and ``actions`` are read
         here: a test re-seats them inside guarded buffers and binds again)."""
+        from .vector import wide_kernel
+
         h, N, w = self.hip, self.N, self.wide
         self._acts = self._tail = self._step_acts = None
         if self.kernel == "fused":
@@ -176,7 +181,7 @@ class VectorHostEvaluator:
                      actions=self.actions.data_ptr())
             make = h.make_vecw_host_eval_act if w else h.make_vec_host_eval_act
             self._acts = [make(net, d) for net in self.nets]
-            self._fused_act = h.vecw_host_eval_act if w else h.vec_host_eval_act
+            self._fused_act = wide_kernel(h, "host_eval_act", self.wide_dtype) if w else h.vec_host_eval_act
             return
         self._tail = h.make_vec_host_tail(dict(
             E=N, obs=self.obs, F=self.F, stage=self.stage_dev.data_ptr(), ring=self.ring.data_ptr(),
@@ -187,7 +192,7 @@ class VectorHostEvaluator:
         self._step_acts = [make(net, self.ring.data_ptr(), self.hist.data_ptr(), N, self.eps.data_ptr(),
                                 self.act_seed, self.counter.data_ptr(), self.q.data_ptr(),
                                 self.actions.data_ptr()) for net in self.nets]
-        self._step_act = h.vecw_act if w else h.vec_act
+        self._step_act = wide_kernel(h, "act", self.wide_dtype) if w else h.vec_act
 
     # ------------------------------------------------------------------ weights
     def refresh(self) -> bool:

@@ -56,6 +56,7 @@ HIP_SOURCES = [
     "ipc_kernels.hip",
     "vector_kernels.hip",
     "vector_wide_kernels.hip",
+    "vector_wide_bf16_kernels.hip",
     "vector_host_kernels.hip",
     "host_env_kernels.hip",
     "host_eval_kernels.hip",
@@ -183,6 +184,7 @@ HIP_FLAGS = [
 # (v_pk_add/mul/fma_f32): their epilogues and reductions stay on the scalar fp32 forms.
 EXTRA_HIP_FLAGS = {
     "vector_wide_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "vector_wide_bf16_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

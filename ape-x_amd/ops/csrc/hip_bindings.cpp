@@ -1268,6 +1268,15 @@ PYBIND11_MODULE(_apex_hip, m) {
   });
   m.def("vecw_grad_blocks", &vecw_grad_blocks);
   m.def("vecw_grad", [](const VecGrad& g, uint64_t s) { vecw_grad(g, S(s)); });
+  // the same four launches with bf16 matrix-core operands (vector_wide_bf16_kernels.hip) over the make_vecw_*
+  // handles
+  m.def("vecwb_act", [](const VecAct& a, uint64_t s) { vecwb_act(a, S(s)); });
+  m.def("vecwb_host_eval_act", [](VecHostEvalAct a, int64_t k, uint64_t s) {
+    a.k = k;
+    vecwb_host_eval_act(a, S(s));
+  }, py::arg("a"), py::arg("k"), py::arg("s"));
+  m.def("vecwb_learn", [](const VecLearn& p, uint64_t s) { vecwb_learn(p, S(s)); });
+  m.def("vecwb_grad", [](const VecGrad& g, uint64_t s) { vecwb_grad(g, S(s)); });
 
   // ---- host gym-API envs (engine/host_env.py)
   py::class_<HostEnvTaps>(m, "HostEnvTaps").def_readonly("max_count", &HostEnvTaps::max_count);

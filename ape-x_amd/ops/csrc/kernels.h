@@ -1033,6 +1033,13 @@ void vecw_host_eval_act(const VecHostEvalAct& a, hipStream_t s);
 void vecw_learn(const VecLearn& p, hipStream_t s);
 int vecw_grad_blocks(int obs, int A);
 void vecw_grad(const VecGrad& g, hipStream_t s);
+// ---- vector_wide_bf16_kernels.hip: the four wide kernels with bf16 matrix-core operands
+// (v_mfma_f32_32x32x16_bf16, fp32 accumulation; every operand rounded to nearest even where it becomes
+// one, everything else fp32).  Same descriptors, limits, vecw row layout and vecw_grad_blocks tiles.
+void vecwb_act(const VecAct& a, hipStream_t s);
+void vecwb_host_eval_act(const VecHostEvalAct& a, hipStream_t s);
+void vecwb_learn(const VecLearn& p, hipStream_t s);
+void vecwb_grad(const VecGrad& g, hipStream_t s);
 // The actor side of one frame of the single-process prioritized DQN (reference DQN.py) in ONE
 // launch of one workgroup, E <= 8 envs: epsilon(t) / beta(t) in fp64, vec_act's forward and
 // draw on the online net, vec_classic_step's env step, frame_hist_step's FrameStack advance,

@@ -27,7 +27,8 @@ checkpoints and JSON log.  ``step`` mode there is the blocking ``VectorHostEngin
 device synchronize, then whole episodes on a CPU copy of the net inside the training loop).
 ``--wide`` (either kind of env) runs the acting forward and the learner through the fp32-MFMA
 kernels (``VectorEngineConfig.wide_net``): a host env may then have up to 128 observation floats
-and 32 actions.  It is still refused with ``--eval-envs``: the evaluator itself takes a wide engine
+and 32 actions; ``--wide --dtype bf16`` takes their bf16-operand variants (``wide_dtype``: bf16
+matrix-core operands, fp32 accumulation, fp32 master weights and checkpoints).  ``--wide`` is still refused with ``--eval-envs``: the evaluator itself takes a wide engine
 (``vecw_host_eval_act``, :mod:`apex_amd.engine.vector_host_eval`), this command line's switch-over is
 a follow-up; the blocking evaluator and the reference-format checkpoints work as they are.
 ``--eval-envs N`` (with ``--eval-workers W``, ``--eval-kernel``) evaluates beside training instead:
@@ -57,6 +58,8 @@ class _Parser(argparse.ArgumentParser):
 
     def parse_args(self, args=None, namespace=None):
         a = super().parse_args(args, namespace)
+        if a.dtype != "fp32" and not a.wide:
+            self.error("--dtype bf16 is a mode of the wide kernels: pass --wide")
         if a.host_envs:
             if a.eval_mode != "step":
                 self.error("--host-envs evaluates on the host: --eval-mode must be 'step'")
@@ -99,6 +102,8 @@ def parser() -> argparse.ArgumentParser:
                         "with --wide)")
     p.add_argument("--wide", action="store_true",
                    help="the fp32-MFMA kernels (vecw_*): flat observation <= 128, discrete actions <= 32")
+    p.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"],
+                   help="(--wide) bf16: bf16 matrix-core operands, fp32 accumulation and master weights (vecwb_*)")
     p.add_argument("--learner-steps", type=int, default=1, help="(--host-envs) SGD steps per env step")
     p.add_argument("--host-serial", action="store_true",
                    help="(--host-envs) learner steps, then the acting step: no overlap with the host's env step")
@@ -148,7 +153,7 @@ def config_from_args(a) -> VectorEngineConfig:
                               lr=a.lr, replay_capacity=a.capacity, actor_steps_per_learner_step=a.actor_steps,
                               nstep_mode=a.nstep_mode, target_update_interval=a.target_update_interval,
                               publish_param_interval=a.publish_interval, seed=a.seed,
-                              wide_net=a.wide).validate(not a.host_envs)
+                              wide_net=a.wide, wide_dtype=a.dtype).validate(not a.host_envs)
 
 
 def _crossed(t: int, prev: int, interval: int) -> bool:
