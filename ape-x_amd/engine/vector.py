@@ -37,7 +37,10 @@ parameter storage, so it is offered for the device envs only.  ``wide_dtype="bf1
 ``wide_net``) takes the same launches from ``ops/csrc/vector_wide_bf16_kernels.hip`` instead
 (``vecwb_act`` / ``vecwb_learn`` / ``vecwb_grad``): bf16 matrix-core operands rounded from the fp32
 master weights and activations inside the kernels, fp32 accumulation, everything else -- parameters,
-target net, optimizer, checkpoints -- fp32 as before.
+target net, optimizer, checkpoints -- fp32 as before.  ``tall_obs=True`` (with ``wide_net``, fp32 only)
+takes them from ``ops/csrc/vector_tall_kernels.hip`` (``vect_act`` / ``vect_learn`` / ``vect_grad``):
+observations to 1024 floats, ``features.0`` streamed through a double-buffered LDS slab, its weight
+gradient contracted against the observations in the ring (no copy in the per-sample rows).
 
 Serial actor-then-learner on one stream; overlap and multi-GPU topologies are the Atari
 engine's and are not offered here.  Envs other than ``VECTOR_ENVS`` -- any gym-API env with a
@@ -99,12 +102,15 @@ def load_state_dict(path: str, env_id: str | None = None, model: DuelingDQN | No
 WIDE_DTYPES = ("fp32", "bf16")
 
 
-def wide_kernel(hip, name: str, dtype: str = "fp32"):
+def wide_kernel(hip, name: str, dtype: str = "fp32", tall: bool = False):
     """The wide launch ``name`` (``act``, ``learn``, ``grad``, ``host_eval_act``) of ``wide_dtype``
-    ``dtype``: ``vecw_<name>`` (fp32 MFMA) or ``vecwb_<name>`` (bf16 operands)."""
+    ``dtype``: ``vecw_<name>`` (fp32 MFMA) or ``vecwb_<name>`` (bf16 operands); ``tall``:
+    ``vect_<name>`` (fp32 MFMA, observations to 1024 floats)."""
     if dtype not in WIDE_DTYPES:
         raise ValueError(f"wide_dtype must be one of {WIDE_DTYPES}, got {dtype!r}")
-    return getattr(hip, ("vecwb_" if dtype == "bf16" else "vecw_") + name)
+    if tall and dtype != "fp32":
+        raise ValueError("the tall kernels are fp32: a bf16 tall mode is out of scope")
+    return getattr(hip, ("vect_" if tall else "vecwb_" if dtype == "bf16" else "vecw_") + name)
 
 
 def vec_net(hip, model: DuelingDQN):
@@ -128,7 +134,8 @@ class VectorActorShard(NStepShard):
     def __init__(self, replay: HBMReplay, n_envs: int, env_id: str, n_step: int = 3, gamma: float = 0.99,
                  eps_base: float = 0.4, eps_alpha: float = 7.0, actor_offset: int = 0,
                  total_actors: int | None = None, seed: int = 0, mode: str = "reference",
-                 max_episode_steps: int | None = None, wide: bool = False, wide_dtype: str = "fp32"):
+                 max_episode_steps: int | None = None, wide: bool = False, wide_dtype: str = "fp32",
+                 tall: bool = False):
         self.env_id = env_id
         self.wide = bool(wide)   # act with vecw_act (the MFMA forward) instead of vec_act
         self.kind, self.obs_dim, n_actions, limit = env_spec(env_id)
@@ -137,7 +144,8 @@ class VectorActorShard(NStepShard):
             raise ValueError(f"replay frame_bytes must be 4 * obs_dim = {4 * self.obs_dim}")
         super().__init__(replay, n_envs, n_actions, n_step, gamma, eps_base, eps_alpha, actor_offset, total_actors,
                          seed, mode)
-        self._wide_act = wide_kernel(self.hip, "act", wide_dtype) if self.wide else None   # (vecwb_act for bf16)
+        # (vecwb_act for bf16, vect_act for tall)
+        self._wide_act = wide_kernel(self.hip, "act", wide_dtype, tall) if self.wide else None
         E = self.E
         self.layout = self.hip.vec_env_state_layout()
         self.env_state = torch.zeros(E, self.layout["STRIDE"], dtype=torch.float32, device=self.device)
@@ -217,6 +225,7 @@ class VectorEngineConfig:
     fused_norm: bool = True          # grad-norm partials from the gradient launch (5 launches per SGD step)
     wide_net: bool = False           # the MFMA kernels (vecw_*): obs <= 128, A <= 32; same launch sequence
     wide_dtype: str = "fp32"         # (wide_net) "bf16": bf16 matrix-core operands, fp32 accumulation (vecwb_*)
+    tall_obs: bool = False           # (wide_net, fp32) the streamed kernels (vect_*): obs <= 1024
     seed: int = 0
 
     def validate(self, device_env: bool = True) -> "VectorEngineConfig":
@@ -240,6 +249,10 @@ class VectorEngineConfig:
             raise ValueError(f"wide_dtype must be one of {WIDE_DTYPES}, got {self.wide_dtype!r}")
         if self.wide_dtype != "fp32" and not self.wide_net:
             raise ValueError("wide_dtype='bf16' is a mode of the wide kernels: set wide_net")
+        if self.tall_obs and not self.wide_net:
+            raise ValueError("tall_obs is a mode of the wide kernels: set wide_net")
+        if self.tall_obs and self.wide_dtype != "fp32":
+            raise ValueError("tall_obs takes wide_dtype='fp32': a bf16 tall mode is out of scope")
         return self
 
 
@@ -285,7 +298,7 @@ class MLPDQNLearner:
         self.q_s = torch.zeros(B, A, **f32)
         self.q_s2 = torch.zeros(B, A, **f32)
         self.qt_s2 = torch.zeros(B, A, **f32)
-        wide = bool(cfg.wide_net)
+        wide, tall = bool(cfg.wide_net), bool(cfg.tall_obs)
         self.lay = h.vecw_layout() if wide else h.vec_layout()
         self.vec = torch.zeros(B, self.lay["STRIDE"], **f32)
         self.delta = torch.zeros(B, **f32)
@@ -296,13 +309,15 @@ class MLPDQNLearner:
         self.step_counter = torch.zeros(1, dtype=torch.int64, device=dev)
         # PER beta, annealed on the device: vec_learn writes beta_by_frame(step + 1) for the next draw
         self.beta = torch.full((1,), float(cfg.beta), **f32)
-        self.nblk = h.vecw_grad_blocks(self.obs_dim, A) if wide else h.vec_grad_blocks(self.P)
+        self.nblk = ((h.vect_grad_blocks if tall else h.vecw_grad_blocks)(self.obs_dim, A) if wide
+                     else h.vec_grad_blocks(self.P))
         self.part = torch.zeros(self.nblk, dtype=torch.float64, device=dev)
         self.partials = torch.zeros(h.grad_norm_partials(), dtype=torch.float64, device=dev)
         self.ring = replay.frames.view(torch.float32)
         self.net = vec_net(h, self.model)
         self.tnet = vec_net(h, self.target)
-        self._learn, self._grad = ((wide_kernel(h, "learn", cfg.wide_dtype), wide_kernel(h, "grad", cfg.wide_dtype))
+        self._learn, self._grad = ((wide_kernel(h, "learn", cfg.wide_dtype, tall),
+                                    wide_kernel(h, "grad", cfg.wide_dtype, tall))
                                    if wide else (h.vec_learn, h.vec_grad))
         self.L = (h.make_vecw_learn if wide else h.make_vec_learn)(self.net, self.tnet, dict(
             replay.trans_ptrs(), ring=self.ring.data_ptr(), idx=self.idx.data_ptr(), w=self.w.data_ptr(), B=B,
@@ -310,8 +325,11 @@ class MLPDQNLearner:
             qt_s2=self.qt_s2.data_ptr(), vec=self.vec.data_ptr(), delta=self.delta.data_ptr(),
             lw=self.lw.data_ptr(), step=self.step_counter.data_ptr(), beta_out=self.beta.data_ptr(),
             beta0=float(cfg.beta), beta_horizon=float(cfg.beta_horizon)))
-        self.G = (h.make_vecw_grad if wide else h.make_vec_grad)(
-            self.vec.data_ptr(), B, self.obs_dim, A, self.P, self.flat_grad.data_ptr(), self.part.data_ptr())
+        g = (self.vec.data_ptr(), B, self.obs_dim, A, self.P, self.flat_grad.data_ptr(), self.part.data_ptr())
+        if tall:   # dW0 reads the sampled observations where they lie: the ring, through the ids of s
+            self.G = h.make_vect_grad(*g, self.ring.data_ptr(), replay.trans_ptrs()["s_ids"], self.idx.data_ptr())
+        else:
+            self.G = (h.make_vecw_grad if wide else h.make_vec_grad)(*g)
 
     @staticmethod
     def _stream() -> int:
@@ -382,7 +400,7 @@ class VectorApexEngine(GreedyRollouts):
         self.actor_flat = self.actor_model.flatten_parameters()
         self.shard = VectorActorShard(self.replay, cfg.n_envs, cfg.env_id, cfg.n_step, cfg.gamma, cfg.eps_base,
                                       cfg.eps_alpha, seed=cfg.seed * 0x2545F491 + 0xAC7, mode=cfg.nstep_mode,
-                                      wide=cfg.wide_net, wide_dtype=cfg.wide_dtype)
+                                      wide=cfg.wide_net, wide_dtype=cfg.wide_dtype, tall=cfg.tall_obs)
         self.shard.set_policy(self.actor_model)
         self.publish_params()
         self.learn_steps = 0

@@ -52,7 +52,9 @@ Shapes: observations to 8 floats and 7 actions (``kVecMaxObs`` / ``kVecMaxA``) b
 ``VectorEngineConfig.wide_net`` the acting forward and the learner are the MFMA kernels of
 ``ops/csrc/vector_wide_kernels.hip`` and the limits are 128 / 32 (``kVecWideMaxObs`` /
 ``kVecWideMaxA``); ``wide_dtype="bf16"`` takes them from ``ops/csrc/vector_wide_bf16_kernels.hip``
-(``vecwb_*``: bf16 matrix-core operands, fp32 accumulation and master weights).  The side-stream
+(``vecwb_*``: bf16 matrix-core operands, fp32 accumulation and master weights); ``tall_obs`` (with
+``wide_net``, fp32) raises the observation limit to 1024 (``kVecTallMaxObs``) on the streamed kernels of
+``ops/csrc/vector_tall_kernels.hip`` (``vect_*``).  The side-stream
 evaluator follows the engine: over a wide engine its act is ``vecw_host_eval_act`` / ``vecwb_host_eval_act``
 (:mod:`apex_amd.engine.vector_host_eval`, through the API; ``train_vector
 --wide --eval-envs`` is still refused, the CLI's switch-over is a follow-up, so on the command line a
@@ -78,19 +80,26 @@ MAX_OBS = 8       # kVecMaxObs: the MLP kernels' widest observation
 MAX_ACTIONS = 7   # kVecMaxA: their widest action set
 WIDE_MAX_OBS = 128      # kVecWideMaxObs: the wide (MFMA) kernels' widest observation
 WIDE_MAX_ACTIONS = 32   # kVecWideMaxA: their widest action set
+TALL_MAX_OBS = 1024     # kVecTallMaxObs: the tall (streamed) mode of the wide kernels
 
 
-def host_env_spec(vec, wide: bool = False) -> tuple[int, int, int | None]:
+def host_env_spec(vec, wide: bool = False, tall: bool = False) -> tuple[int, int, int | None]:
     """``(obs_dim, n_actions, max_episode_steps)`` of a vector env the MLP kernels can play
     (``max_episode_steps``: its registered TimeLimit, None if it has none); ``wide``: the limits
-    of the wide kernels (``VectorEngineConfig.wide_net``).  No GPU needed."""
+    of the wide kernels (``VectorEngineConfig.wide_net``); ``tall`` (with ``wide``): their tall mode's
+    observation limit (``tall_obs``).  No GPU needed."""
+    if tall and not wide:
+        raise ValueError("tall is a mode of the wide kernels: pass wide=True")
     if getattr(vec, "continuous", False):
         raise ValueError("the vector Ape-X engine takes a discrete action space; a continuous (Box) one is AQL's "
                          "(engine/aql_host.py)")
     obs, n_actions = int(vec.obs_dim), int(vec.n_actions)
     max_obs, max_a, tag = (WIDE_MAX_OBS, WIDE_MAX_ACTIONS, "kVecWideMax") if wide else (MAX_OBS, MAX_ACTIONS, "kVecMax")
+    if tall:
+        max_obs = TALL_MAX_OBS
     if not 1 <= obs <= max_obs:
-        raise ValueError(f"observation dim {obs} is outside the MLP kernels' limit of {max_obs} ({tag}Obs)")
+        raise ValueError(f"observation dim {obs} is outside the MLP kernels' limit of {max_obs} "
+                         f"({'kVecTallMax' if tall else tag}Obs)")
     if not 1 <= n_actions <= max_a:
         raise ValueError(f"{n_actions} actions are outside the MLP kernels' limit of {max_a} ({tag}A)")
     lim = getattr(vec, "max_episode_steps", None)
@@ -105,10 +114,11 @@ class VectorHostShard(NStepShard):
 
     def __init__(self, replay: HBMReplay, vec, n_step: int = 3, gamma: float = 0.99, eps_base: float = 0.4,
                  eps_alpha: float = 7.0, actor_offset: int = 0, total_actors: int | None = None, seed: int = 0,
-                 mode: str = "reference", wide: bool = False, wide_dtype: str = "fp32"):
+                 mode: str = "reference", wide: bool = False, wide_dtype: str = "fp32", tall: bool = False):
         self.vec = vec
         self.wide = bool(wide)   # act with vecw_act; the tail takes the wide observation limit
-        self.obs_dim, n_actions, self.max_episode_steps = host_env_spec(vec, self.wide)
+        self.tall = bool(tall)   # (wide) act with vect_act; the tail takes the tall observation limit
+        self.obs_dim, n_actions, self.max_episode_steps = host_env_spec(vec, self.wide, self.tall)
         E = len(vec)
         if not 1 <= E <= 4096:
             raise ValueError("VectorHostShard: 1 <= envs <= 4096 (the actor step's one-launch tree write)")
@@ -116,7 +126,8 @@ class VectorHostShard(NStepShard):
             raise ValueError(f"replay frame_bytes must be 4 * obs_dim = {4 * self.obs_dim}")
         super().__init__(replay, E, n_actions, n_step, gamma, eps_base, eps_alpha, actor_offset, total_actors, seed,
                          mode)
-        self._wide_act = wide_kernel(self.hip, "act", wide_dtype) if self.wide else None   # (vecwb_act for bf16)
+        # (vecwb_act for bf16, vect_act for tall)
+        self._wide_act = wide_kernel(self.hip, "act", wide_dtype, self.tall) if self.wide else None
         h, dev = self.hip, self.device
         self.ring = replay.frames.view(torch.float32)  # [F, obs_dim]
         self.ep_ret = torch.zeros(E, dtype=torch.float32, device=dev)
@@ -138,7 +149,7 @@ class VectorHostShard(NStepShard):
             ring=self.ring.data_ptr(), step=self.step_counter.data_ptr(), reward=self.reward.data_ptr(),
             done=self.done.data_ptr(), new_frame=self.new_frame.data_ptr(), hist=self.st["hist"].data_ptr(),
             ep_log=self.ep_log.data_ptr(), ep_ret=self.ep_ret.data_ptr(), ep_len=self.ep_len.data_ptr(),
-            wide=self.wide))
+            wide=self.wide, tall=self.tall))
         self._act = None
         self.env_steps = 0    # host env steps taken (all envs)
         self.host_seconds = 0.0   # wall time inside vec.step
@@ -228,7 +239,7 @@ class VectorHostEngine:
         if cfg.actor_steps_per_learner_step != 1:
             raise ValueError("a host-env engine takes one env step per iteration: set learner_steps, not "
                              "actor_steps_per_learner_step")
-        self.obs_dim, self.A, self.limit = host_env_spec(vec, cfg.wide_net)
+        self.obs_dim, self.A, self.limit = host_env_spec(vec, cfg.wide_net, cfg.tall_obs)
         self.cfg = cfg = dataclasses.replace(cfg, n_envs=len(vec)).validate(device_env=False)
         self.vec = vec
         self.K = int(learner_steps)
@@ -245,7 +256,7 @@ class VectorHostEngine:
         self.actor_flat = self.actor_model.flatten_parameters()
         self.shard = VectorHostShard(self.replay, vec, cfg.n_step, cfg.gamma, cfg.eps_base, cfg.eps_alpha,
                                      seed=cfg.seed * 0x2545F491 + 0xAC7, mode=cfg.nstep_mode, wide=cfg.wide_net,
-                                     wide_dtype=cfg.wide_dtype)
+                                     wide_dtype=cfg.wide_dtype, tall=cfg.tall_obs)
         self.shard._enqueued = lambda: self._enqueued()
         self.shard.set_policy(self.actor_model)
         self.publish_params()

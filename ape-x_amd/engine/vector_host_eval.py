@@ -27,7 +27,8 @@ the fp32-MFMA forward of ops/csrc/vector_wide_kernels.hip: ``"fused"`` is ``vecw
 (one launch, one workgroup per 32 envs), ``"step"`` is ``vec_host_tail`` with its wide observation
 limit -> ``frame_hist_step`` -> ``vecw_act``; everything else is shared.  With ``cfg.wide_dtype ==
 "bf16"`` the two acts are ``vecwb_host_eval_act`` / ``vecwb_act`` (ops/csrc/vector_wide_bf16_kernels.hip)
-over the same descriptors.  :func:`make_pool` takes
+over the same descriptors, with ``cfg.tall_obs`` (observations to 1024 floats) ``vect_host_eval_act`` /
+``vect_act`` (ops/csrc/vector_tall_kernels.hip).  :func:`make_pool` takes
 ``wide=True`` to let the workers' envs have that many observation floats.  The command line does not
 reach this yet: ``train_vector --wide --eval-envs`` is still refused, its switch-over is a follow-up.
 
@@ -70,13 +71,15 @@ ACT_XOR = 0x5EC7   # the evaluator's action-draw seed = (eval_seed(seed) & (2^48
 
 
 def make_pool(env_id: str, n: int, workers: int, seed: int = 0, max_episode_length: int = 50000, wide: bool = False,
-              **kw):
+              tall: bool = False, **kw):
     """:func:`apex_amd.engine.aql_host_eval.make_pool`; ``wide``: the evaluator of a ``wide_net``
-    engine, whose envs may have up to 128 observation floats."""
+    engine, whose envs may have up to 128 observation floats (``tall``, with ``wide``: 1024)."""
+    if tall and not wide:
+        raise ValueError("tall is a mode of the wide kernels: pass wide=True")
     if wide:
-        from .vector_host import WIDE_MAX_OBS
+        from .vector_host import TALL_MAX_OBS, WIDE_MAX_OBS
 
-        kw.setdefault("max_obs", WIDE_MAX_OBS)
+        kw.setdefault("max_obs", TALL_MAX_OBS if tall else WIDE_MAX_OBS)
     return _aql.make_pool(env_id, n, workers, seed=seed, max_episode_length=max_episode_length, **kw)
 
 
@@ -107,6 +110,7 @@ class VectorHostEvaluator:
         self.N, self.obs, self.A = N, engine.obs_dim, engine.A
         self.wide = bool(getattr(getattr(engine, "cfg", None), "wide_net", False))   # the vecw_* act kernels
         self.wide_dtype = getattr(getattr(engine, "cfg", None), "wide_dtype", "fp32")     # "bf16": the vecwb_* ones
+        self.tall = bool(getattr(getattr(engine, "cfg", None), "tall_obs", False))        # the vect_* ones
         self.seed = int(seed)
         self.sd = eval_seed(self.seed) & 0xFFFFFFFFFFFF
         self.act_seed = self.sd ^ ACT_XOR
@@ -181,18 +185,19 @@ class VectorHostEvaluator:
                      actions=self.actions.data_ptr())
             make = h.make_vecw_host_eval_act if w else h.make_vec_host_eval_act
             self._acts = [make(net, d) for net in self.nets]
-            self._fused_act = wide_kernel(h, "host_eval_act", self.wide_dtype) if w else h.vec_host_eval_act
+            self._fused_act = (wide_kernel(h, "host_eval_act", self.wide_dtype, self.tall) if w
+                               else h.vec_host_eval_act)
             return
         self._tail = h.make_vec_host_tail(dict(
             E=N, obs=self.obs, F=self.F, stage=self.stage_dev.data_ptr(), ring=self.ring.data_ptr(),
             step=self.counter.data_ptr(), reward=self.reward.data_ptr(), done=self.done.data_ptr(),
             new_frame=self.new_frame.data_ptr(), hist=self.hist.data_ptr(), ep_log=self.ep_log.data_ptr(),
-            ep_ret=self.ep_ret.data_ptr(), ep_len=self.ep_len.data_ptr(), wide=w))
+            ep_ret=self.ep_ret.data_ptr(), ep_len=self.ep_len.data_ptr(), wide=w, tall=self.tall))
         make = h.make_vecw_act if w else h.make_vec_act
         self._step_acts = [make(net, self.ring.data_ptr(), self.hist.data_ptr(), N, self.eps.data_ptr(),
                                 self.act_seed, self.counter.data_ptr(), self.q.data_ptr(),
                                 self.actions.data_ptr()) for net in self.nets]
-        self._step_act = wide_kernel(h, "act", self.wide_dtype) if w else h.vec_act
+        self._step_act = wide_kernel(h, "act", self.wide_dtype, self.tall) if w else h.vec_act
 
     # ------------------------------------------------------------------ weights
     def refresh(self) -> bool:

@@ -1129,7 +1129,8 @@ PYBIND11_MODULE(_apex_hip, m) {
                      P<int>(new_frame), P<float>(ep_log), S(s));
   });
   // the acting step's env half over host envs (vector_host_kernels.hip); d: E, obs, F, stage, ring, step,
-  // reward, done, new_frame, hist, ep_log, ep_ret, ep_len [+ wide: the wide net's observation limit]
+  // reward, done, new_frame, hist, ep_log, ep_ret, ep_len [+ wide: the wide net's observation limit; + tall: the
+  // tall net's]
   py::class_<VecHostTail>(m, "VecHostTail");
   m.def("make_vec_host_tail", [](py::dict d) {
     auto g = [&](const char* k) { return d[k].cast<uint64_t>(); };
@@ -1140,6 +1141,7 @@ PYBIND11_MODULE(_apex_hip, m) {
     a.hist = P<int>(g("hist")); a.ep_log = P<float>(g("ep_log")); a.ep_ret = P<float>(g("ep_ret"));
     a.ep_len = P<float>(g("ep_len"));
     a.wide = d.contains("wide") && d["wide"].cast<bool>();
+    a.tall = d.contains("tall") && d["tall"].cast<bool>();
     return a;
   });
   m.def("vec_host_tail", [](const VecHostTail& a, bool reset, uint64_t s) { vec_host_tail(a, reset, S(s)); },
@@ -1277,6 +1279,22 @@ PYBIND11_MODULE(_apex_hip, m) {
   }, py::arg("a"), py::arg("k"), py::arg("s"));
   m.def("vecwb_learn", [](const VecLearn& p, uint64_t s) { vecwb_learn(p, S(s)); });
   m.def("vecwb_grad", [](const VecGrad& g, uint64_t s) { vecwb_grad(g, S(s)); });
+  // the tall mode of the fp32 wide path (vector_tall_kernels.hip, obs <= 1024) over the make_vecw_* handles and the
+  // vecw row layout; its gradient handle adds the ring and the sampled ids, where dW0 reads the observations
+  m.def("vect_act", [](const VecAct& a, uint64_t s) { vect_act(a, S(s)); });
+  m.def("vect_host_eval_act", [](VecHostEvalAct a, int64_t k, uint64_t s) {
+    a.k = k;
+    vect_host_eval_act(a, S(s));
+  }, py::arg("a"), py::arg("k"), py::arg("s"));
+  m.def("vect_learn", [](const VecLearn& p, uint64_t s) { vect_learn(p, S(s)); });
+  py::class_<VecTallGrad>(m, "VecTallGrad");
+  m.def("make_vect_grad", [](uint64_t vec, int B, int obs, int A, int64_t n, uint64_t grad, uint64_t part,
+                             uint64_t ring, uint64_t s_ids, uint64_t idx) {
+    return VecTallGrad{VecGrad{P<const float>(vec), B, obs, A, n, P<float>(grad), P<double>(part)},
+                       P<const float>(ring), P<const int>(s_ids), P<const int>(idx)};
+  });
+  m.def("vect_grad_blocks", &vect_grad_blocks);
+  m.def("vect_grad", [](const VecTallGrad& g, uint64_t s) { vect_grad(g, S(s)); });
 
   // ---- host gym-API envs (engine/host_env.py)
   py::class_<HostEnvTaps>(m, "HostEnvTaps").def_readonly("max_count", &HostEnvTaps::max_count);

@@ -883,6 +883,8 @@ void aql_apply_staged(const AqlInsert& src, const AqlInsert& dst, int E, int obs
 constexpr int kVecHidden = 128, kVecMaxObs = 8, kVecMaxA = 7;
 // the wide (MFMA) path of the same net, vector_wide_kernels.hip
 constexpr int kVecWideMaxObs = 128, kVecWideMaxA = 32;
+// the tall mode of the wide path (vector_tall_kernels.hip): features.0 streamed over the observation
+constexpr int kVecTallMaxObs = 1024;
 // the ten tensors of DuelingDQN.parameters() (MLP form), reference layouts
 struct VecNet {
   const float *w0, *b0;      // features.0   [128][obs], [128]
@@ -934,6 +936,7 @@ struct VecHostTail {
   float* ep_ret;         // [E] running return
   float* ep_len;         // [E] running length
   bool wide;             // obs up to kVecWideMaxObs (the wide net's shard) instead of kVecMaxObs
+  bool tall;             // (with wide) obs up to kVecTallMaxObs: the tall net's shard
 };
 void vec_host_tail(const VecHostTail& a, bool reset, hipStream_t s);
 // Q[E][A] of the observations at ring row hist[e][3] + select_actions_k's epsilon-greedy draw
@@ -1040,6 +1043,24 @@ void vecwb_act(const VecAct& a, hipStream_t s);
 void vecwb_host_eval_act(const VecHostEvalAct& a, hipStream_t s);
 void vecwb_learn(const VecLearn& p, hipStream_t s);
 void vecwb_grad(const VecGrad& g, hipStream_t s);
+// ---- vector_tall_kernels.hip: the tall mode of the wide fp32-MFMA path, obs <= kVecTallMaxObs
+// (A <= kVecWideMaxA, batch <= 1024).  features.0 streams the observation through a double-buffered
+// LDS slab of 128 columns; everything after it is the wide kernels' code.  vect_act /
+// vect_host_eval_act / vect_learn take their vecw_* counterparts' descriptors.  vect_learn writes the
+// vecw row layout WITHOUT the observation (vecw::X is never written or read); vect_grad contracts
+// dW0 = dF^T . x with x read from the ring through the sampled ids, the other nine tensors as
+// vecw_grad does.  VecTallGrad::g.part holds vect_grad_blocks(obs, A) partials.
+struct VecTallGrad {
+  VecGrad g;
+  const float* ring;   // the replay's frame ring viewed as [F][obs] fp32
+  const int* s_ids;    // [C][4] frame ids of s (observation = [3]), read through idx
+  const int* idx;      // [B] sampled slots
+};
+void vect_act(const VecAct& a, hipStream_t s);
+void vect_host_eval_act(const VecHostEvalAct& a, hipStream_t s);
+void vect_learn(const VecLearn& p, hipStream_t s);
+int vect_grad_blocks(int obs, int A);
+void vect_grad(const VecTallGrad& g, hipStream_t s);
 // The actor side of one frame of the single-process prioritized DQN (reference DQN.py) in ONE
 // launch of one workgroup, E <= 8 envs: epsilon(t) / beta(t) in fp64, vec_act's forward and
 // draw on the online net, vec_classic_step's env step, frame_hist_step's FrameStack advance,

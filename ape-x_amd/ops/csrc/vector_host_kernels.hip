@@ -78,8 +78,11 @@ __global__ __launch_bounds__(kTailThreads) void vec_host_tail_k(VecHostTail T, i
 
 void vec_host_tail(const VecHostTail& a, bool reset, hipStream_t s) {
   if (a.E < 1 || a.E > 4096) throw std::invalid_argument("vec_host_tail: 1 <= envs <= 4096");
-  if (a.obs < 1 || a.obs > (a.wide ? kVecWideMaxObs : kVecMaxObs))
-    throw std::invalid_argument(a.wide ? "vec_host_tail: 1 <= obs <= 128 (wide)" : "vec_host_tail: 1 <= obs <= 8");
+  if (a.tall && !a.wide) throw std::invalid_argument("vec_host_tail: tall is a mode of wide");
+  if (a.obs < 1 || a.obs > (a.tall ? kVecTallMaxObs : a.wide ? kVecWideMaxObs : kVecMaxObs))
+    throw std::invalid_argument(a.tall   ? "vec_host_tail: 1 <= obs <= 1024 (tall)"
+                                : a.wide ? "vec_host_tail: 1 <= obs <= 128 (wide)"
+                                         : "vec_host_tail: 1 <= obs <= 8");
   if (a.F < 2 * a.E) throw std::invalid_argument("vec_host_tail: ring must hold >= 2 E rows");
   if (!a.stage || !a.ring || !a.step || !a.reward || !a.done || !a.new_frame || !a.hist || !a.ep_log || !a.ep_ret ||
       !a.ep_len)

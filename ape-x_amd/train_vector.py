@@ -28,7 +28,9 @@ device synchronize, then whole episodes on a CPU copy of the net inside the trai
 ``--wide`` (either kind of env) runs the acting forward and the learner through the fp32-MFMA
 kernels (``VectorEngineConfig.wide_net``): a host env may then have up to 128 observation floats
 and 32 actions; ``--wide --dtype bf16`` takes their bf16-operand variants (``wide_dtype``: bf16
-matrix-core operands, fp32 accumulation, fp32 master weights and checkpoints).  ``--wide`` is still refused with ``--eval-envs``: the evaluator itself takes a wide engine
+matrix-core operands, fp32 accumulation, fp32 master weights and checkpoints); ``--host-envs --wide
+--tall`` takes the streamed fp32 kernels (``tall_obs``, ``vect_*``): up to 1024 observation floats.
+``--wide`` is still refused with ``--eval-envs``: the evaluator itself takes a wide engine
 (``vecw_host_eval_act``, :mod:`apex_amd.engine.vector_host_eval`), this command line's switch-over is
 a follow-up; the blocking evaluator and the reference-format checkpoints work as they are.
 ``--eval-envs N`` (with ``--eval-workers W``, ``--eval-kernel``) evaluates beside training instead:
@@ -60,6 +62,10 @@ class _Parser(argparse.ArgumentParser):
         a = super().parse_args(args, namespace)
         if a.dtype != "fp32" and not a.wide:
             self.error("--dtype bf16 is a mode of the wide kernels: pass --wide")
+        if a.tall and not (a.host_envs and a.wide):
+            self.error("--tall is a mode of the wide kernels on host envs: pass --host-envs --wide")
+        if a.tall and a.dtype != "fp32":
+            self.error("--tall takes --dtype fp32: a bf16 tall mode is out of scope")
         if a.host_envs:
             if a.eval_mode != "step":
                 self.error("--host-envs evaluates on the host: --eval-mode must be 'step'")
@@ -104,6 +110,8 @@ def parser() -> argparse.ArgumentParser:
                    help="the fp32-MFMA kernels (vecw_*): flat observation <= 128, discrete actions <= 32")
     p.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"],
                    help="(--wide) bf16: bf16 matrix-core operands, fp32 accumulation and master weights (vecwb_*)")
+    p.add_argument("--tall", action="store_true",
+                   help="(--host-envs --wide) the streamed fp32-MFMA kernels (vect_*): flat observation <= 1024")
     p.add_argument("--learner-steps", type=int, default=1, help="(--host-envs) SGD steps per env step")
     p.add_argument("--host-serial", action="store_true",
                    help="(--host-envs) learner steps, then the acting step: no overlap with the host's env step")
@@ -153,7 +161,7 @@ def config_from_args(a) -> VectorEngineConfig:
                               lr=a.lr, replay_capacity=a.capacity, actor_steps_per_learner_step=a.actor_steps,
                               nstep_mode=a.nstep_mode, target_update_interval=a.target_update_interval,
                               publish_param_interval=a.publish_interval, seed=a.seed,
-                              wide_net=a.wide, wide_dtype=a.dtype).validate(not a.host_envs)
+                              wide_net=a.wide, wide_dtype=a.dtype, tall_obs=a.tall).validate(not a.host_envs)
 
 
 def _crossed(t: int, prev: int, interval: int) -> bool:
@@ -164,10 +172,10 @@ def _crossed(t: int, prev: int, interval: int) -> bool:
 def make_engine(a, cfg: VectorEngineConfig):
     if not a.host_envs:
         return VectorApexEngine(cfg, a.device)
-    from .engine.vector_host import WIDE_MAX_OBS, VectorHostEngine
+    from .engine.vector_host import TALL_MAX_OBS, WIDE_MAX_OBS, VectorHostEngine
     from .envs.host_vector import HostVectorEnv
 
-    kw = dict(max_obs=WIDE_MAX_OBS) if a.wide else {}
+    kw = dict(max_obs=TALL_MAX_OBS if a.tall else WIDE_MAX_OBS) if a.wide else {}
     vec = HostVectorEnv(a.env, a.envs, seed=a.seed, max_episode_length=a.max_episode_length, **kw)
     return VectorHostEngine(cfg, vec, a.device, learner_steps=a.learner_steps, host_overlap=not a.host_serial)
 
