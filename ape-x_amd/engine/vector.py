@@ -37,10 +37,13 @@ parameter storage, so it is offered for the device envs only.  ``wide_dtype="bf1
 ``wide_net``) takes the same launches from ``ops/csrc/vector_wide_bf16_kernels.hip`` instead
 (``vecwb_act`` / ``vecwb_learn`` / ``vecwb_grad``): bf16 matrix-core operands rounded from the fp32
 master weights and activations inside the kernels, fp32 accumulation, everything else -- parameters,
-target net, optimizer, checkpoints -- fp32 as before.  ``tall_obs=True`` (with ``wide_net``, fp32 only)
-takes them from ``ops/csrc/vector_tall_kernels.hip`` (``vect_act`` / ``vect_learn`` / ``vect_grad``):
-observations to 1024 floats, ``features.0`` streamed through a double-buffered LDS slab, its weight
-gradient contracted against the observations in the ring (no copy in the per-sample rows).
+target net, optimizer, checkpoints -- fp32 as before.  ``tall_obs=True`` (with ``wide_net`` and
+``wide_dtype="fp32"``) takes them from ``ops/csrc/vector_tall_kernels.hip`` (``vect_act`` / ``vect_learn`` /
+``vect_grad``): observations to 1024 floats, ``features.0`` streamed through a double-buffered LDS slab, its
+weight gradient contracted against the observations in the ring (no copy in the per-sample rows).
+``tall_dtype="bf16"`` (with ``tall_obs``) takes the tall launches from
+``ops/csrc/vector_tall_bf16_kernels.hip`` (``vectb_act`` / ``vectb_learn`` / ``vectb_grad``): the same
+streaming under ``wide_dtype="bf16"``'s precision contract.
 
 Serial actor-then-learner on one stream; overlap and multi-GPU topologies are the Atari
 engine's and are not offered here.  Envs other than ``VECTOR_ENVS`` -- any gym-API env with a
@@ -102,15 +105,22 @@ def load_state_dict(path: str, env_id: str | None = None, model: DuelingDQN | No
 WIDE_DTYPES = ("fp32", "bf16")
 
 
-def wide_kernel(hip, name: str, dtype: str = "fp32", tall: bool = False):
+def wide_kernel(hip, name: str, dtype: str = "fp32", tall: bool = False, tall_dtype: str = "fp32"):
     """The wide launch ``name`` (``act``, ``learn``, ``grad``, ``host_eval_act``) of ``wide_dtype``
     ``dtype``: ``vecw_<name>`` (fp32 MFMA) or ``vecwb_<name>`` (bf16 operands); ``tall``:
-    ``vect_<name>`` (fp32 MFMA, observations to 1024 floats)."""
+    ``vect_<name>`` (fp32 MFMA, observations to 1024 floats) or, with ``tall_dtype="bf16"``,
+    ``vectb_<name>`` (bf16 operands)."""
     if dtype not in WIDE_DTYPES:
         raise ValueError(f"wide_dtype must be one of {WIDE_DTYPES}, got {dtype!r}")
+    if tall_dtype not in WIDE_DTYPES:
+        raise ValueError(f"tall_dtype must be one of {WIDE_DTYPES}, got {tall_dtype!r}")
     if tall and dtype != "fp32":
-        raise ValueError("the tall kernels are fp32: a bf16 tall mode is out of scope")
-    return getattr(hip, ("vect_" if tall else "vecwb_" if dtype == "bf16" else "vecw_") + name)
+        raise ValueError("the tall kernels take wide_dtype='fp32' (as wide_dtype a bf16 tall mode is out of scope): "
+                         "their bf16 operands are tall_dtype='bf16'")
+    if tall_dtype != "fp32" and not tall:
+        raise ValueError("tall_dtype='bf16' is a mode of the tall kernels: pass tall=True")
+    prefix = ("vectb_" if tall_dtype == "bf16" else "vect_") if tall else "vecwb_" if dtype == "bf16" else "vecw_"
+    return getattr(hip, prefix + name)
 
 
 def vec_net(hip, model: DuelingDQN):
@@ -135,7 +145,7 @@ class VectorActorShard(NStepShard):
                  eps_base: float = 0.4, eps_alpha: float = 7.0, actor_offset: int = 0,
                  total_actors: int | None = None, seed: int = 0, mode: str = "reference",
                  max_episode_steps: int | None = None, wide: bool = False, wide_dtype: str = "fp32",
-                 tall: bool = False):
+                 tall: bool = False, tall_dtype: str = "fp32"):
         self.env_id = env_id
         self.wide = bool(wide)   # act with vecw_act (the MFMA forward) instead of vec_act
         self.kind, self.obs_dim, n_actions, limit = env_spec(env_id)
@@ -144,8 +154,8 @@ class VectorActorShard(NStepShard):
             raise ValueError(f"replay frame_bytes must be 4 * obs_dim = {4 * self.obs_dim}")
         super().__init__(replay, n_envs, n_actions, n_step, gamma, eps_base, eps_alpha, actor_offset, total_actors,
                          seed, mode)
-        # (vecwb_act for bf16, vect_act for tall)
-        self._wide_act = wide_kernel(self.hip, "act", wide_dtype, tall) if self.wide else None
+        # (vecwb_act for bf16, vect_act / vectb_act for tall)
+        self._wide_act = wide_kernel(self.hip, "act", wide_dtype, tall, tall_dtype) if self.wide else None
         E = self.E
         self.layout = self.hip.vec_env_state_layout()
         self.env_state = torch.zeros(E, self.layout["STRIDE"], dtype=torch.float32, device=self.device)
@@ -226,6 +236,7 @@ class VectorEngineConfig:
     wide_net: bool = False           # the MFMA kernels (vecw_*): obs <= 128, A <= 32; same launch sequence
     wide_dtype: str = "fp32"         # (wide_net) "bf16": bf16 matrix-core operands, fp32 accumulation (vecwb_*)
     tall_obs: bool = False           # (wide_net, fp32) the streamed kernels (vect_*): obs <= 1024
+    tall_dtype: str = "fp32"         # (tall_obs) "bf16": the streamed kernels with bf16 operands (vectb_*)
     seed: int = 0
 
     def validate(self, device_env: bool = True) -> "VectorEngineConfig":
@@ -252,7 +263,12 @@ class VectorEngineConfig:
         if self.tall_obs and not self.wide_net:
             raise ValueError("tall_obs is a mode of the wide kernels: set wide_net")
         if self.tall_obs and self.wide_dtype != "fp32":
-            raise ValueError("tall_obs takes wide_dtype='fp32': a bf16 tall mode is out of scope")
+            raise ValueError("tall_obs takes wide_dtype='fp32' (as wide_dtype a bf16 tall mode is out of scope): "
+                             "set tall_dtype='bf16' for the tall kernels' bf16 operands")
+        if self.tall_dtype not in WIDE_DTYPES:
+            raise ValueError(f"tall_dtype must be one of {WIDE_DTYPES}, got {self.tall_dtype!r}")
+        if self.tall_dtype != "fp32" and not self.tall_obs:
+            raise ValueError("tall_dtype='bf16' is a mode of the tall kernels: set tall_obs")
         return self
 
 
@@ -316,8 +332,8 @@ class MLPDQNLearner:
         self.ring = replay.frames.view(torch.float32)
         self.net = vec_net(h, self.model)
         self.tnet = vec_net(h, self.target)
-        self._learn, self._grad = ((wide_kernel(h, "learn", cfg.wide_dtype, tall),
-                                    wide_kernel(h, "grad", cfg.wide_dtype, tall))
+        self._learn, self._grad = ((wide_kernel(h, "learn", cfg.wide_dtype, tall, cfg.tall_dtype),
+                                    wide_kernel(h, "grad", cfg.wide_dtype, tall, cfg.tall_dtype))
                                    if wide else (h.vec_learn, h.vec_grad))
         self.L = (h.make_vecw_learn if wide else h.make_vec_learn)(self.net, self.tnet, dict(
             replay.trans_ptrs(), ring=self.ring.data_ptr(), idx=self.idx.data_ptr(), w=self.w.data_ptr(), B=B,
@@ -400,7 +416,8 @@ class VectorApexEngine(GreedyRollouts):
         self.actor_flat = self.actor_model.flatten_parameters()
         self.shard = VectorActorShard(self.replay, cfg.n_envs, cfg.env_id, cfg.n_step, cfg.gamma, cfg.eps_base,
                                       cfg.eps_alpha, seed=cfg.seed * 0x2545F491 + 0xAC7, mode=cfg.nstep_mode,
-                                      wide=cfg.wide_net, wide_dtype=cfg.wide_dtype, tall=cfg.tall_obs)
+                                      wide=cfg.wide_net, wide_dtype=cfg.wide_dtype, tall=cfg.tall_obs,
+                                      tall_dtype=cfg.tall_dtype)
         self.shard.set_policy(self.actor_model)
         self.publish_params()
         self.learn_steps = 0

@@ -54,7 +54,8 @@ Shapes: observations to 8 floats and 7 actions (``kVecMaxObs`` / ``kVecMaxA``) b
 ``kVecWideMaxA``); ``wide_dtype="bf16"`` takes them from ``ops/csrc/vector_wide_bf16_kernels.hip``
 (``vecwb_*``: bf16 matrix-core operands, fp32 accumulation and master weights); ``tall_obs`` (with
 ``wide_net``, fp32) raises the observation limit to 1024 (``kVecTallMaxObs``) on the streamed kernels of
-``ops/csrc/vector_tall_kernels.hip`` (``vect_*``).  The side-stream
+``ops/csrc/vector_tall_kernels.hip`` (``vect_*``), ``tall_dtype="bf16"`` takes those with bf16 operands
+(``ops/csrc/vector_tall_bf16_kernels.hip``, ``vectb_*``).  The side-stream
 evaluator follows the engine: over a wide engine its act is ``vecw_host_eval_act`` / ``vecwb_host_eval_act``
 (:mod:`apex_amd.engine.vector_host_eval`, through the API; ``train_vector
 --wide --eval-envs`` is still refused, the CLI's switch-over is a follow-up, so on the command line a
@@ -114,7 +115,8 @@ class VectorHostShard(NStepShard):
 
     def __init__(self, replay: HBMReplay, vec, n_step: int = 3, gamma: float = 0.99, eps_base: float = 0.4,
                  eps_alpha: float = 7.0, actor_offset: int = 0, total_actors: int | None = None, seed: int = 0,
-                 mode: str = "reference", wide: bool = False, wide_dtype: str = "fp32", tall: bool = False):
+                 mode: str = "reference", wide: bool = False, wide_dtype: str = "fp32", tall: bool = False,
+                 tall_dtype: str = "fp32"):
         self.vec = vec
         self.wide = bool(wide)   # act with vecw_act; the tail takes the wide observation limit
         self.tall = bool(tall)   # (wide) act with vect_act; the tail takes the tall observation limit
@@ -127,7 +129,7 @@ class VectorHostShard(NStepShard):
         super().__init__(replay, E, n_actions, n_step, gamma, eps_base, eps_alpha, actor_offset, total_actors, seed,
                          mode)
         # (vecwb_act for bf16, vect_act for tall)
-        self._wide_act = wide_kernel(self.hip, "act", wide_dtype, self.tall) if self.wide else None
+        self._wide_act = wide_kernel(self.hip, "act", wide_dtype, self.tall, tall_dtype) if self.wide else None
         h, dev = self.hip, self.device
         self.ring = replay.frames.view(torch.float32)  # [F, obs_dim]
         self.ep_ret = torch.zeros(E, dtype=torch.float32, device=dev)
@@ -256,7 +258,7 @@ class VectorHostEngine:
         self.actor_flat = self.actor_model.flatten_parameters()
         self.shard = VectorHostShard(self.replay, vec, cfg.n_step, cfg.gamma, cfg.eps_base, cfg.eps_alpha,
                                      seed=cfg.seed * 0x2545F491 + 0xAC7, mode=cfg.nstep_mode, wide=cfg.wide_net,
-                                     wide_dtype=cfg.wide_dtype, tall=cfg.tall_obs)
+                                     wide_dtype=cfg.wide_dtype, tall=cfg.tall_obs, tall_dtype=cfg.tall_dtype)
         self.shard._enqueued = lambda: self._enqueued()
         self.shard.set_policy(self.actor_model)
         self.publish_params()

@@ -28,7 +28,8 @@ the fp32-MFMA forward of ops/csrc/vector_wide_kernels.hip: ``"fused"`` is ``vecw
 limit -> ``frame_hist_step`` -> ``vecw_act``; everything else is shared.  With ``cfg.wide_dtype ==
 "bf16"`` the two acts are ``vecwb_host_eval_act`` / ``vecwb_act`` (ops/csrc/vector_wide_bf16_kernels.hip)
 over the same descriptors, with ``cfg.tall_obs`` (observations to 1024 floats) ``vect_host_eval_act`` /
-``vect_act`` (ops/csrc/vector_tall_kernels.hip).  :func:`make_pool` takes
+``vect_act`` (ops/csrc/vector_tall_kernels.hip), with ``cfg.tall_dtype == "bf16"`` ``vectb_host_eval_act`` /
+``vectb_act`` (ops/csrc/vector_tall_bf16_kernels.hip).  :func:`make_pool` takes
 ``wide=True`` to let the workers' envs have that many observation floats.  The command line does not
 reach this yet: ``train_vector --wide --eval-envs`` is still refused, its switch-over is a follow-up.
 
@@ -111,6 +112,7 @@ class VectorHostEvaluator:
         self.wide = bool(getattr(getattr(engine, "cfg", None), "wide_net", False))   # the vecw_* act kernels
         self.wide_dtype = getattr(getattr(engine, "cfg", None), "wide_dtype", "fp32")     # "bf16": the vecwb_* ones
         self.tall = bool(getattr(getattr(engine, "cfg", None), "tall_obs", False))        # the vect_* ones
+        self.tall_dtype = getattr(getattr(engine, "cfg", None), "tall_dtype", "fp32")     # "bf16": the vectb_* ones
         self.seed = int(seed)
         self.sd = eval_seed(self.seed) & 0xFFFFFFFFFFFF
         self.act_seed = self.sd ^ ACT_XOR
@@ -185,7 +187,7 @@ class VectorHostEvaluator:
                      actions=self.actions.data_ptr())
             make = h.make_vecw_host_eval_act if w else h.make_vec_host_eval_act
             self._acts = [make(net, d) for net in self.nets]
-            self._fused_act = (wide_kernel(h, "host_eval_act", self.wide_dtype, self.tall) if w
+            self._fused_act = (wide_kernel(h, "host_eval_act", self.wide_dtype, self.tall, self.tall_dtype) if w
                                else h.vec_host_eval_act)
             return
         self._tail = h.make_vec_host_tail(dict(
@@ -197,7 +199,7 @@ class VectorHostEvaluator:
         self._step_acts = [make(net, self.ring.data_ptr(), self.hist.data_ptr(), N, self.eps.data_ptr(),
                                 self.act_seed, self.counter.data_ptr(), self.q.data_ptr(),
                                 self.actions.data_ptr()) for net in self.nets]
-        self._step_act = wide_kernel(h, "act", self.wide_dtype, self.tall) if w else h.vec_act
+        self._step_act = wide_kernel(h, "act", self.wide_dtype, self.tall, self.tall_dtype) if w else h.vec_act
 
     # ------------------------------------------------------------------ weights
     def refresh(self) -> bool:

@@ -58,6 +58,7 @@ HIP_SOURCES = [
     "vector_wide_kernels.hip",
     "vector_wide_bf16_kernels.hip",
     "vector_tall_kernels.hip",
+    "vector_tall_bf16_kernels.hip",
     "vector_host_kernels.hip",
     "host_env_kernels.hip",
     "host_eval_kernels.hip",
@@ -187,6 +188,7 @@ EXTRA_HIP_FLAGS = {
     "vector_wide_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "vector_wide_bf16_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "vector_tall_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "vector_tall_bf16_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

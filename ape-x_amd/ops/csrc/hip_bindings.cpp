@@ -1295,6 +1295,14 @@ PYBIND11_MODULE(_apex_hip, m) {
   });
   m.def("vect_grad_blocks", &vect_grad_blocks);
   m.def("vect_grad", [](const VecTallGrad& g, uint64_t s) { vect_grad(g, S(s)); });
+  // the tall mode with bf16 matrix-core operands (vector_tall_bf16_kernels.hip) over the same handles
+  m.def("vectb_act", [](const VecAct& a, uint64_t s) { vectb_act(a, S(s)); });
+  m.def("vectb_host_eval_act", [](VecHostEvalAct a, int64_t k, uint64_t s) {
+    a.k = k;
+    vectb_host_eval_act(a, S(s));
+  }, py::arg("a"), py::arg("k"), py::arg("s"));
+  m.def("vectb_learn", [](const VecLearn& p, uint64_t s) { vectb_learn(p, S(s)); });
+  m.def("vectb_grad", [](const VecTallGrad& g, uint64_t s) { vectb_grad(g, S(s)); });
 
   // ---- host gym-API envs (engine/host_env.py)
   py::class_<HostEnvTaps>(m, "HostEnvTaps").def_readonly("max_count", &HostEnvTaps::max_count);

@@ -1061,6 +1061,15 @@ void vect_host_eval_act(const VecHostEvalAct& a, hipStream_t s);
 void vect_learn(const VecLearn& p, hipStream_t s);
 int vect_grad_blocks(int obs, int A);
 void vect_grad(const VecTallGrad& g, hipStream_t s);
+// ---- vector_tall_bf16_kernels.hip: the tall mode with bf16 matrix-core operands -- vect_*'s limits,
+// descriptors, row layout (vecw::X never written) and vect_grad_blocks tiles under vecwb_*'s precision
+// contract.  features.0 streams the observation through a double-buffered bf16 LDS slab of 256 columns
+// with the next round's fp32 weight loads in flight behind the current round's MFMAs; everything
+// after it is the bf16 wide kernels' code.
+void vectb_act(const VecAct& a, hipStream_t s);
+void vectb_host_eval_act(const VecHostEvalAct& a, hipStream_t s);
+void vectb_learn(const VecLearn& p, hipStream_t s);
+void vectb_grad(const VecTallGrad& g, hipStream_t s);
 // The actor side of one frame of the single-process prioritized DQN (reference DQN.py) in ONE
 // launch of one workgroup, E <= 8 envs: epsilon(t) / beta(t) in fp64, vec_act's forward and
 // draw on the online net, vec_classic_step's env step, frame_hist_step's FrameStack advance,

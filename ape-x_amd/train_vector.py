@@ -29,7 +29,8 @@ device synchronize, then whole episodes on a CPU copy of the net inside the trai
 kernels (``VectorEngineConfig.wide_net``): a host env may then have up to 128 observation floats
 and 32 actions; ``--wide --dtype bf16`` takes their bf16-operand variants (``wide_dtype``: bf16
 matrix-core operands, fp32 accumulation, fp32 master weights and checkpoints); ``--host-envs --wide
---tall`` takes the streamed fp32 kernels (``tall_obs``, ``vect_*``): up to 1024 observation floats.
+--tall`` takes the streamed fp32 kernels (``tall_obs``, ``vect_*``): up to 1024 observation floats;
+``--host-envs --wide --tall --dtype bf16`` takes those with bf16 operands (``tall_dtype``, ``vectb_*``).
 ``--wide`` is still refused with ``--eval-envs``: the evaluator itself takes a wide engine
 (``vecw_host_eval_act``, :mod:`apex_amd.engine.vector_host_eval`), this command line's switch-over is
 a follow-up; the blocking evaluator and the reference-format checkpoints work as they are.
@@ -64,8 +65,6 @@ class _Parser(argparse.ArgumentParser):
             self.error("--dtype bf16 is a mode of the wide kernels: pass --wide")
         if a.tall and not (a.host_envs and a.wide):
             self.error("--tall is a mode of the wide kernels on host envs: pass --host-envs --wide")
-        if a.tall and a.dtype != "fp32":
-            self.error("--tall takes --dtype fp32: a bf16 tall mode is out of scope")
         if a.host_envs:
             if a.eval_mode != "step":
                 self.error("--host-envs evaluates on the host: --eval-mode must be 'step'")
@@ -109,7 +108,8 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--wide", action="store_true",
                    help="the fp32-MFMA kernels (vecw_*): flat observation <= 128, discrete actions <= 32")
     p.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"],
-                   help="(--wide) bf16: bf16 matrix-core operands, fp32 accumulation and master weights (vecwb_*)")
+                   help="(--wide) bf16: bf16 matrix-core operands, fp32 accumulation and master weights (vecwb_*; with "
+                        "--tall vectb_*)")
     p.add_argument("--tall", action="store_true",
                    help="(--host-envs --wide) the streamed fp32-MFMA kernels (vect_*): flat observation <= 1024")
     p.add_argument("--learner-steps", type=int, default=1, help="(--host-envs) SGD steps per env step")
@@ -161,7 +161,8 @@ def config_from_args(a) -> VectorEngineConfig:
                               lr=a.lr, replay_capacity=a.capacity, actor_steps_per_learner_step=a.actor_steps,
                               nstep_mode=a.nstep_mode, target_update_interval=a.target_update_interval,
                               publish_param_interval=a.publish_interval, seed=a.seed,
-                              wide_net=a.wide, wide_dtype=a.dtype, tall_obs=a.tall).validate(not a.host_envs)
+                              wide_net=a.wide, wide_dtype="fp32" if a.tall else a.dtype, tall_obs=a.tall,
+                              tall_dtype=a.dtype if a.tall else "fp32").validate(not a.host_envs)
 
 
 def _crossed(t: int, prev: int, interval: int) -> bool:

@@ -10,6 +10,10 @@
 * ``train_vector --host-envs --wide --tall`` itself on a synthetic env of Humanoid's 376 floats, ``--cli-steps``
   SGD steps.
 
+``--vectb`` measures the bf16-operand tall kernels instead (profiles/vector_tall_bf16.md): ``vectb_*`` alternated
+with ``vect_*`` inside every repetition at obs 128 / 256 / 512 / 1024, B 64 / 512, the two acts at E = 16 and
+4096, and the captured loop at obs 1024 / B 64 for both.
+
 One JSON line per shape."""
 import argparse
 import json
@@ -24,7 +28,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from bench_vector_wide_bf16 import _us  # noqa: E402
 
 
-def _engine(a, obs, B, tall, k=1, envs=64):
+def _engine(a, obs, B, tall, k=1, envs=64, tall_dtype="fp32"):
     from bench_vector_host_eval import wide_env
 
     from apex_amd.engine.vector import VectorEngineConfig
@@ -33,15 +37,15 @@ def _engine(a, obs, B, tall, k=1, envs=64):
 
     vec = HostVectorEnv([lambda: wide_env(f"wide-{obs}x18")] * envs, seed=a.seed, max_obs=1024)
     cfg = VectorEngineConfig(env_id=f"wide-{obs}x18", batch_size=B, replay_capacity=16384, wide_net=True,
-                             tall_obs=tall, seed=a.seed)
+                             tall_obs=tall, tall_dtype=tall_dtype, seed=a.seed)
     return VectorHostEngine(cfg, vec, "cuda:0", learner_steps=k)
 
 
 def kernels(a, obs, B, modes):
-    """``modes``: the (name, tall) variants measured on this shape, alternated."""
+    """``modes``: the (name, tall[, tall_dtype]) variants measured on this shape, alternated."""
     import torch
 
-    engs = {n: _engine(a, obs, B, t) for n, t in modes}
+    engs = {n: _engine(a, obs, B, t, tall_dtype=(d or ["fp32"])[0]) for n, t, *d in modes}
     f = {}
     for n, e in engs.items():
         e.fill(4 * B)
@@ -66,7 +70,7 @@ def kernels(a, obs, B, modes):
     return out
 
 
-def act(a, obs, E):
+def act(a, obs, E, tall_dtype="fp32"):
     import numpy as np
     import torch
 
@@ -87,19 +91,20 @@ def act(a, obs, E):
             self.staging[E * obs:2 * E * obs] = np.random.default_rng(a.seed).standard_normal(E * obs)
 
     rp = HBMReplay(max(4096, 4 * E), n_envs=E, n_step=3, device="cuda:0", frame_bytes=4 * obs)
-    sh = VectorHostShard(rp, Rows(), seed=a.seed, wide=True, tall=True)
+    sh = VectorHostShard(rp, Rows(), seed=a.seed, wide=True, tall=True, tall_dtype=tall_dtype)
     sh.set_policy(DuelingDQN.from_shapes((obs,), 18).to("cuda:0"))
     _us(sh.act, 50)
     v = [_us(sh.act, a.launches) for _ in range(a.reps)]
     sh.close()
-    return dict(what="act", obs=obs, A=18, E=E, vect_act_us=round(statistics.median(v), 2),
+    name = "vectb_act_us" if tall_dtype == "bf16" else "vect_act_us"
+    return dict(what="act", obs=obs, A=18, E=E, **{name: round(statistics.median(v), 2)},
                 spread=round((max(v) - min(v)) / statistics.median(v), 4))
 
 
-def loop(a, obs, B):
+def loop(a, obs, B, tall_dtype="fp32"):
     import torch
 
-    e = _engine(a, obs, B, True, a.k)
+    e = _engine(a, obs, B, True, a.k, tall_dtype=tall_dtype)
     e.fill(4 * B)
     e.capture()
     for _ in range(50):
@@ -114,7 +119,8 @@ def loop(a, obs, B):
         torch.cuda.synchronize()
         rate.append(n * e.K / (time.perf_counter() - t0))
     e.close()
-    return dict(what="loop", obs=obs, A=18, B=B, K=a.k, envs=64, sgd_steps_per_s=round(statistics.median(rate)),
+    return dict(what="loop", tall_dtype=tall_dtype, obs=obs, A=18, B=B, K=a.k, envs=64,
+                sgd_steps_per_s=round(statistics.median(rate)),
                 spread=round((max(rate) - min(rate)) / statistics.median(rate), 4))
 
 
@@ -146,7 +152,18 @@ def main():
     ap.add_argument("--seconds", type=float, default=2.0)
     ap.add_argument("--cli-steps", type=int, default=2000)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--vectb", action="store_true", help="vectb_* against vect_* (profiles/vector_tall_bf16.md)")
     a = ap.parse_args()
+    if a.vectb:
+        for E in (16, 4096):
+            for dt in ("fp32", "bf16"):
+                print(json.dumps(act(a, 1024, E, dt)), flush=True)
+        for B in (64, 512):
+            for obs in (128, 256, 512, 1024):
+                print(json.dumps(kernels(a, obs, B, (("vect", True), ("vectb", True, "bf16")))), flush=True)
+        for dt in ("fp32", "bf16"):
+            print(json.dumps(loop(a, 1024, 64, dt)), flush=True)
+        return
     for E in (16, 4096):
         print(json.dumps(act(a, 1024, E)), flush=True)
     for B in (64, 512):
