@@ -43,7 +43,12 @@ target net, optimizer, checkpoints -- fp32 as before.  ``tall_obs=True`` (with `
 weight gradient contracted against the observations in the ring (no copy in the per-sample rows).
 ``tall_dtype="bf16"`` (with ``tall_obs``) takes the tall launches from
 ``ops/csrc/vector_tall_bf16_kernels.hip`` (``vectb_act`` / ``vectb_learn`` / ``vectb_grad``): the same
-streaming under ``wide_dtype="bf16"``'s precision contract.
+streaming under ``wide_dtype="bf16"``'s precision contract.  ``ring_dtype="bf16"`` (with ``tall_obs`` and
+``tall_dtype="bf16"``, host-env engine only) stores the observation ring as bf16 (``frame_bytes = 2 * obs_dim``):
+``vec_host_tail`` rounds each row once where it is written, and ``vectb_act`` / ``vectb_learn`` / ``vectb_grad``
+load the operand bits themselves, 8 columns per 16-byte load, with no conversion.  The rounding is the one those
+kernels apply to an fp32 row at every read, so every result is bit-equal to the fp32 ring's at half the
+observation bytes in the replay.
 
 Serial actor-then-learner on one stream; overlap and multi-GPU topologies are the Atari
 engine's and are not offered here.  Envs other than ``VECTOR_ENVS`` -- any gym-API env with a
@@ -105,11 +110,23 @@ def load_state_dict(path: str, env_id: str | None = None, model: DuelingDQN | No
 WIDE_DTYPES = ("fp32", "bf16")
 
 
-def wide_kernel(hip, name: str, dtype: str = "fp32", tall: bool = False, tall_dtype: str = "fp32"):
+def ring_bytes(ring_dtype: str) -> int:
+    """Bytes per observation component in the frame ring."""
+    if ring_dtype not in WIDE_DTYPES:
+        raise ValueError(f"ring_dtype must be one of {WIDE_DTYPES}, got {ring_dtype!r}")
+    return 2 if ring_dtype == "bf16" else 4
+
+
+def wide_kernel(hip, name: str, dtype: str = "fp32", tall: bool = False, tall_dtype: str = "fp32",
+                ring_dtype: str = "fp32"):
     """The wide launch ``name`` (``act``, ``learn``, ``grad``, ``host_eval_act``) of ``wide_dtype``
     ``dtype``: ``vecw_<name>`` (fp32 MFMA) or ``vecwb_<name>`` (bf16 operands); ``tall``:
     ``vect_<name>`` (fp32 MFMA, observations to 1024 floats) or, with ``tall_dtype="bf16"``,
-    ``vectb_<name>`` (bf16 operands)."""
+    ``vectb_<name>`` (bf16 operands).  ``ring_dtype="bf16"`` is taken by the ``vectb_*`` launches alone
+    (the handle carries ``ring_bf16``; the launch is the same)."""
+    ring_bytes(ring_dtype)
+    if ring_dtype != "fp32" and not (tall and tall_dtype == "bf16"):
+        raise ValueError("ring_dtype='bf16' is a layout of the tall bf16 kernels: pass tall=True and tall_dtype='bf16'")
     if dtype not in WIDE_DTYPES:
         raise ValueError(f"wide_dtype must be one of {WIDE_DTYPES}, got {dtype!r}")
     if tall_dtype not in WIDE_DTYPES:
@@ -237,6 +254,7 @@ class VectorEngineConfig:
     wide_dtype: str = "fp32"         # (wide_net) "bf16": bf16 matrix-core operands, fp32 accumulation (vecwb_*)
     tall_obs: bool = False           # (wide_net, fp32) the streamed kernels (vect_*): obs <= 1024
     tall_dtype: str = "fp32"         # (tall_obs) "bf16": the streamed kernels with bf16 operands (vectb_*)
+    ring_dtype: str = "fp32"         # (tall_dtype "bf16", host envs) "bf16": the observation ring stored as bf16
     seed: int = 0
 
     def validate(self, device_env: bool = True) -> "VectorEngineConfig":
@@ -269,6 +287,14 @@ class VectorEngineConfig:
             raise ValueError(f"tall_dtype must be one of {WIDE_DTYPES}, got {self.tall_dtype!r}")
         if self.tall_dtype != "fp32" and not self.tall_obs:
             raise ValueError("tall_dtype='bf16' is a mode of the tall kernels: set tall_obs")
+        if self.ring_dtype not in WIDE_DTYPES:
+            raise ValueError(f"ring_dtype must be one of {WIDE_DTYPES}, got {self.ring_dtype!r}")
+        if self.ring_dtype != "fp32" and not (self.wide_net and self.tall_obs and self.tall_dtype == "bf16"):
+            raise ValueError("ring_dtype='bf16' is a layout of the tall bf16 kernels: set tall_obs and "
+                             "tall_dtype='bf16'")
+        if self.ring_dtype != "fp32" and device_env:
+            raise ValueError("ring_dtype='bf16' is written by the host-env engine's vec_host_tail: the device envs "
+                             "keep an fp32 ring")
         return self
 
 
@@ -290,8 +316,9 @@ class MLPDQNLearner:
             p.requires_grad_(False)
         self.P = self.flat.numel()
         self.obs_dim, self.A = self.model.input_shape[0], self.model.num_actions
-        if replay.frame_bytes != 4 * self.obs_dim:
-            raise ValueError("replay frame_bytes must be 4 * obs_dim")
+        self.ring_bf16 = cfg.ring_dtype == "bf16"
+        if replay.frame_bytes != ring_bytes(cfg.ring_dtype) * self.obs_dim:
+            raise ValueError(f"replay frame_bytes must be {ring_bytes(cfg.ring_dtype)} * obs_dim")
         if self.P != h.vec_param_count(self.obs_dim, self.A):
             raise ValueError("unexpected parameter count for the MLP dueling net")
         self.segments = self.model.param_segments()
@@ -329,21 +356,22 @@ class MLPDQNLearner:
                      else h.vec_grad_blocks(self.P))
         self.part = torch.zeros(self.nblk, dtype=torch.float64, device=dev)
         self.partials = torch.zeros(h.grad_norm_partials(), dtype=torch.float64, device=dev)
-        self.ring = replay.frames.view(torch.float32)
+        self.ring = replay.frames.view(torch.bfloat16 if self.ring_bf16 else torch.float32)
         self.net = vec_net(h, self.model)
         self.tnet = vec_net(h, self.target)
-        self._learn, self._grad = ((wide_kernel(h, "learn", cfg.wide_dtype, tall, cfg.tall_dtype),
-                                    wide_kernel(h, "grad", cfg.wide_dtype, tall, cfg.tall_dtype))
+        self._learn, self._grad = ((wide_kernel(h, "learn", cfg.wide_dtype, tall, cfg.tall_dtype, cfg.ring_dtype),
+                                    wide_kernel(h, "grad", cfg.wide_dtype, tall, cfg.tall_dtype, cfg.ring_dtype))
                                    if wide else (h.vec_learn, h.vec_grad))
         self.L = (h.make_vecw_learn if wide else h.make_vec_learn)(self.net, self.tnet, dict(
             replay.trans_ptrs(), ring=self.ring.data_ptr(), idx=self.idx.data_ptr(), w=self.w.data_ptr(), B=B,
             gamma_n=float(cfg.gamma ** cfg.n_step), q_s=self.q_s.data_ptr(), q_s2=self.q_s2.data_ptr(),
             qt_s2=self.qt_s2.data_ptr(), vec=self.vec.data_ptr(), delta=self.delta.data_ptr(),
             lw=self.lw.data_ptr(), step=self.step_counter.data_ptr(), beta_out=self.beta.data_ptr(),
-            beta0=float(cfg.beta), beta_horizon=float(cfg.beta_horizon)))
+            beta0=float(cfg.beta), beta_horizon=float(cfg.beta_horizon), ring_bf16=self.ring_bf16))
         g = (self.vec.data_ptr(), B, self.obs_dim, A, self.P, self.flat_grad.data_ptr(), self.part.data_ptr())
         if tall:   # dW0 reads the sampled observations where they lie: the ring, through the ids of s
-            self.G = h.make_vect_grad(*g, self.ring.data_ptr(), replay.trans_ptrs()["s_ids"], self.idx.data_ptr())
+            self.G = h.make_vect_grad(*g, self.ring.data_ptr(), replay.trans_ptrs()["s_ids"], self.idx.data_ptr(),
+                                      ring_bf16=self.ring_bf16)
         else:
             self.G = (h.make_vecw_grad if wide else h.make_vec_grad)(*g)
 

@@ -55,7 +55,11 @@ Shapes: observations to 8 floats and 7 actions (``kVecMaxObs`` / ``kVecMaxA``) b
 (``vecwb_*``: bf16 matrix-core operands, fp32 accumulation and master weights); ``tall_obs`` (with
 ``wide_net``, fp32) raises the observation limit to 1024 (``kVecTallMaxObs``) on the streamed kernels of
 ``ops/csrc/vector_tall_kernels.hip`` (``vect_*``), ``tall_dtype="bf16"`` takes those with bf16 operands
-(``ops/csrc/vector_tall_bf16_kernels.hip``, ``vectb_*``).  The side-stream
+(``ops/csrc/vector_tall_bf16_kernels.hip``, ``vectb_*``), and ``ring_dtype="bf16"`` (with those) stores the
+observation ring as bf16: ``vec_host_tail`` writes ``to_bf16`` of each staged row (nearest even, the rounding the
+``vectb_*`` kernels apply to an fp32 row at every read), the replay holds ``2 * obs_dim`` bytes per observation, the
+three kernels load the operand bits without converting, and every result is bit-equal to the fp32 ring's.  The
+staging block, the evaluators and :meth:`VectorHostShard.observe` stay fp32.  The side-stream
 evaluator follows the engine: over a wide engine its act is ``vecw_host_eval_act`` / ``vecwb_host_eval_act``
 (:mod:`apex_amd.engine.vector_host_eval`, through the API; ``train_vector
 --wide --eval-envs`` is still refused, the CLI's switch-over is a follow-up, so on the command line a
@@ -75,7 +79,7 @@ from .graphs import capture_graph
 from .hbm_replay import HBMReplay
 from .host_env import PinnedMirror
 from .shard import NStepShard
-from .vector import MLPDQNLearner, VectorEngineConfig, save_state_dict, vec_net, wide_kernel
+from .vector import MLPDQNLearner, VectorEngineConfig, ring_bytes, save_state_dict, vec_net, wide_kernel
 
 MAX_OBS = 8       # kVecMaxObs: the MLP kernels' widest observation
 MAX_ACTIONS = 7   # kVecMaxA: their widest action set
@@ -116,7 +120,7 @@ class VectorHostShard(NStepShard):
     def __init__(self, replay: HBMReplay, vec, n_step: int = 3, gamma: float = 0.99, eps_base: float = 0.4,
                  eps_alpha: float = 7.0, actor_offset: int = 0, total_actors: int | None = None, seed: int = 0,
                  mode: str = "reference", wide: bool = False, wide_dtype: str = "fp32", tall: bool = False,
-                 tall_dtype: str = "fp32"):
+                 tall_dtype: str = "fp32", ring_dtype: str = "fp32"):
         self.vec = vec
         self.wide = bool(wide)   # act with vecw_act; the tail takes the wide observation limit
         self.tall = bool(tall)   # (wide) act with vect_act; the tail takes the tall observation limit
@@ -124,14 +128,20 @@ class VectorHostShard(NStepShard):
         E = len(vec)
         if not 1 <= E <= 4096:
             raise ValueError("VectorHostShard: 1 <= envs <= 4096 (the actor step's one-launch tree write)")
-        if replay.frame_bytes != 4 * self.obs_dim:
-            raise ValueError(f"replay frame_bytes must be 4 * obs_dim = {4 * self.obs_dim}")
+        width = ring_bytes(ring_dtype)
+        self.ring_bf16 = width == 2   # vec_host_tail rounds the row once; vectb_act reads the bits
+        if self.ring_bf16 and not (self.wide and self.tall and tall_dtype == "bf16"):
+            raise ValueError("ring_dtype='bf16' is a layout of the tall bf16 kernels: pass wide, tall and "
+                             "tall_dtype='bf16'")
+        if replay.frame_bytes != width * self.obs_dim:
+            raise ValueError(f"replay frame_bytes must be {width} * obs_dim = {width * self.obs_dim}")
         super().__init__(replay, E, n_actions, n_step, gamma, eps_base, eps_alpha, actor_offset, total_actors, seed,
                          mode)
         # (vecwb_act for bf16, vect_act for tall)
-        self._wide_act = wide_kernel(self.hip, "act", wide_dtype, self.tall, tall_dtype) if self.wide else None
+        self._wide_act = (wide_kernel(self.hip, "act", wide_dtype, self.tall, tall_dtype, ring_dtype) if self.wide
+                          else None)
         h, dev = self.hip, self.device
-        self.ring = replay.frames.view(torch.float32)  # [F, obs_dim]
+        self.ring = replay.frames.view(torch.bfloat16 if self.ring_bf16 else torch.float32)  # [F, obs_dim]
         self.ep_ret = torch.zeros(E, dtype=torch.float32, device=dev)
         self.ep_len = torch.zeros(E, dtype=torch.float32, device=dev)
         # the staging block, shipped through its pinned twin, and its device copy
@@ -151,7 +161,7 @@ class VectorHostShard(NStepShard):
             ring=self.ring.data_ptr(), step=self.step_counter.data_ptr(), reward=self.reward.data_ptr(),
             done=self.done.data_ptr(), new_frame=self.new_frame.data_ptr(), hist=self.st["hist"].data_ptr(),
             ep_log=self.ep_log.data_ptr(), ep_ret=self.ep_ret.data_ptr(), ep_len=self.ep_len.data_ptr(),
-            wide=self.wide, tall=self.tall))
+            wide=self.wide, tall=self.tall, ring_bf16=self.ring_bf16))
         self._act = None
         self.env_steps = 0    # host env steps taken (all envs)
         self.host_seconds = 0.0   # wall time inside vec.step
@@ -166,9 +176,10 @@ class VectorHostShard(NStepShard):
             raise ValueError("policy shape does not match the env")
         self._policy = model
         make = self.hip.make_vecw_act if self.wide else self.hip.make_vec_act
+        kw = dict(ring_bf16=True) if self.ring_bf16 else {}
         self._act = make(vec_net(self.hip, model), self.ring.data_ptr(), self.st["hist"].data_ptr(), self.E,
                          self.eps.data_ptr(), self.act_seed, self.step_counter.data_ptr(), self.q.data_ptr(),
-                         self.actions.data_ptr())
+                         self.actions.data_ptr(), **kw)
 
     def reset(self) -> None:
         """Start every host env; their first observations into the ring (the reset form of
@@ -178,8 +189,9 @@ class VectorHostShard(NStepShard):
         self.hip.vec_host_tail(self._tail, True, self._stream())
 
     def observe(self) -> torch.Tensor:
-        """Current observations f32 [E, obs_dim] (a gather from the ring; allocates)."""
-        return self.ring[self.st["hist"][:, 3].long()]
+        """Current observations f32 [E, obs_dim] (a gather from the ring; allocates; over a bf16 ring the
+        stored, rounded values as floats)."""
+        return self.ring[self.st["hist"][:, 3].long()].float()
 
     def act(self) -> None:
         """Q of the current observations into ``self.q`` and the epsilon-greedy actions."""
@@ -252,13 +264,14 @@ class VectorHostEngine:
         torch.manual_seed(cfg.seed)
         model = DuelingDQN.from_shapes((self.obs_dim,), self.A)
         self.replay = HBMReplay(cfg.replay_capacity, cfg.n_envs, cfg.n_step, cfg.alpha, dev,
-                                frame_bytes=4 * self.obs_dim, seed=cfg.seed + 17)
+                                frame_bytes=ring_bytes(cfg.ring_dtype) * self.obs_dim, seed=cfg.seed + 17)
         self.learner = MLPDQNLearner(model, self.replay, cfg)
         self.actor_model = DuelingDQN.from_shapes((self.obs_dim,), self.A).to(dev)
         self.actor_flat = self.actor_model.flatten_parameters()
         self.shard = VectorHostShard(self.replay, vec, cfg.n_step, cfg.gamma, cfg.eps_base, cfg.eps_alpha,
                                      seed=cfg.seed * 0x2545F491 + 0xAC7, mode=cfg.nstep_mode, wide=cfg.wide_net,
-                                     wide_dtype=cfg.wide_dtype, tall=cfg.tall_obs, tall_dtype=cfg.tall_dtype)
+                                     wide_dtype=cfg.wide_dtype, tall=cfg.tall_obs, tall_dtype=cfg.tall_dtype,
+                                     ring_dtype=cfg.ring_dtype)
         self.shard._enqueued = lambda: self._enqueued()
         self.shard.set_policy(self.actor_model)
         self.publish_params()

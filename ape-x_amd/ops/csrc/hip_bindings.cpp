@@ -1130,7 +1130,7 @@ PYBIND11_MODULE(_apex_hip, m) {
   });
   // the acting step's env half over host envs (vector_host_kernels.hip); d: E, obs, F, stage, ring, step,
   // reward, done, new_frame, hist, ep_log, ep_ret, ep_len [+ wide: the wide net's observation limit; + tall: the
-  // tall net's]
+  // tall net's; + ring_bf16 (tall): `ring` is the bf16 ring of the tall bf16 kernels]
   py::class_<VecHostTail>(m, "VecHostTail");
   m.def("make_vec_host_tail", [](py::dict d) {
     auto g = [&](const char* k) { return d[k].cast<uint64_t>(); };
@@ -1142,6 +1142,7 @@ PYBIND11_MODULE(_apex_hip, m) {
     a.ep_len = P<float>(g("ep_len"));
     a.wide = d.contains("wide") && d["wide"].cast<bool>();
     a.tall = d.contains("tall") && d["tall"].cast<bool>();
+    a.ring_bf16 = d.contains("ring_bf16") && d["ring_bf16"].cast<bool>();
     return a;
   });
   m.def("vec_host_tail", [](const VecHostTail& a, bool reset, uint64_t s) { vec_host_tail(a, reset, S(s)); },
@@ -1232,6 +1233,7 @@ PYBIND11_MODULE(_apex_hip, m) {
     p.step = P<const int64_t>(opt("step")); p.beta_out = P<float>(opt("beta_out"));
     p.beta0 = d.contains("beta0") ? d["beta0"].cast<double>() : 0.4;
     p.beta_horizon = d.contains("beta_horizon") ? d["beta_horizon"].cast<double>() : 1000.0;
+    p.ring_bf16 = d.contains("ring_bf16") && d["ring_bf16"].cast<bool>();   // (vectb_learn's handle alone)
     return p;
   };
   m.def("make_vec_learn", make_learn);
@@ -1251,11 +1253,13 @@ PYBIND11_MODULE(_apex_hip, m) {
   m.def("vec_grad", [](const VecGrad& g, uint64_t s) { vec_grad(g, S(s)); });
   // the wide (MFMA) path of the same net (vector_wide_kernels.hip): make_vecw_* build vec_act's / vec_learn's /
   // vec_grad's handles, whose shapes the vecw launchers check against the wide limits
+  // (ring_bf16: `ring` is a bf16 ring -- the handle is vectb_act's alone)
   m.def("make_vecw_act", [](const VecNet& net, uint64_t ring, uint64_t hist, int E, uint64_t eps, uint64_t seed,
-                            uint64_t counter, uint64_t q, uint64_t actions) {
+                            uint64_t counter, uint64_t q, uint64_t actions, bool ring_bf16) {
     return VecAct{net, P<const float>(ring), P<const int>(hist), E, P<const float>(eps), seed,
-                  P<const int64_t>(counter), P<float>(q), P<int>(actions)};
-  });
+                  P<const int64_t>(counter), P<float>(q), P<int>(actions), ring_bf16};
+  }, py::arg("net"), py::arg("ring"), py::arg("hist"), py::arg("E"), py::arg("eps"), py::arg("seed"),
+     py::arg("counter"), py::arg("q"), py::arg("actions"), py::arg("ring_bf16") = false);
   m.def("vecw_act", [](const VecAct& a, uint64_t s) { vecw_act(a, S(s)); });
   m.def("make_vecw_learn", make_learn);
   m.def("vecw_learn", [](const VecLearn& p, uint64_t s) { vecw_learn(p, S(s)); });
@@ -1289,10 +1293,11 @@ PYBIND11_MODULE(_apex_hip, m) {
   m.def("vect_learn", [](const VecLearn& p, uint64_t s) { vect_learn(p, S(s)); });
   py::class_<VecTallGrad>(m, "VecTallGrad");
   m.def("make_vect_grad", [](uint64_t vec, int B, int obs, int A, int64_t n, uint64_t grad, uint64_t part,
-                             uint64_t ring, uint64_t s_ids, uint64_t idx) {
+                             uint64_t ring, uint64_t s_ids, uint64_t idx, bool ring_bf16) {
     return VecTallGrad{VecGrad{P<const float>(vec), B, obs, A, n, P<float>(grad), P<double>(part)},
-                       P<const float>(ring), P<const int>(s_ids), P<const int>(idx)};
-  });
+                       P<const float>(ring), P<const int>(s_ids), P<const int>(idx), ring_bf16};
+  }, py::arg("vec"), py::arg("B"), py::arg("obs"), py::arg("A"), py::arg("n"), py::arg("grad"), py::arg("part"),
+     py::arg("ring"), py::arg("s_ids"), py::arg("idx"), py::arg("ring_bf16") = false);
   m.def("vect_grad_blocks", &vect_grad_blocks);
   m.def("vect_grad", [](const VecTallGrad& g, uint64_t s) { vect_grad(g, S(s)); });
   // the tall mode with bf16 matrix-core operands (vector_tall_bf16_kernels.hip) over the same handles

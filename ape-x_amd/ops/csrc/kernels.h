@@ -937,6 +937,7 @@ struct VecHostTail {
   float* ep_len;         // [E] running length
   bool wide;             // obs up to kVecWideMaxObs (the wide net's shard) instead of kVecMaxObs
   bool tall;             // (with wide) obs up to kVecTallMaxObs: the tall net's shard
+  bool ring_bf16;        // (with tall) the ring is [F][obs] bf16: row = to_bf16(reset_obs[e]), nearest even
 };
 void vec_host_tail(const VecHostTail& a, bool reset, hipStream_t s);
 // Q[E][A] of the observations at ring row hist[e][3] + select_actions_k's epsilon-greedy draw
@@ -950,6 +951,7 @@ struct VecAct {
   const int64_t* counter;  // the shard's step counter
   float* q;                // [E][A]
   int* actions;            // [E]
+  bool ring_bf16;          // `ring` points at [F][obs] bf16 (vectb_act only; every other launcher refuses it)
 };
 void vec_act(const VecAct& a, hipStream_t s);
 // The act half of one greedy evaluator step over HOST envs in one launch (vector_kernels.hip
@@ -1008,6 +1010,7 @@ struct VecLearn {
   const int64_t* step;               // learner step counter (read)
   float* beta_out;                   // optional: beta_by_frame(step + 1, beta0, horizon) for the next draw
   double beta0, beta_horizon;
+  bool ring_bf16;                    // `ring` points at [F][obs] bf16 (vectb_learn only; the others refuse it)
 };
 void vec_learn(const VecLearn& p, hipStream_t s);
 struct VecGrad {
@@ -1055,6 +1058,7 @@ struct VecTallGrad {
   const float* ring;   // the replay's frame ring viewed as [F][obs] fp32
   const int* s_ids;    // [C][4] frame ids of s (observation = [3]), read through idx
   const int* idx;      // [B] sampled slots
+  bool ring_bf16;      // `ring` points at [F][obs] bf16 (vectb_grad only; vect_grad refuses it)
 };
 void vect_act(const VecAct& a, hipStream_t s);
 void vect_host_eval_act(const VecHostEvalAct& a, hipStream_t s);
@@ -1065,7 +1069,9 @@ void vect_grad(const VecTallGrad& g, hipStream_t s);
 // descriptors, row layout (vecw::X never written) and vect_grad_blocks tiles under vecwb_*'s precision
 // contract.  features.0 streams the observation through a double-buffered bf16 LDS slab of 256 columns
 // with the next round's fp32 weight loads in flight behind the current round's MFMAs; everything
-// after it is the bf16 wide kernels' code.
+// after it is the bf16 wide kernels' code.  With ring_bf16 set in the handle (VectorEngineConfig.ring_dtype =
+// "bf16") vectb_act / vectb_learn / vectb_grad read a bf16 ring written by vec_host_tail: the rows are the
+// operand bits (16-byte loads of 8 columns, no convert) and every result is bit-equal to the fp32 ring's.
 void vectb_act(const VecAct& a, hipStream_t s);
 void vectb_host_eval_act(const VecHostEvalAct& a, hipStream_t s);
 void vectb_learn(const VecLearn& p, hipStream_t s);

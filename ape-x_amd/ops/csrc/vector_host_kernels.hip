@@ -25,16 +25,42 @@
 // workgroup depends on another (nstep_emit bumps the step counter afterwards).  Only device memory
 // is touched, with vector loads and stores; every index is bounded by E, obs and F (checked by
 // the launcher).
+//
+// VecHostTail::ring_bf16 (the tall bf16 kernels' ring, VectorEngineConfig.ring_dtype = "bf16"): the ring
+// is [F][obs] bf16 and the row is to_bf16(reset_obs[e]) -- widebf16::to_bf16, the rounding (nearest even,
+// NaN and infinity as v_cvt_pk_bf16_f32 has them) the tall bf16 kernels apply to an fp32 row at every
+// read, here once at the write.  An even obs (rows 4-byte aligned): the thread of an even component
+// stores its pair as one dword and the odd one's stores nothing; an odd obs (rows 2-byte aligned): one
+// 2-byte store per thread.  The scalars are the fp32 form's.
 #include <stdexcept>
 
-#include "common.h"
-#include "kernels.h"
+#include <type_traits>
+
+#include "vector_wide_bf16_common.h"
 
 namespace apex {
 namespace {
 
 constexpr int kTailThreads = 256;
 
+// component k of ring row `slot` = reset_obs[i] (fp32 ring), its rounded value (bf16 ring)
+template <class RingT>
+__device__ __forceinline__ void store_row(const VecHostTail& T, const float* reset_obs, int i, int slot, int k) {
+  if constexpr (std::is_same<RingT, float>::value) {
+    T.ring[(size_t)slot * T.obs + k] = reset_obs[i];
+  } else {
+    __bf16* row = reinterpret_cast<__bf16*>(T.ring) + (size_t)slot * T.obs;
+    if (T.obs & 1) {
+      row[k] = widebf16::to_bf16(reset_obs[i]);
+    } else if (!(k & 1)) {   // k + 1 < obs: obs is even
+      typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+      const bf16x2 pair = {widebf16::to_bf16(reset_obs[i]), widebf16::to_bf16(reset_obs[i + 1])};
+      *reinterpret_cast<bf16x2*>(row + k) = pair;
+    }
+  }
+}
+
+template <class RingT>
 __global__ __launch_bounds__(kTailThreads) void vec_host_tail_k(VecHostTail T, int reset) {
   const int i = blockIdx.x * kTailThreads + threadIdx.x;
   const int E = T.E, obs = T.obs;
@@ -43,7 +69,7 @@ __global__ __launch_bounds__(kTailThreads) void vec_host_tail_k(VecHostTail T, i
   const float* reset_obs = T.stage + (size_t)E * obs;
   const int64_t step = T.step[0] + (reset ? 0 : 1);
   const int slot = (int)((step * E + e) % T.F);
-  T.ring[(size_t)slot * obs + k] = reset_obs[i];
+  store_row<RingT>(T, reset_obs, i, slot, k);
   if (k != 0) return;
   T.new_frame[e] = slot;
   float* lg = T.ep_log + (size_t)e * 4;
@@ -83,12 +109,16 @@ void vec_host_tail(const VecHostTail& a, bool reset, hipStream_t s) {
     throw std::invalid_argument(a.tall   ? "vec_host_tail: 1 <= obs <= 1024 (tall)"
                                 : a.wide ? "vec_host_tail: 1 <= obs <= 128 (wide)"
                                          : "vec_host_tail: 1 <= obs <= 8");
+  if (a.ring_bf16 && !a.tall) throw std::invalid_argument("vec_host_tail: a bf16 ring is the tall bf16 kernels' (tall)");
+  if (a.ring_bf16 && (reinterpret_cast<uintptr_t>(a.ring) & 3))
+    throw std::invalid_argument("vec_host_tail: a bf16 ring must be 4-byte aligned (the paired stores)");
   if (a.F < 2 * a.E) throw std::invalid_argument("vec_host_tail: ring must hold >= 2 E rows");
   if (!a.stage || !a.ring || !a.step || !a.reward || !a.done || !a.new_frame || !a.hist || !a.ep_log || !a.ep_ret ||
       !a.ep_len)
     throw std::invalid_argument("vec_host_tail: missing buffers");
   const int n = a.E * a.obs;
-  vec_host_tail_k<<<(n + kTailThreads - 1) / kTailThreads, kTailThreads, 0, s>>>(a, reset ? 1 : 0);
+  (a.ring_bf16 ? vec_host_tail_k<__bf16> : vec_host_tail_k<float>)<<<(n + kTailThreads - 1) / kTailThreads,
+                                                                    kTailThreads, 0, s>>>(a, reset ? 1 : 0);
   LAUNCH_CHECK();
 }
 

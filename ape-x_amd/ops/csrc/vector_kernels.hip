@@ -744,6 +744,7 @@ void vec_classic_step(const VecEnv& V, const int* actions, const int64_t* step_c
 }
 
 void vec_act(const VecAct& a, hipStream_t s) {
+  if (a.ring_bf16) throw std::invalid_argument("vec_act: a bf16 ring is read by the tall bf16 kernels (vectb_*) only");
   check_net(a.net, "vec_act");
   if (a.E < 1 || !a.ring || !a.hist || !a.eps || !a.q || !a.actions)
     throw std::invalid_argument("vec_act: E >= 1 with ring, hist, eps, q and actions");
@@ -794,6 +795,7 @@ void vec_rollout(const VecRollout& r, hipStream_t s) {
 }
 
 void vec_learn(const VecLearn& p, hipStream_t s) {
+  if (p.ring_bf16) throw std::invalid_argument("vec_learn: a bf16 ring is read by the tall bf16 kernels (vectb_*) only");
   check_net(p.on, "vec_learn (online)");
   check_net(p.tg, "vec_learn (target)");
   if (p.on.obs != p.tg.obs || p.on.A != p.tg.A) throw std::invalid_argument("vec_learn: nets differ in shape");

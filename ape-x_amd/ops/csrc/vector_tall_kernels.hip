@@ -255,6 +255,7 @@ void check_tall_net(const VecNet& n, const char* who) {
 
 // ------------------------------------------------------------------ launchers
 void vect_act(const VecAct& a, hipStream_t s) {
+  if (a.ring_bf16) throw std::invalid_argument("vect_act: a bf16 ring is read by the tall bf16 kernels (vectb_*) only");
   check_tall_net(a.net, "vect_act");
   if (a.E < 1 || a.E > 4096 || !a.ring || !a.hist || !a.eps || !a.q || !a.actions)
     throw std::invalid_argument("vect_act: 1 <= E <= 4096 with ring, hist, eps, q and actions");
@@ -273,6 +274,7 @@ void vect_host_eval_act(const VecHostEvalAct& a, hipStream_t s) {
 }
 
 void vect_learn(const VecLearn& p, hipStream_t s) {
+  if (p.ring_bf16) throw std::invalid_argument("vect_learn: a bf16 ring is read by the tall bf16 kernels (vectb_*) only");
   check_tall_net(p.on, "vect_learn (online)");
   check_tall_net(p.tg, "vect_learn (target)");
   if (p.on.obs != p.tg.obs || p.on.A != p.tg.A) throw std::invalid_argument("vect_learn: nets differ in shape");
@@ -292,6 +294,7 @@ int vect_grad_blocks(int obs, int A) {
 }
 
 void vect_grad(const VecTallGrad& G, hipStream_t s) {
+  if (G.ring_bf16) throw std::invalid_argument("vect_grad: a bf16 ring is read by the tall bf16 kernels (vectb_*) only");
   const VecGrad& g = G.g;
   if (g.obs < 1 || g.obs > kVecTallMaxObs || g.A < 1 || g.A > kVecWideMaxA || g.n != vec_param_count(g.obs, g.A))
     throw std::invalid_argument("vect_grad: n must be the MLP dueling net's parameter count");

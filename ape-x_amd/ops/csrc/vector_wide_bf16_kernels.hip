@@ -200,6 +200,7 @@ void check_wide_net(const VecNet& n, const char* who) {
 
 // ------------------------------------------------------------------ launchers
 void vecwb_act(const VecAct& a, hipStream_t s) {
+  if (a.ring_bf16) throw std::invalid_argument("vecwb_act: a bf16 ring is read by the tall bf16 kernels (vectb_*) only");
   check_wide_net(a.net, "vecwb_act");
   if (a.E < 1 || a.E > 4096 || !a.ring || !a.hist || !a.eps || !a.q || !a.actions)
     throw std::invalid_argument("vecwb_act: 1 <= E <= 4096 with ring, hist, eps, q and actions");
@@ -218,6 +219,7 @@ void vecwb_host_eval_act(const VecHostEvalAct& a, hipStream_t s) {
 }
 
 void vecwb_learn(const VecLearn& p, hipStream_t s) {
+  if (p.ring_bf16) throw std::invalid_argument("vecwb_learn: a bf16 ring is read by the tall bf16 kernels (vectb_*) only");
   check_wide_net(p.on, "vecwb_learn (online)");
   check_wide_net(p.tg, "vecwb_learn (target)");
   if (p.on.obs != p.tg.obs || p.on.A != p.tg.A) throw std::invalid_argument("vecwb_learn: nets differ in shape");

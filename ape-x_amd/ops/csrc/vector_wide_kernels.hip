@@ -235,6 +235,7 @@ void check_wide_net(const VecNet& n, const char* who) {
 
 // ------------------------------------------------------------------ launchers
 void vecw_act(const VecAct& a, hipStream_t s) {
+  if (a.ring_bf16) throw std::invalid_argument("vecw_act: a bf16 ring is read by the tall bf16 kernels (vectb_*) only");
   check_wide_net(a.net, "vecw_act");
   if (a.E < 1 || a.E > 4096 || !a.ring || !a.hist || !a.eps || !a.q || !a.actions)
     throw std::invalid_argument("vecw_act: 1 <= E <= 4096 with ring, hist, eps, q and actions");
@@ -253,6 +254,7 @@ void vecw_host_eval_act(const VecHostEvalAct& a, hipStream_t s) {
 }
 
 void vecw_learn(const VecLearn& p, hipStream_t s) {
+  if (p.ring_bf16) throw std::invalid_argument("vecw_learn: a bf16 ring is read by the tall bf16 kernels (vectb_*) only");
   check_wide_net(p.on, "vecw_learn (online)");
   check_wide_net(p.tg, "vecw_learn (target)");
   if (p.on.obs != p.tg.obs || p.on.A != p.tg.A) throw std::invalid_argument("vecw_learn: nets differ in shape");

@@ -30,7 +30,9 @@ kernels (``VectorEngineConfig.wide_net``): a host env may then have up to 128 ob
 and 32 actions; ``--wide --dtype bf16`` takes their bf16-operand variants (``wide_dtype``: bf16
 matrix-core operands, fp32 accumulation, fp32 master weights and checkpoints); ``--host-envs --wide
 --tall`` takes the streamed fp32 kernels (``tall_obs``, ``vect_*``): up to 1024 observation floats;
-``--host-envs --wide --tall --dtype bf16`` takes those with bf16 operands (``tall_dtype``, ``vectb_*``).
+``--host-envs --wide --tall --dtype bf16`` takes those with bf16 operands (``tall_dtype``, ``vectb_*``);
+``--ring-dtype bf16`` (with exactly those flags) stores the observation ring as bf16 (``ring_dtype``: half the
+replay's observation bytes, the same numbers bit for bit).
 ``--wide`` is still refused with ``--eval-envs``: the evaluator itself takes a wide engine
 (``vecw_host_eval_act``, :mod:`apex_amd.engine.vector_host_eval`), this command line's switch-over is
 a follow-up; the blocking evaluator and the reference-format checkpoints work as they are.
@@ -65,6 +67,9 @@ class _Parser(argparse.ArgumentParser):
             self.error("--dtype bf16 is a mode of the wide kernels: pass --wide")
         if a.tall and not (a.host_envs and a.wide):
             self.error("--tall is a mode of the wide kernels on host envs: pass --host-envs --wide")
+        if a.ring_dtype != "fp32" and not (a.tall and a.dtype == "bf16"):
+            self.error("--ring-dtype bf16 is a layout of the tall bf16 kernels: pass --host-envs --wide --tall "
+                       "--dtype bf16")
         if a.host_envs:
             if a.eval_mode != "step":
                 self.error("--host-envs evaluates on the host: --eval-mode must be 'step'")
@@ -112,6 +117,9 @@ def parser() -> argparse.ArgumentParser:
                         "--tall vectb_*)")
     p.add_argument("--tall", action="store_true",
                    help="(--host-envs --wide) the streamed fp32-MFMA kernels (vect_*): flat observation <= 1024")
+    p.add_argument("--ring-dtype", default="fp32", choices=["fp32", "bf16"],
+                   help="(--host-envs --wide --tall --dtype bf16) bf16: the observation ring stored as bf16, rounded "
+                        "once at the write; results are bit-equal to the fp32 ring's")
     p.add_argument("--learner-steps", type=int, default=1, help="(--host-envs) SGD steps per env step")
     p.add_argument("--host-serial", action="store_true",
                    help="(--host-envs) learner steps, then the acting step: no overlap with the host's env step")
@@ -162,7 +170,8 @@ def config_from_args(a) -> VectorEngineConfig:
                               nstep_mode=a.nstep_mode, target_update_interval=a.target_update_interval,
                               publish_param_interval=a.publish_interval, seed=a.seed,
                               wide_net=a.wide, wide_dtype="fp32" if a.tall else a.dtype, tall_obs=a.tall,
-                              tall_dtype=a.dtype if a.tall else "fp32").validate(not a.host_envs)
+                              tall_dtype=a.dtype if a.tall else "fp32",
+                              ring_dtype=a.ring_dtype).validate(not a.host_envs)
 
 
 def _crossed(t: int, prev: int, interval: int) -> bool:

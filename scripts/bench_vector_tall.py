@@ -14,6 +14,10 @@
 with ``vect_*`` inside every repetition at obs 128 / 256 / 512 / 1024, B 64 / 512, the two acts at E = 16 and
 4096, and the captured loop at obs 1024 / B 64 for both.
 
+``--ring`` measures ``vectb_*`` over the bf16 observation ring against the fp32 ring (profiles/vector_tall_bf16_ring.md),
+alternated inside every repetition: the act at obs 1024, E = 16 and 4096; learn / grad / pair at obs 256 / 512 / 1024,
+B 512; the captured loop at obs 1024 / B 64, its windows alternated between the two engines.
+
 One JSON line per shape."""
 import argparse
 import json
@@ -28,7 +32,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from bench_vector_wide_bf16 import _us  # noqa: E402
 
 
-def _engine(a, obs, B, tall, k=1, envs=64, tall_dtype="fp32"):
+def _engine(a, obs, B, tall, k=1, envs=64, tall_dtype="fp32", ring_dtype="fp32"):
     from bench_vector_host_eval import wide_env
 
     from apex_amd.engine.vector import VectorEngineConfig
@@ -37,15 +41,16 @@ def _engine(a, obs, B, tall, k=1, envs=64, tall_dtype="fp32"):
 
     vec = HostVectorEnv([lambda: wide_env(f"wide-{obs}x18")] * envs, seed=a.seed, max_obs=1024)
     cfg = VectorEngineConfig(env_id=f"wide-{obs}x18", batch_size=B, replay_capacity=16384, wide_net=True,
-                             tall_obs=tall, tall_dtype=tall_dtype, seed=a.seed)
+                             tall_obs=tall, tall_dtype=tall_dtype, ring_dtype=ring_dtype, seed=a.seed)
     return VectorHostEngine(cfg, vec, "cuda:0", learner_steps=k)
 
 
 def kernels(a, obs, B, modes):
-    """``modes``: the (name, tall[, tall_dtype]) variants measured on this shape, alternated."""
+    """``modes``: the (name, tall[, tall_dtype[, ring_dtype]]) variants measured on this shape, alternated."""
     import torch
 
-    engs = {n: _engine(a, obs, B, t, tall_dtype=(d or ["fp32"])[0]) for n, t, *d in modes}
+    engs = {n: _engine(a, obs, B, t, tall_dtype=(d + ["fp32"])[0], ring_dtype=(d + ["fp32"] * 2)[1])
+            for n, t, *d in modes}
     f = {}
     for n, e in engs.items():
         e.fill(4 * B)
@@ -70,7 +75,8 @@ def kernels(a, obs, B, modes):
     return out
 
 
-def act(a, obs, E, tall_dtype="fp32"):
+def act(a, obs, E, tall_dtype="fp32", ring_dtypes=("fp32",)):
+    """``ring_dtypes``: one shard per ring, alternated inside every repetition."""
     import numpy as np
     import torch
 
@@ -90,15 +96,26 @@ def act(a, obs, E, tall_dtype="fp32"):
         def reset(self):
             self.staging[E * obs:2 * E * obs] = np.random.default_rng(a.seed).standard_normal(E * obs)
 
-    rp = HBMReplay(max(4096, 4 * E), n_envs=E, n_step=3, device="cuda:0", frame_bytes=4 * obs)
-    sh = VectorHostShard(rp, Rows(), seed=a.seed, wide=True, tall=True, tall_dtype=tall_dtype)
-    sh.set_policy(DuelingDQN.from_shapes((obs,), 18).to("cuda:0"))
-    _us(sh.act, 50)
-    v = [_us(sh.act, a.launches) for _ in range(a.reps)]
-    sh.close()
-    name = "vectb_act_us" if tall_dtype == "bf16" else "vect_act_us"
-    return dict(what="act", obs=obs, A=18, E=E, **{name: round(statistics.median(v), 2)},
-                spread=round((max(v) - min(v)) / statistics.median(v), 4))
+    shards = {}
+    for rd in ring_dtypes:
+        rp = HBMReplay(max(4096, 4 * E), n_envs=E, n_step=3, device="cuda:0", frame_bytes=(2 if rd == "bf16" else 4) * obs)
+        sh = VectorHostShard(rp, Rows(), seed=a.seed, wide=True, tall=True, tall_dtype=tall_dtype, ring_dtype=rd)
+        sh.set_policy(DuelingDQN.from_shapes((obs,), 18).to("cuda:0"))
+        _us(sh.act, 50)
+        shards[rd] = sh
+    v = {rd: [] for rd in shards}
+    for _ in range(a.reps):
+        for rd, sh in shards.items():
+            v[rd].append(_us(sh.act, a.launches))
+    for sh in shards.values():
+        sh.close()
+    name = "vectb_act" if tall_dtype == "bf16" else "vect_act"
+    out = dict(what="act", obs=obs, A=18, E=E)
+    for rd, t in v.items():
+        tag = name + ("" if len(v) == 1 else "_ring_" + rd)
+        out[tag + "_us"] = round(statistics.median(t), 2)
+        out["spread" if len(v) == 1 else tag + "_spread"] = round((max(t) - min(t)) / statistics.median(t), 4)
+    return out
 
 
 def loop(a, obs, B, tall_dtype="fp32"):
@@ -122,6 +139,35 @@ def loop(a, obs, B, tall_dtype="fp32"):
     return dict(what="loop", tall_dtype=tall_dtype, obs=obs, A=18, B=B, K=a.k, envs=64,
                 sgd_steps_per_s=round(statistics.median(rate)),
                 spread=round((max(rate) - min(rate)) / statistics.median(rate), 4))
+
+
+def ring_loop(a, obs, B):
+    """``loop`` for the fp32 and the bf16 ring in one process, the timed windows alternated."""
+    import torch
+
+    engs = {rd: _engine(a, obs, B, True, a.k, tall_dtype="bf16", ring_dtype=rd) for rd in ("fp32", "bf16")}
+    for e in engs.values():
+        e.fill(4 * B)
+        e.capture()
+        for _ in range(50):
+            e.train_step()
+    torch.cuda.synchronize()
+    rate = {rd: [] for rd in engs}
+    for _ in range(a.reps):
+        for rd, e in engs.items():
+            n, t0 = 0, time.perf_counter()
+            while time.perf_counter() - t0 < a.seconds:
+                e.train_step()
+                n += 1
+            torch.cuda.synchronize()
+            rate[rd].append(n * e.K / (time.perf_counter() - t0))
+    out = dict(what="ring_loop", obs=obs, A=18, B=B, K=a.k, envs=64)
+    for rd, e in engs.items():
+        out[f"sgd_steps_per_s_ring_{rd}"] = round(statistics.median(rate[rd]))
+        out[f"spread_ring_{rd}"] = round((max(rate[rd]) - min(rate[rd])) / statistics.median(rate[rd]), 4)
+        out[f"replay_obs_bytes_ring_{rd}"] = e.replay.frame_bytes
+        e.close()
+    return out
 
 
 def cli(a):
@@ -153,7 +199,17 @@ def main():
     ap.add_argument("--cli-steps", type=int, default=2000)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--vectb", action="store_true", help="vectb_* against vect_* (profiles/vector_tall_bf16.md)")
+    ap.add_argument("--ring", action="store_true",
+                    help="vectb_* over a bf16 ring against the fp32 ring (profiles/vector_tall_bf16_ring.md)")
     a = ap.parse_args()
+    if a.ring:
+        for E in (16, 4096):
+            print(json.dumps(act(a, 1024, E, "bf16", ("fp32", "bf16"))), flush=True)
+        for obs in (256, 512, 1024):
+            modes = (("ring_fp32", True, "bf16", "fp32"), ("ring_bf16", True, "bf16", "bf16"))
+            print(json.dumps(kernels(a, obs, 512, modes)), flush=True)
+        print(json.dumps(ring_loop(a, 1024, 64)), flush=True)
+        return
     if a.vectb:
         for E in (16, 4096):
             for dt in ("fp32", "bf16"):
