@@ -67,10 +67,15 @@ class DQNEngineConfig:
     target_update_interval: int = 1000
     exact_mass: bool = False         # False: the reference's exclusive-end mass
     max_episode_steps: int | None = None   # None: the env's registered TimeLimit
+    noisy_heads: bool = False        # refused: see validate()
     seed: int = 0
 
     def validate(self) -> "DQNEngineConfig":
         env_spec(self.env_id)
+        if self.noisy_heads:
+            raise ValueError("noisy_heads is an option of the vector Ape-X engines (engine/vector.py, "
+                             "engine/vector_host.py): dqn_frame acts on the online net in place, with no "
+                             "effective weight set to compose")
         if not 1 <= self.n_envs <= MAX_ENVS:
             raise ValueError(f"n_envs must be in [1, {MAX_ENVS}] (one workgroup's forward pass)")
         if not 1 <= self.batch_size <= MAX_BATCH:

@@ -50,6 +50,22 @@ load the operand bits themselves, 8 columns per 16-byte load, with no conversion
 kernels apply to an fp32 row at every read, so every result is bit-equal to the fp32 ring's at half the
 observation bytes in the replay.
 
+``noisy_heads=True`` (any of the modes above) makes ``advantage.{0,2}`` and ``value.{0,2}`` the reference's
+factorised-Gaussian ``NoisyLinear`` (``models/noisy.py``, ``std_init`` 0.4).  One noise sample serves a whole
+forward, so the layer is ``F.linear(x, mu + sigma * eps)``: the learner keeps the noisy MASTER model (``mu``,
+``sigma``; ``P_n`` floats, the optimizer's buffer) and plain ten-tensor EFFECTIVE sets for the online, target and
+acting nets, and every launch above runs over those, untouched.  ``ops/csrc/vector_noisy_kernels.hip`` adds two
+launches to the SGD step (7 in all): ``per_sample`` -> ``*_learn`` -> ``*_grad`` -> ``vecn_grad`` (effective gradient
+-> ``d mu = g``, ``d sigma = g * eps`` + the fp64 norm partials of the master gradient, the ones ``rmsprop_step``
+clips by) -> ``rmsprop_step`` over the master -> ``vecn_compose`` (fresh Philox noise keyed by the device step
+counter and the effective weights of the online AND target nets, one launch: the reference's ``reset_noise()`` per
+update) -> ``per_write_batch``.  At every ``*_learn`` launch each effective set is compose(master, the noise in that
+net's ``weight_epsilon`` / ``bias_epsilon`` buffers); ``sync_target`` re-composes the target from its copied master
+and the noise it holds.  ``publish_params`` composes the acting set with noise of its own, redrawn at each publish.
+The epsilon ladder still applies on top: ``eps_base=0`` gives pure noisy exploration.  Every greedy evaluation
+(``evaluate``, ``rollout_evaluate``, :class:`VectorEvaluator`, the host evaluators' weight sets) reads ``mu`` through
+the ``noise = 0`` compose.
+
 Serial actor-then-learner on one stream; overlap and multi-GPU topologies are the Atari
 engine's and are not offered here.  Envs other than ``VECTOR_ENVS`` -- any gym-API env with a
 flat observation and a discrete action space, stepped on the CPU -- train under the same
@@ -88,10 +104,10 @@ def env_spec(env_id: str) -> tuple[int, int, int, int]:
     return VECTOR_ENVS[env_id]
 
 
-def make_model(env_id: str) -> DuelingDQN:
-    """The MLP ``DuelingDQN`` of ``env_id`` (reference state_dict keys)."""
+def make_model(env_id: str, noisy: bool = False) -> DuelingDQN:
+    """The MLP ``DuelingDQN`` of ``env_id`` (reference state_dict keys); ``noisy``: NoisyLinear heads."""
     _, obs, n_actions, _ = env_spec(env_id)
-    return DuelingDQN.from_shapes((obs,), n_actions)
+    return DuelingDQN.from_shapes((obs,), n_actions, noisy=noisy)
 
 
 def save_state_dict(model: DuelingDQN, path: str) -> str:
@@ -255,6 +271,7 @@ class VectorEngineConfig:
     tall_obs: bool = False           # (wide_net, fp32) the streamed kernels (vect_*): obs <= 1024
     tall_dtype: str = "fp32"         # (tall_obs) "bf16": the streamed kernels with bf16 operands (vectb_*)
     ring_dtype: str = "fp32"         # (tall_dtype "bf16", host envs) "bf16": the observation ring stored as bf16
+    noisy_heads: bool = False        # NoisyLinear advantage / value heads (vecn_*); eps_base=0: noise alone explores
     seed: int = 0
 
     def validate(self, device_env: bool = True) -> "VectorEngineConfig":
@@ -307,6 +324,9 @@ class MLPDQNLearner:
         self.cfg = cfg
         self.replay = replay
         self.device = dev = replay.device
+        self.noisy = bool(cfg.noisy_heads)
+        if self.noisy != bool(getattr(model, "noisy", False)):
+            raise ValueError("noisy_heads and the model disagree: build it with DuelingDQN.from_shapes(noisy=...)")
         self.model = model.to(dev)
         self.flat = self.model.flatten_parameters()
         self.target = copy.deepcopy(self.model)
@@ -314,26 +334,38 @@ class MLPDQNLearner:
         self.tflat = self.target.flatten_parameters()
         for p in self.target.parameters():
             p.requires_grad_(False)
-        self.P = self.flat.numel()
         self.obs_dim, self.A = self.model.input_shape[0], self.model.num_actions
+        self.P_opt = self.flat.numel()   # the optimizer's buffer (the master): P, or P_n under noisy_heads
+        if self.noisy:
+            # plain holders of the effective weights: what self.net / self.tnet (and every launch) read
+            self.P = int(h.vec_param_count(self.obs_dim, self.A))
+            if self.P_opt != h.vecn_param_count(self.obs_dim, self.A):
+                raise ValueError("unexpected parameter count for the noisy MLP dueling net")
+            self.net_model, self.eff = self._plain_holder()
+            self.tnet_model, self.teff = self._plain_holder()
+        else:
+            self.P = self.P_opt
+            self.net_model, self.tnet_model = self.model, self.target
         self.ring_bf16 = cfg.ring_dtype == "bf16"
         if replay.frame_bytes != ring_bytes(cfg.ring_dtype) * self.obs_dim:
             raise ValueError(f"replay frame_bytes must be {ring_bytes(cfg.ring_dtype)} * obs_dim")
         if self.P != h.vec_param_count(self.obs_dim, self.A):
             raise ValueError("unexpected parameter count for the MLP dueling net")
         self.segments = self.model.param_segments()
-        assert tuple(n for n, _, _ in self.segments) == PARAM_KEYS
+        assert self.noisy or tuple(n for n, _, _ in self.segments) == PARAM_KEYS
         B, A = int(cfg.batch_size), self.A
         self.B = B
         f32 = dict(dtype=torch.float32, device=dev)
-        self.flat_grad = torch.zeros(self.P, **f32)
+        self.flat_grad = torch.zeros(self.P_opt, **f32)   # the optimizer's gradient (over the master)
+        # what the *_grad launch writes: the gradient over the effective layout (noisy_heads), else the same buffer
+        self.eff_grad = torch.zeros(self.P, **f32) if self.noisy else self.flat_grad
         off = 0
         for p in self.model.parameters():
             n = p.numel()
             p.grad = self.flat_grad[off:off + n].view_as(p)
             off += n
-        self.opt_s1 = torch.zeros(self.P, **f32)
-        self.opt_s2 = torch.zeros(self.P, **f32)
+        self.opt_s1 = torch.zeros(self.P_opt, **f32)
+        self.opt_s2 = torch.zeros(self.P_opt, **f32)
         self.hp = h.RMSpropParams(cfg.lr, cfg.rms_alpha, cfg.rms_eps, cfg.max_norm, cfg.lr_gamma, cfg.lr_step_size,
                                   cfg.lr_step_offset, cfg.centered)
         self.idx = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -357,8 +389,8 @@ class MLPDQNLearner:
         self.part = torch.zeros(self.nblk, dtype=torch.float64, device=dev)
         self.partials = torch.zeros(h.grad_norm_partials(), dtype=torch.float64, device=dev)
         self.ring = replay.frames.view(torch.bfloat16 if self.ring_bf16 else torch.float32)
-        self.net = vec_net(h, self.model)
-        self.tnet = vec_net(h, self.target)
+        self.net = vec_net(h, self.net_model)
+        self.tnet = vec_net(h, self.tnet_model)
         self._learn, self._grad = ((wide_kernel(h, "learn", cfg.wide_dtype, tall, cfg.tall_dtype, cfg.ring_dtype),
                                     wide_kernel(h, "grad", cfg.wide_dtype, tall, cfg.tall_dtype, cfg.ring_dtype))
                                    if wide else (h.vec_learn, h.vec_grad))
@@ -368,12 +400,83 @@ class MLPDQNLearner:
             qt_s2=self.qt_s2.data_ptr(), vec=self.vec.data_ptr(), delta=self.delta.data_ptr(),
             lw=self.lw.data_ptr(), step=self.step_counter.data_ptr(), beta_out=self.beta.data_ptr(),
             beta0=float(cfg.beta), beta_horizon=float(cfg.beta_horizon), ring_bf16=self.ring_bf16))
-        g = (self.vec.data_ptr(), B, self.obs_dim, A, self.P, self.flat_grad.data_ptr(), self.part.data_ptr())
+        g = (self.vec.data_ptr(), B, self.obs_dim, A, self.P, self.eff_grad.data_ptr(), self.part.data_ptr())
         if tall:   # dW0 reads the sampled observations where they lie: the ring, through the ids of s
             self.G = h.make_vect_grad(*g, self.ring.data_ptr(), replay.trans_ptrs()["s_ids"], self.idx.data_ptr(),
                                       ring_bf16=self.ring_bf16)
         else:
             self.G = (h.make_vecw_grad if wide else h.make_vec_grad)(*g)
+        if self.noisy:
+            self._init_noisy()
+
+    # ------------------------------------------------------------------ noisy heads (vector_noisy_kernels.hip)
+    def _plain_holder(self) -> tuple[DuelingDQN, torch.Tensor]:
+        m = DuelingDQN.from_shapes((self.obs_dim,), self.A).to(self.device)
+        for p in m.parameters():
+            p.requires_grad_(False)
+        return m, m.flatten_parameters()
+
+    @staticmethod
+    def _eps_ptrs(model: DuelingDQN) -> dict:
+        ls = model.noisy_layers()
+        return dict(weps=[m.weight_epsilon.data_ptr() for m in ls], beps=[m.bias_epsilon.data_ptr() for m in ls])
+
+    def _compose(self, sets: list, mode: int, ahead: int = 0):
+        """A ``vecn_compose`` handle: mode 1 draws (key: the step counter + ``ahead``), 2 keeps the noise in the
+        epsilon buffers, 0 writes ``mu``."""
+        return self.hip.make_vecn_compose(sets, self.obs_dim, self.A, mode, self.noise_seed,
+                                          self.step_counter.data_ptr(), ahead)
+
+    def _init_noisy(self) -> None:
+        h, cfg = self.hip, self.cfg
+        self.noise_seed = (cfg.seed * 0x9E3779B1 + 0x4E01) & 0x7FFFFFFFFFFFFFFF
+        self.nparts = int(h.vecn_blocks(self.obs_dim, self.A))
+        self.npart = torch.zeros(self.nparts, dtype=torch.float64, device=self.device)
+        eps = self._eps_ptrs(self.model)
+        self.NG = h.make_vecn_grad(self.eff_grad.data_ptr(), self.flat_grad.data_ptr(), eps["weps"], eps["beps"],
+                                   self.obs_dim, self.A, self.npart.data_ptr())
+        on = dict(master=self.flat.data_ptr(), eff=self.eff.data_ptr(), net=0, **eps)
+        tg = dict(master=self.tflat.data_ptr(), eff=self.teff.data_ptr(), net=1, **self._eps_ptrs(self.target))
+        # the noise in use at learner step k is keyed by k: the step's own compose draws step k + 1's
+        self._c_step = self._compose([on, tg], 1, ahead=1)
+        self._c_keep = self._compose([on, tg], 2)
+        # the acting copy's noise record (its effective set is the engine's actor model)
+        self.actor_noise = DuelingDQN.from_shapes((self.obs_dim,), self.A, noisy=True).to(self.device)
+        self._c_actor = {}
+        self.eval_model, self.eval_flat = self._plain_holder()   # mu: the greedy evaluations' set
+        self.eval_net = vec_net(h, self.eval_model)
+        self._c_eval = self._compose([dict(master=self.flat.data_ptr(), eff=self.eval_flat.data_ptr(), net=0)], 0)
+        h.vecn_compose(self._compose([on, tg], 1, ahead=0), self._stream())
+
+    def compose(self) -> None:
+        """Fresh noise and the effective weights of the online and target nets (one launch)."""
+        self.hip.vecn_compose(self._c_step, self._stream())
+
+    def refresh_effective(self) -> None:
+        """Both effective sets again from the masters as they are and the noise the epsilon buffers hold (after
+        a target sync, or after the master parameters were written from outside)."""
+        self.hip.vecn_compose(self._c_keep, self._stream())
+
+    def greedy_net(self):
+        """The ``VecNet`` greedy evaluation reads: the online net, under ``noisy_heads`` its ``mu`` (composed
+        here, on the current stream, into a set of its own)."""
+        if not self.noisy:
+            return self.net
+        self.hip.vecn_compose(self._c_eval, self._stream())
+        return self.eval_net
+
+    def publish_to(self, dst_flat: torch.Tensor) -> None:
+        """The acting copy: the online parameters, under ``noisy_heads`` composed with noise of its own (net 2),
+        redrawn at every call and recorded in ``actor_noise``'s epsilon buffers."""
+        if not self.noisy:
+            return self.copy_params_to(dst_flat)
+        if dst_flat.numel() != self.P:
+            raise ValueError("the acting copy holds the plain parameter set")
+        c = self._c_actor.get(dst_flat.data_ptr())
+        if c is None:
+            c = self._c_actor[dst_flat.data_ptr()] = self._compose(
+                [dict(master=self.flat.data_ptr(), eff=dst_flat.data_ptr(), net=2, **self._eps_ptrs(self.actor_noise))], 1)
+        self.hip.vecn_compose(c, self._stream())
 
     @staticmethod
     def _stream() -> int:
@@ -387,16 +490,20 @@ class MLPDQNLearner:
         s = self._stream()
         self._learn(self.L, s)
         self._grad(self.G, s)
+        if self.noisy:   # effective gradient -> master gradient + ITS norm partials (self.part is W_eff's norm)
+            self.hip.vecn_grad(self.NG, s)
 
     def optimize(self) -> None:
         h, s = self.hip, self._stream()
-        if self.cfg.fused_norm:
-            parts, nparts = self.part, self.nblk
-        else:
-            h.grad_sumsq(self.flat_grad.data_ptr(), self.P, self.partials.data_ptr(), s)
+        if not self.cfg.fused_norm:
+            h.grad_sumsq(self.flat_grad.data_ptr(), self.P_opt, self.partials.data_ptr(), s)
             parts, nparts = self.partials, self.partials.numel()
+        elif self.noisy:
+            parts, nparts = self.npart, self.nparts
+        else:
+            parts, nparts = self.part, self.nblk
         h.rmsprop_step(self.flat.data_ptr(), self.flat_grad.data_ptr(), self.opt_s1.data_ptr(),
-                       self.opt_s2.data_ptr(), self.P, parts.data_ptr(), nparts, self.hp,
+                       self.opt_s2.data_ptr(), self.P_opt, parts.data_ptr(), nparts, self.hp,
                        self.step_counter.data_ptr(), self.norms.data_ptr(), s)
 
     def write_priorities(self) -> None:
@@ -408,12 +515,23 @@ class MLPDQNLearner:
         self.sample()
         self.forward_backward()
         self.optimize()
+        if self.noisy:
+            self.compose()
         self.write_priorities()
 
     def sync_target(self) -> None:
-        self.hip.copy_f32(self.tflat.data_ptr(), self.flat.data_ptr(), self.P, self._stream())
+        self.hip.copy_f32(self.tflat.data_ptr(), self.flat.data_ptr(), self.P_opt, self._stream())
+        if self.noisy:   # the target's effective set from its new master and the noise it holds
+            self.refresh_effective()
 
     def copy_params_to(self, dst_flat: torch.Tensor) -> None:
+        """The online parameters into a plain flat set (``P`` floats): under ``noisy_heads`` their ``mu``, through
+        the ``noise = 0`` compose (the evaluators' snapshots)."""
+        if self.noisy:
+            if dst_flat.numel() != self.P:
+                raise ValueError("copy_params_to fills a plain parameter set")
+            c = self._compose([dict(master=self.flat.data_ptr(), eff=dst_flat.data_ptr(), net=0)], 0)
+            return self.hip.vecn_compose(c, self._stream())
         self.hip.copy_f32(dst_flat.data_ptr(), self.flat.data_ptr(), self.P, self._stream())
 
     def state_dict(self):
@@ -436,7 +554,7 @@ class VectorApexEngine(GreedyRollouts):
         self.hip = ops.hip()
         self.kind, self.obs_dim, self.A, self.limit = env_spec(cfg.env_id)
         torch.manual_seed(cfg.seed)
-        model = make_model(cfg.env_id)
+        model = make_model(cfg.env_id, cfg.noisy_heads)
         self.replay = HBMReplay(cfg.replay_capacity, cfg.n_envs, cfg.n_step, cfg.alpha, dev,
                                 frame_bytes=4 * self.obs_dim, seed=cfg.seed + 17)
         self.learner = MLPDQNLearner(model, self.replay, cfg)
@@ -455,7 +573,7 @@ class VectorApexEngine(GreedyRollouts):
 
     # ------------------------------------------------------------------ phases
     def publish_params(self) -> None:
-        self.learner.copy_params_to(self.actor_flat)
+        self.learner.publish_to(self.actor_flat)
 
     def _actor_body(self) -> None:
         self.shard.act_and_step()
@@ -525,6 +643,7 @@ class VectorApexEngine(GreedyRollouts):
         to the replay."""
         h, dev = self.hip, self.device
         n = int(episodes)
+        net = self.learner.greedy_net()
         if self._eval is None or self._eval["n"] != n:
             ring = torch.zeros(4 * n, self.obs_dim, dtype=torch.float32, device=dev)
             lay = h.vec_env_state_layout()
@@ -538,7 +657,7 @@ class VectorApexEngine(GreedyRollouts):
                   "done": torch.zeros(n, dtype=torch.float32, device=dev),
                   "eps": torch.zeros(n, dtype=torch.float32, device=dev),
                   "counter": torch.zeros(1, dtype=torch.int64, device=dev)}
-            ev["act"] = h.make_vec_act(self.learner.net, ring.data_ptr(), ev["hist"].data_ptr(), n,
+            ev["act"] = h.make_vec_act(net, ring.data_ptr(), ev["hist"].data_ptr(), n,
                                        ev["eps"].data_ptr(), 0, ev["counter"].data_ptr(), ev["q"].data_ptr(),
                                        ev["actions"].data_ptr())
             self._eval = ev
@@ -569,19 +688,25 @@ class VectorApexEngine(GreedyRollouts):
     _eval_limit = property(lambda self: self.limit)
 
     def _make_rollout(self, n: int) -> VecRolloutBuffers:
-        return VecRolloutBuffers(self.hip, self.learner.net, self.kind, self.obs_dim, n, self.device)
+        # (noisy_heads: the rollout reads the evaluation set; every launch first composes mu as it is now into it)
+        return VecRolloutBuffers(self.hip, self.learner.greedy_net(), self.kind, self.obs_dim, n, self.device,
+                                 prepare=self.learner.greedy_net if self.learner.noisy else None)
 
 
 class VecRolloutBuffers(RolloutBuffers):
-    """Device outputs of ``vec_rollout`` for ``n`` episodes of one net + the launch."""
+    """Device outputs of ``vec_rollout`` for ``n`` episodes of one net + the launch.  ``prepare``: called on the
+    current stream before every launch, where ``net`` is a set that has to be brought up to date first."""
 
-    def __init__(self, hip, net, kind: int, obs_dim: int, n: int, device):
+    def __init__(self, hip, net, kind: int, obs_dim: int, n: int, device, prepare=None):
         super().__init__(n, device)
         self.hip, self.net, self.kind, self.obs_dim = hip, net, int(kind), int(obs_dim)
+        self.prepare = prepare
 
     def launch(self, seed: int, max_steps: int, trace: dict | None = None) -> None:
         """One ``vec_rollout`` launch on the current stream.  ``trace``: the tensors
         ``obs`` f32 [n, T, obs_dim], ``q`` f32 [n, T, A] and ``act`` i32 [n, T]."""
+        if self.prepare is not None:
+            self.prepare()
         d = dict(kind=self.kind, N=self.n, obs=self.obs_dim, max_steps=int(max_steps), seed=int(seed),
                  returns=self.returns.data_ptr(), lengths=self.lengths.data_ptr(), ended=self.ended.data_ptr())
         if trace is not None:
@@ -602,7 +727,7 @@ class VectorEvaluator(RolloutEvaluation):
             raise TypeError("VectorEvaluator plays vec_rollout's device envs: it needs a VectorApexEngine; a "
                             "host-env engine evaluates on the host (VectorHostEngine.evaluate)")
         self.hip, self.n = engine.hip, int(episodes)
-        self.model = copy.deepcopy(engine.learner.model)   # the snapshot
+        self.model = copy.deepcopy(engine.learner.net_model)   # the snapshot (a plain set; noisy_heads: of mu)
         self.model._flat = None
         self.flat = self.model.flatten_parameters()
         for p in self.model.parameters():

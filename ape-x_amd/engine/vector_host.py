@@ -262,7 +262,7 @@ class VectorHostEngine:
         self.device = dev = torch.device(device)
         self.hip = ops.hip()
         torch.manual_seed(cfg.seed)
-        model = DuelingDQN.from_shapes((self.obs_dim,), self.A)
+        model = DuelingDQN.from_shapes((self.obs_dim,), self.A, noisy=cfg.noisy_heads)
         self.replay = HBMReplay(cfg.replay_capacity, cfg.n_envs, cfg.n_step, cfg.alpha, dev,
                                 frame_bytes=ring_bytes(cfg.ring_dtype) * self.obs_dim, seed=cfg.seed + 17)
         self.learner = MLPDQNLearner(model, self.replay, cfg)
@@ -286,7 +286,7 @@ class VectorHostEngine:
         """Called after every enqueue of an iteration (a test synchronizes here)."""
 
     def publish_params(self) -> None:
-        self.learner.copy_params_to(self.actor_flat)
+        self.learner.publish_to(self.actor_flat)   # (noisy_heads: composed with the acting copy's own noise)
         self._enqueued()
 
     def actor_step(self) -> None:
@@ -355,7 +355,7 @@ class VectorHostEngine:
         env = self.eval_env() if self.eval_env is not None else envs.make(self.cfg.env_id)
         env.seed(int(seed))
         torch.cuda.synchronize(self.device)
-        m = DuelingDQN.from_shapes((self.obs_dim,), self.A)
+        m = DuelingDQN.from_shapes((self.obs_dim,), self.A, noisy=self.cfg.noisy_heads)   # (eval mode: mu)
         m.load_state_dict({k: v.detach().cpu() for k, v in self.learner.model.state_dict().items()})
         m.eval()
         limit = int(getattr(env, "_max_episode_steps", None) or self.limit

@@ -26,6 +26,7 @@ import torch
 import torch.nn as nn
 
 from ..envs.spaces import Box, Discrete
+from .noisy import NoisyLinear
 
 
 class Flatten(nn.Module):
@@ -53,10 +54,15 @@ def env_spec(obs_shape, n_actions: int):
 class DuelingDQN(nn.Module):
     HIDDEN = 128
 
-    def __init__(self, env):
+    NOISY_LAYERS = ("advantage.0", "advantage.2", "value.0", "value.2")
+
+    def __init__(self, env, noisy: bool = False):
         super().__init__()
         self.input_shape = tuple(env.observation_space.shape)
         self.cnn = len(self.input_shape) == 3
+        self.noisy = bool(noisy)
+        if self.noisy and self.cnn:
+            raise ValueError("noisy heads are offered for the MLP form of DuelingDQN")
         self.num_actions = int(env.action_space.n)
         self.flatten = Flatten()
         if self.cnn:
@@ -69,14 +75,34 @@ class DuelingDQN(nn.Module):
         else:
             self.features = nn.Sequential(init(nn.Linear(self.input_shape[0], self.HIDDEN)), nn.ReLU())
         f = self._feature_size()
-        self.advantage = nn.Sequential(init(nn.Linear(f, self.HIDDEN)), nn.ReLU(),
-                                       init(nn.Linear(self.HIDDEN, self.num_actions)))
-        self.value = nn.Sequential(init(nn.Linear(f, self.HIDDEN)), nn.ReLU(), init(nn.Linear(self.HIDDEN, 1)))
+        if self.noisy:
+            # the reference's commented-out NoisyLinear heads (model.py): factorised noise, std_init 0.4,
+            # NoisyLinear's own init; train mode uses mu + sigma * eps, eval mode mu
+            def head(i, o):
+                return NoisyLinear(i, o, std_init=0.4)
+        else:
+            def head(i, o):
+                return init(nn.Linear(i, o))
+        self.advantage = nn.Sequential(head(f, self.HIDDEN), nn.ReLU(), head(self.HIDDEN, self.num_actions))
+        self.value = nn.Sequential(head(f, self.HIDDEN), nn.ReLU(), head(self.HIDDEN, 1))
         self._flat = None
 
     @classmethod
-    def from_shapes(cls, obs_shape, n_actions: int) -> "DuelingDQN":
-        return cls(env_spec(obs_shape, n_actions))
+    def from_shapes(cls, obs_shape, n_actions: int, noisy: bool = False) -> "DuelingDQN":
+        """``noisy``: advantage.{0,2} and value.{0,2} are :class:`~apex_amd.models.noisy.NoisyLinear`
+        (state_dict keys ``weight_mu``, ``weight_sigma``, ``bias_mu``, ``bias_sigma`` + the buffers
+        ``weight_epsilon``, ``bias_epsilon`` under those names); ``features.0`` stays ``nn.Linear``."""
+        return cls(env_spec(obs_shape, n_actions), noisy=noisy)
+
+    def noisy_layers(self) -> list:
+        """The four NoisyLinear modules in ``NOISY_LAYERS`` order."""
+        if not self.noisy:
+            raise ValueError("not a noisy model")
+        return [self.advantage[0], self.advantage[2], self.value[0], self.value[2]]
+
+    def reset_noise(self) -> None:
+        for m in self.noisy_layers():
+            m.reset_noise()
 
     def forward(self, x):
         h = self.flatten(self.features(x))

@@ -59,6 +59,7 @@ HIP_SOURCES = [
     "vector_wide_bf16_kernels.hip",
     "vector_tall_kernels.hip",
     "vector_tall_bf16_kernels.hip",
+    "vector_noisy_kernels.hip",
     "vector_host_kernels.hip",
     "host_env_kernels.hip",
     "host_eval_kernels.hip",

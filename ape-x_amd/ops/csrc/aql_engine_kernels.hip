@@ -849,13 +849,7 @@ __device__ __forceinline__ float aql_grad_block(const AqlGrad& G, int bid, int n
 }
 
 // ------------------------------------------------------------------ noise reset + proposal copy
-__device__ __forceinline__ float scaled_noise(uint64_t seed, int layer, int kind, int i, uint64_t ctr) {
-  float u[4];
-  uniform4(seed, ((uint64_t)layer << 40) | ((uint64_t)kind << 32) | (uint32_t)i, ctr, u);
-  const float x = std_normal(u[0], u[1]);
-  return copysignf(sqrtf(fabsf(x)), x);  // f(x) = sign(x) sqrt(|x|) (model.py:160-163)
-}
-
+// (scaled_noise: common.h, shared with vector_noisy_kernels.hip)
 // noise reset / effective weights / proposal copy for the elements of this block
 __device__ __forceinline__ void aql_post_block(const AqlPost& P, int regen, uint64_t st) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -220,6 +220,17 @@ __device__ __forceinline__ float std_normal(float u1, float u2) {
   return r * cospif(2.f * u2);
 }
 
+// One factorised-Gaussian NoisyNet draw f(x) = sign(x) sqrt(|x|), x ~ N(0, 1) (model.py:160-163), at the
+// Philox key (seed, stream (layer, kind, i), counter).  kind: 0 eps_out, 1 eps_in, 2 the bias draw.  Shared by
+// the AQL critic's noise reset (aql_engine_kernels.hip) and vecn_compose (vector_noisy_kernels.hip), which
+// puts its net into bits 8.. of ``layer``.
+__device__ __forceinline__ float scaled_noise(uint64_t seed, int layer, int kind, int i, uint64_t ctr) {
+  float u[4];
+  uniform4(seed, ((uint64_t)layer << 40) | ((uint64_t)kind << 32) | (uint32_t)i, ctr, u);
+  const float x = std_normal(u[0], u[1]);
+  return copysignf(sqrtf(fabsf(x)), x);
+}
+
 __device__ __forceinline__ double uniform_double(uint64_t seed, uint64_t stream, uint64_t counter) {
   u32x4 c{(uint32_t)counter, (uint32_t)(counter >> 32), (uint32_t)stream, (uint32_t)(stream >> 32)};
   u32x4 r = philox4x32(c, (uint32_t)seed, (uint32_t)(seed >> 32));

@@ -1308,6 +1308,47 @@ PYBIND11_MODULE(_apex_hip, m) {
   }, py::arg("a"), py::arg("k"), py::arg("s"));
   m.def("vectb_learn", [](const VecLearn& p, uint64_t s) { vectb_learn(p, S(s)); });
   m.def("vectb_grad", [](const VecTallGrad& g, uint64_t s) { vectb_grad(g, S(s)); });
+  // NoisyNet heads (vector_noisy_kernels.hip).  A set: dict(master, eff, net, weps=[4 pointers], beps=[4 pointers])
+  // in the order advantage.0, advantage.2, value.0, value.2 (weps / beps may be left out for mode 0)
+  py::class_<VecnCompose>(m, "VecnCompose");
+  m.def("make_vecn_compose", [](py::list sets, int obs, int A, int mode, uint64_t seed, uint64_t step, int ahead) {
+    if (sets.size() < 1 || sets.size() > (size_t)kVecnMaxNets)
+      throw std::invalid_argument("make_vecn_compose: one to three nets");
+    VecnCompose c{};
+    c.n_nets = (int)sets.size();
+    for (int i = 0; i < c.n_nets; ++i) {
+      py::dict d = sets[i].cast<py::dict>();
+      VecnSet& S = c.set[i];
+      S.master = P<const float>(d["master"].cast<uint64_t>());
+      S.eff = P<float>(d["eff"].cast<uint64_t>());
+      S.net = d["net"].cast<int>();
+      if (d.contains("weps")) {
+        auto w = d["weps"].cast<std::vector<uint64_t>>(), b = d["beps"].cast<std::vector<uint64_t>>();
+        if (w.size() != (size_t)kVecnLayers || b.size() != (size_t)kVecnLayers)
+          throw std::invalid_argument("make_vecn_compose: four weight_epsilon and four bias_epsilon buffers");
+        for (int l = 0; l < kVecnLayers; ++l) { S.weps[l] = P<float>(w[l]); S.beps[l] = P<float>(b[l]); }
+      }
+    }
+    c.obs = obs; c.A = A; c.mode = mode; c.seed = seed; c.step = P<const int64_t>(step); c.ahead = ahead;
+    return c;
+  }, py::arg("sets"), py::arg("obs"), py::arg("A"), py::arg("mode"), py::arg("seed") = 0, py::arg("step") = 0,
+     py::arg("ahead") = 0);
+  m.def("vecn_compose", [](const VecnCompose& c, uint64_t s) { vecn_compose(c, S(s)); });
+  py::class_<VecnGrad>(m, "VecnGrad");
+  m.def("make_vecn_grad", [](uint64_t g_eff, uint64_t g_master, std::vector<uint64_t> weps, std::vector<uint64_t> beps,
+                             int obs, int A, uint64_t part) {
+    if (weps.size() != (size_t)kVecnLayers || beps.size() != (size_t)kVecnLayers)
+      throw std::invalid_argument("make_vecn_grad: four weight_epsilon and four bias_epsilon buffers");
+    VecnGrad g{};
+    g.g_eff = P<const float>(g_eff); g.g_master = P<float>(g_master);
+    for (int l = 0; l < kVecnLayers; ++l) { g.weps[l] = P<const float>(weps[l]); g.beps[l] = P<const float>(beps[l]); }
+    g.obs = obs; g.A = A; g.part = P<double>(part);
+    return g;
+  }, py::arg("g_eff"), py::arg("g_master"), py::arg("weps"), py::arg("beps"), py::arg("obs"), py::arg("A"),
+     py::arg("part"));
+  m.def("vecn_grad", [](const VecnGrad& g, uint64_t s) { vecn_grad(g, S(s)); });
+  m.def("vecn_param_count", &vecn_param_count);
+  m.def("vecn_blocks", &vecn_blocks);
 
   // ---- host gym-API envs (engine/host_env.py)
   py::class_<HostEnvTaps>(m, "HostEnvTaps").def_readonly("max_count", &HostEnvTaps::max_count);

@@ -1076,6 +1076,51 @@ void vectb_act(const VecAct& a, hipStream_t s);
 void vectb_host_eval_act(const VecHostEvalAct& a, hipStream_t s);
 void vectb_learn(const VecLearn& p, hipStream_t s);
 void vectb_grad(const VecTallGrad& g, hipStream_t s);
+// ---- vector_noisy_kernels.hip: NoisyNet heads for the MLP dueling DQN.  The four head layers (advantage.0,
+// advantage.2, value.0, value.2; 128 inputs each) are NoisyLinear: the MASTER buffer holds
+// DuelingDQN(noisy).parameters() -- features.0.weight, features.0.bias, then per noisy layer weight_mu,
+// weight_sigma, bias_mu, bias_sigma (vecn_param_count(obs, A) floats) -- and every vec_* / vecw_* / vecwb_* /
+// vect_* / vectb_* launch reads an EFFECTIVE set W = mu + sigma * eps in the plain VecNet layout
+// (vec_param_count(obs, A) floats, DuelingDQN.parameters() order).
+constexpr int kVecnLayers = 4, kVecnMaxNets = 3, kVecnBand = 8;
+struct VecnSet {
+  const float* master;        // [vecn_param_count]
+  float* eff;                 // [vec_param_count] the effective set
+  float* weps[kVecnLayers];   // the model's weight_epsilon buffers [out][128] (mode 0: unused)
+  float* beps[kVecnLayers];   // the model's bias_epsilon buffers [out]
+  int net;                    // the net's id in the Philox key (0 online, 1 target, 2 acting)
+};
+// mode 1: draw eps_in / eps_out / eps_b as scaled_noise at key (seed, net, layer, kind, index, step[0] + ahead),
+//         write weight_epsilon = outer(eps_out, eps_in), bias_epsilon and W_eff = fmaf(sigma, eps, mu);
+// mode 2: keep the noise in the epsilon buffers (read, not drawn) and write W_eff from it;
+// mode 0: W_eff = mu (the greedy evaluators' set; the epsilon buffers are not touched).
+// features.0 is copied in every mode.  One launch for n_nets sets; a workgroup owns kVecnBand output rows of
+// one layer of one net (or 4096 floats of features.0).
+struct VecnCompose {
+  VecnSet set[kVecnMaxNets];
+  int n_nets;
+  int obs, A;
+  int mode;
+  uint64_t seed;
+  const int64_t* step;   // the learner's step counter (read)
+  int ahead;             // added to step[0] in the key: 1 inside a learner step (the noise of the NEXT step)
+};
+int64_t vecn_param_count(int obs, int A);
+int vecn_blocks(int obs, int A);   // workgroups per net of vecn_compose; vecn_grad's grid and partial count
+void vecn_compose(const VecnCompose& c, hipStream_t s);
+// The gradient over the effective layout (``g_eff``, what any *_grad launch wrote) mapped onto the master
+// layout: d mu = g, d sigma = g * eps (weights and biases, eps from the epsilon buffers), features.0 passed
+// through; part[vecn_blocks] = the fp64 sum of squares of the MASTER gradient per workgroup, fixed order
+// (rmsprop_step's norm input).
+struct VecnGrad {
+  const float* g_eff;                 // [vec_param_count]
+  float* g_master;                    // [vecn_param_count]
+  const float* weps[kVecnLayers];
+  const float* beps[kVecnLayers];
+  int obs, A;
+  double* part;                       // [vecn_blocks(obs, A)]
+};
+void vecn_grad(const VecnGrad& g, hipStream_t s);
 // The actor side of one frame of the single-process prioritized DQN (reference DQN.py) in ONE
 // launch of one workgroup, E <= 8 envs: epsilon(t) / beta(t) in fp64, vec_act's forward and
 // draw on the online net, vec_classic_step's env step, frame_hist_step's FrameStack advance,

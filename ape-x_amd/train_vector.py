@@ -33,6 +33,10 @@ matrix-core operands, fp32 accumulation, fp32 master weights and checkpoints); `
 ``--host-envs --wide --tall --dtype bf16`` takes those with bf16 operands (``tall_dtype``, ``vectb_*``);
 ``--ring-dtype bf16`` (with exactly those flags) stores the observation ring as bf16 (``ring_dtype``: half the
 replay's observation bytes, the same numbers bit for bit).
+``--noisy`` (with any of the flags above, exactly as they combine without it) trains the NoisyNet variant
+(``VectorEngineConfig.noisy_heads``): NoisyLinear advantage and value heads, fresh factorised noise per SGD step
+and per publish (``vecn_compose`` / ``vecn_grad``), greedy evaluation on ``mu``; ``model{t}.pth`` then carries the
+reference's NoisyLinear keys.
 ``--wide`` is still refused with ``--eval-envs``: the evaluator itself takes a wide engine
 (``vecw_host_eval_act``, :mod:`apex_amd.engine.vector_host_eval`), this command line's switch-over is
 a follow-up; the blocking evaluator and the reference-format checkpoints work as they are.
@@ -120,6 +124,9 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--ring-dtype", default="fp32", choices=["fp32", "bf16"],
                    help="(--host-envs --wide --tall --dtype bf16) bf16: the observation ring stored as bf16, rounded "
                         "once at the write; results are bit-equal to the fp32 ring's")
+    p.add_argument("--noisy", action="store_true",
+                   help="NoisyLinear advantage / value heads (noisy_heads): noise redrawn on the device every SGD step "
+                        "and publish; evaluation is greedy on mu")
     p.add_argument("--learner-steps", type=int, default=1, help="(--host-envs) SGD steps per env step")
     p.add_argument("--host-serial", action="store_true",
                    help="(--host-envs) learner steps, then the acting step: no overlap with the host's env step")
@@ -171,7 +178,7 @@ def config_from_args(a) -> VectorEngineConfig:
                               publish_param_interval=a.publish_interval, seed=a.seed,
                               wide_net=a.wide, wide_dtype="fp32" if a.tall else a.dtype, tall_obs=a.tall,
                               tall_dtype=a.dtype if a.tall else "fp32",
-                              ring_dtype=a.ring_dtype).validate(not a.host_envs)
+                              ring_dtype=a.ring_dtype, noisy_heads=a.noisy).validate(not a.host_envs)
 
 
 def _crossed(t: int, prev: int, interval: int) -> bool:
