@@ -68,6 +68,7 @@ class DQNEngineConfig:
     exact_mass: bool = False         # False: the reference's exclusive-end mass
     max_episode_steps: int | None = None   # None: the env's registered TimeLimit
     noisy_heads: bool = False        # refused: see validate()
+    dist_atoms: int = 0              # refused: see validate()
     seed: int = 0
 
     def validate(self) -> "DQNEngineConfig":
@@ -76,6 +77,10 @@ class DQNEngineConfig:
             raise ValueError("noisy_heads is an option of the vector Ape-X engines (engine/vector.py, "
                              "engine/vector_host.py): dqn_frame acts on the online net in place, with no "
                              "effective weight set to compose")
+        if self.dist_atoms:
+            raise ValueError("dist_atoms is an option of the vector Ape-X engines (engine/vector.py, "
+                             "engine/vector_host.py) with wide_net: dqn_frame and vec_learn compute a scalar Q per "
+                             "action and the Huber loss")
         if not 1 <= self.n_envs <= MAX_ENVS:
             raise ValueError(f"n_envs must be in [1, {MAX_ENVS}] (one workgroup's forward pass)")
         if not 1 <= self.batch_size <= MAX_BATCH:

@@ -66,6 +66,16 @@ The epsilon ladder still applies on top: ``eps_base=0`` gives pure noisy explora
 (``evaluate``, ``rollout_evaluate``, :class:`VectorEvaluator`, the host evaluators' weight sets) reads ``mu`` through
 the ``noise = 0`` compose.
 
+``dist_atoms=N`` (with ``wide_net`` and ``wide_dtype="fp32"``; not with ``tall_obs`` or ``noisy_heads``, which are
+follow-ups) trains categorical (C51) heads: ``DuelingDQN.from_shapes(atoms=N, v_min=, v_max=)`` has ``advantage.2`` =
+``Linear(128, A * N)`` and ``value.2`` = ``Linear(128, N)`` under the same ten state_dict keys, and the launches come
+from ``ops/csrc/vector_dist_kernels.hip`` (``vecd_act`` / ``vecd_learn`` / ``vecd_grad``; observations to 128 floats,
+at most 8 actions and 64 atoms).  Same launch counts: 5 per SGD step, 4 per actor step.  ``q`` and ``q_s`` / ``q_s2`` /
+``qt_s2`` hold the expected Q; the loss is the cross-entropy against the projected double-DQN target distribution;
+the priority is the expected-value TD error, the scale ``nstep_emit`` writes the initial priorities on.
+``evaluate()`` acts through ``vecd_act`` at epsilon 0; ``rollout_evaluate`` and :class:`VectorEvaluator` play the
+narrow ``vec_rollout`` and raise a ``ValueError``.
+
 Serial actor-then-learner on one stream; overlap and multi-GPU topologies are the Atari
 engine's and are not offered here.  Envs other than ``VECTOR_ENVS`` -- any gym-API env with a
 flat observation and a discrete action space, stepped on the CPU -- train under the same
@@ -104,10 +114,12 @@ def env_spec(env_id: str) -> tuple[int, int, int, int]:
     return VECTOR_ENVS[env_id]
 
 
-def make_model(env_id: str, noisy: bool = False) -> DuelingDQN:
-    """The MLP ``DuelingDQN`` of ``env_id`` (reference state_dict keys); ``noisy``: NoisyLinear heads."""
+def make_model(env_id: str, noisy: bool = False, atoms: int = 0, v_min: float = -10.0,
+               v_max: float = 10.0) -> DuelingDQN:
+    """The MLP ``DuelingDQN`` of ``env_id`` (reference state_dict keys); ``noisy``: NoisyLinear heads;
+    ``atoms``: categorical heads over ``v_min .. v_max``."""
     _, obs, n_actions, _ = env_spec(env_id)
-    return DuelingDQN.from_shapes((obs,), n_actions, noisy=noisy)
+    return DuelingDQN.from_shapes((obs,), n_actions, noisy=noisy, atoms=atoms, v_min=v_min, v_max=v_max)
 
 
 def save_state_dict(model: DuelingDQN, path: str) -> str:
@@ -133,14 +145,26 @@ def ring_bytes(ring_dtype: str) -> int:
     return 2 if ring_dtype == "bf16" else 4
 
 
+DIST_MAX_ACTIONS = 8    # kVecDistMaxA: the categorical kernels' widest action set
+DIST_MAX_ATOMS = 64     # kVecDistMaxAtoms
+
+
 def wide_kernel(hip, name: str, dtype: str = "fp32", tall: bool = False, tall_dtype: str = "fp32",
-                ring_dtype: str = "fp32"):
+                ring_dtype: str = "fp32", dist: bool = False):
     """The wide launch ``name`` (``act``, ``learn``, ``grad``, ``host_eval_act``) of ``wide_dtype``
     ``dtype``: ``vecw_<name>`` (fp32 MFMA) or ``vecwb_<name>`` (bf16 operands); ``tall``:
     ``vect_<name>`` (fp32 MFMA, observations to 1024 floats) or, with ``tall_dtype="bf16"``,
     ``vectb_<name>`` (bf16 operands).  ``ring_dtype="bf16"`` is taken by the ``vectb_*`` launches alone
-    (the handle carries ``ring_bf16``; the launch is the same)."""
+    (the handle carries ``ring_bf16``; the launch is the same).  ``dist``: ``vecd_<name>``, the categorical
+    heads (fp32 MFMA, observations to 128 floats)."""
     ring_bytes(ring_dtype)
+    if dist:
+        if dtype != "fp32":
+            raise ValueError("the categorical kernels (vecd_*) are fp32: bf16 operands for them are a follow-up")
+        if tall:
+            raise ValueError("the categorical kernels (vecd_*) take observations to 128 floats: tall observations "
+                             "for them are a follow-up")
+        return getattr(hip, "vecd_" + name)
     if ring_dtype != "fp32" and not (tall and tall_dtype == "bf16"):
         raise ValueError("ring_dtype='bf16' is a layout of the tall bf16 kernels: pass tall=True and tall_dtype='bf16'")
     if dtype not in WIDE_DTYPES:
@@ -166,6 +190,10 @@ def vec_net(hip, model: DuelingDQN):
             raise ValueError(f"{k}: contiguous fp32 expected")
     d = {k: p.data_ptr() for k, p in sd.items()}
     d.update(obs=model.input_shape[0], A=model.num_actions)
+    if model.atoms:   # categorical heads: advantage.2 [A N, 128], value.2 [N, 128] (the vecd_* launches)
+        if model.atoms > DIST_MAX_ATOMS or model.num_actions > DIST_MAX_ACTIONS:
+            raise ValueError(f"the categorical kernels take up to {DIST_MAX_ATOMS} atoms and {DIST_MAX_ACTIONS} actions")
+        d.update(atoms=model.atoms, v_min=model.v_min, v_max=model.v_max)
     return hip.make_vec_net(d)
 
 
@@ -178,17 +206,19 @@ class VectorActorShard(NStepShard):
                  eps_base: float = 0.4, eps_alpha: float = 7.0, actor_offset: int = 0,
                  total_actors: int | None = None, seed: int = 0, mode: str = "reference",
                  max_episode_steps: int | None = None, wide: bool = False, wide_dtype: str = "fp32",
-                 tall: bool = False, tall_dtype: str = "fp32"):
+                 tall: bool = False, tall_dtype: str = "fp32", dist: bool = False):
         self.env_id = env_id
         self.wide = bool(wide)   # act with vecw_act (the MFMA forward) instead of vec_act
+        if dist and not wide:
+            raise ValueError("the categorical act (vecd_act) is a mode of the wide kernels: pass wide=True")
         self.kind, self.obs_dim, n_actions, limit = env_spec(env_id)
         self.max_episode_steps = int(limit if max_episode_steps is None else max_episode_steps)
         if replay.frame_bytes != 4 * self.obs_dim:
             raise ValueError(f"replay frame_bytes must be 4 * obs_dim = {4 * self.obs_dim}")
         super().__init__(replay, n_envs, n_actions, n_step, gamma, eps_base, eps_alpha, actor_offset, total_actors,
                          seed, mode)
-        # (vecwb_act for bf16, vect_act / vectb_act for tall)
-        self._wide_act = wide_kernel(self.hip, "act", wide_dtype, tall, tall_dtype) if self.wide else None
+        # (vecwb_act for bf16, vect_act / vectb_act for tall, vecd_act for categorical heads)
+        self._wide_act = wide_kernel(self.hip, "act", wide_dtype, tall, tall_dtype, dist=dist) if self.wide else None
         E = self.E
         self.layout = self.hip.vec_env_state_layout()
         self.env_state = torch.zeros(E, self.layout["STRIDE"], dtype=torch.float32, device=self.device)
@@ -272,6 +302,9 @@ class VectorEngineConfig:
     tall_dtype: str = "fp32"         # (tall_obs) "bf16": the streamed kernels with bf16 operands (vectb_*)
     ring_dtype: str = "fp32"         # (tall_dtype "bf16", host envs) "bf16": the observation ring stored as bf16
     noisy_heads: bool = False        # NoisyLinear advantage / value heads (vecn_*); eps_base=0: noise alone explores
+    dist_atoms: int = 0              # (wide_net, fp32) categorical (C51) heads of this many atoms (vecd_*); A <= 8
+    v_min: float = -10.0             # (dist_atoms) the support's ends
+    v_max: float = 10.0
     seed: int = 0
 
     def validate(self, device_env: bool = True) -> "VectorEngineConfig":
@@ -312,6 +345,22 @@ class VectorEngineConfig:
         if self.ring_dtype != "fp32" and device_env:
             raise ValueError("ring_dtype='bf16' is written by the host-env engine's vec_host_tail: the device envs "
                              "keep an fp32 ring")
+        if self.dist_atoms:
+            if not self.wide_net:
+                raise ValueError("dist_atoms is a mode of the wide kernels: set wide_net")
+            if self.wide_dtype != "fp32":
+                raise ValueError("dist_atoms takes wide_dtype='fp32': bf16 operands for the categorical heads are a "
+                                 "follow-up")
+            if self.tall_obs:
+                raise ValueError("dist_atoms with tall_obs is a follow-up: the categorical kernels take observations "
+                                 "to 128 floats")
+            if self.noisy_heads:
+                raise ValueError("dist_atoms with noisy_heads is a follow-up: NoisyNet on the categorical heads is "
+                                 "not built")
+            if not 2 <= self.dist_atoms <= DIST_MAX_ATOMS:
+                raise ValueError(f"dist_atoms must be in [2, {DIST_MAX_ATOMS}]")
+            if not self.v_min < self.v_max:
+                raise ValueError("dist_atoms needs v_min < v_max")
         return self
 
 
@@ -335,6 +384,13 @@ class MLPDQNLearner:
         for p in self.target.parameters():
             p.requires_grad_(False)
         self.obs_dim, self.A = self.model.input_shape[0], self.model.num_actions
+        self.atoms = int(cfg.dist_atoms)
+        support = (float(cfg.v_min), float(cfg.v_max)) == (self.model.v_min, self.model.v_max)
+        if self.atoms != self.model.atoms or (self.atoms and not support):
+            raise ValueError("dist_atoms / v_min / v_max and the model disagree: build it with "
+                             "DuelingDQN.from_shapes(atoms=..., v_min=..., v_max=...)")
+        if self.atoms and self.A > DIST_MAX_ACTIONS:
+            raise ValueError(f"dist_atoms takes up to {DIST_MAX_ACTIONS} actions, the env has {self.A}")
         self.P_opt = self.flat.numel()   # the optimizer's buffer (the master): P, or P_n under noisy_heads
         if self.noisy:
             # plain holders of the effective weights: what self.net / self.tnet (and every launch) read
@@ -349,7 +405,8 @@ class MLPDQNLearner:
         self.ring_bf16 = cfg.ring_dtype == "bf16"
         if replay.frame_bytes != ring_bytes(cfg.ring_dtype) * self.obs_dim:
             raise ValueError(f"replay frame_bytes must be {ring_bytes(cfg.ring_dtype)} * obs_dim")
-        if self.P != h.vec_param_count(self.obs_dim, self.A):
+        if self.P != (h.vecd_param_count(self.obs_dim, self.A, self.atoms) if self.atoms
+                      else h.vec_param_count(self.obs_dim, self.A)):
             raise ValueError("unexpected parameter count for the MLP dueling net")
         self.segments = self.model.param_segments()
         assert self.noisy or tuple(n for n, _, _ in self.segments) == PARAM_KEYS
@@ -374,7 +431,7 @@ class MLPDQNLearner:
         self.q_s2 = torch.zeros(B, A, **f32)
         self.qt_s2 = torch.zeros(B, A, **f32)
         wide, tall = bool(cfg.wide_net), bool(cfg.tall_obs)
-        self.lay = h.vecw_layout() if wide else h.vec_layout()
+        self.lay = h.vecd_layout() if self.atoms else h.vecw_layout() if wide else h.vec_layout()
         self.vec = torch.zeros(B, self.lay["STRIDE"], **f32)
         self.delta = torch.zeros(B, **f32)
         self.lw = torch.zeros(B, **f32)
@@ -384,15 +441,17 @@ class MLPDQNLearner:
         self.step_counter = torch.zeros(1, dtype=torch.int64, device=dev)
         # PER beta, annealed on the device: vec_learn writes beta_by_frame(step + 1) for the next draw
         self.beta = torch.full((1,), float(cfg.beta), **f32)
-        self.nblk = ((h.vect_grad_blocks if tall else h.vecw_grad_blocks)(self.obs_dim, A) if wide
+        self.nblk = (h.vecd_grad_blocks(self.obs_dim, A, self.atoms) if self.atoms
+                     else (h.vect_grad_blocks if tall else h.vecw_grad_blocks)(self.obs_dim, A) if wide
                      else h.vec_grad_blocks(self.P))
         self.part = torch.zeros(self.nblk, dtype=torch.float64, device=dev)
         self.partials = torch.zeros(h.grad_norm_partials(), dtype=torch.float64, device=dev)
         self.ring = replay.frames.view(torch.bfloat16 if self.ring_bf16 else torch.float32)
         self.net = vec_net(h, self.net_model)
         self.tnet = vec_net(h, self.tnet_model)
-        self._learn, self._grad = ((wide_kernel(h, "learn", cfg.wide_dtype, tall, cfg.tall_dtype, cfg.ring_dtype),
-                                    wide_kernel(h, "grad", cfg.wide_dtype, tall, cfg.tall_dtype, cfg.ring_dtype))
+        dist = bool(self.atoms)
+        self._learn, self._grad = ((wide_kernel(h, "learn", cfg.wide_dtype, tall, cfg.tall_dtype, cfg.ring_dtype, dist),
+                                    wide_kernel(h, "grad", cfg.wide_dtype, tall, cfg.tall_dtype, cfg.ring_dtype, dist))
                                    if wide else (h.vec_learn, h.vec_grad))
         self.L = (h.make_vecw_learn if wide else h.make_vec_learn)(self.net, self.tnet, dict(
             replay.trans_ptrs(), ring=self.ring.data_ptr(), idx=self.idx.data_ptr(), w=self.w.data_ptr(), B=B,
@@ -401,7 +460,10 @@ class MLPDQNLearner:
             lw=self.lw.data_ptr(), step=self.step_counter.data_ptr(), beta_out=self.beta.data_ptr(),
             beta0=float(cfg.beta), beta_horizon=float(cfg.beta_horizon), ring_bf16=self.ring_bf16))
         g = (self.vec.data_ptr(), B, self.obs_dim, A, self.P, self.eff_grad.data_ptr(), self.part.data_ptr())
-        if tall:   # dW0 reads the sampled observations where they lie: the ring, through the ids of s
+        if dist:
+            self.G = h.make_vecd_grad(self.vec.data_ptr(), B, self.obs_dim, A, self.atoms, self.P,
+                                      self.eff_grad.data_ptr(), self.part.data_ptr())
+        elif tall:   # dW0 reads the sampled observations where they lie: the ring, through the ids of s
             self.G = h.make_vect_grad(*g, self.ring.data_ptr(), replay.trans_ptrs()["s_ids"], self.idx.data_ptr(),
                                       ring_bf16=self.ring_bf16)
         else:
@@ -554,16 +616,19 @@ class VectorApexEngine(GreedyRollouts):
         self.hip = ops.hip()
         self.kind, self.obs_dim, self.A, self.limit = env_spec(cfg.env_id)
         torch.manual_seed(cfg.seed)
-        model = make_model(cfg.env_id, cfg.noisy_heads)
+        dist = dict(atoms=cfg.dist_atoms, v_min=cfg.v_min, v_max=cfg.v_max) if cfg.dist_atoms else {}
+        if dist and self.A > DIST_MAX_ACTIONS:
+            raise ValueError(f"dist_atoms takes up to {DIST_MAX_ACTIONS} actions, {cfg.env_id} has {self.A}")
+        model = make_model(cfg.env_id, cfg.noisy_heads, **dist)
         self.replay = HBMReplay(cfg.replay_capacity, cfg.n_envs, cfg.n_step, cfg.alpha, dev,
                                 frame_bytes=4 * self.obs_dim, seed=cfg.seed + 17)
         self.learner = MLPDQNLearner(model, self.replay, cfg)
-        self.actor_model = make_model(cfg.env_id).to(dev)
+        self.actor_model = make_model(cfg.env_id, **dist).to(dev)
         self.actor_flat = self.actor_model.flatten_parameters()
         self.shard = VectorActorShard(self.replay, cfg.n_envs, cfg.env_id, cfg.n_step, cfg.gamma, cfg.eps_base,
                                       cfg.eps_alpha, seed=cfg.seed * 0x2545F491 + 0xAC7, mode=cfg.nstep_mode,
                                       wide=cfg.wide_net, wide_dtype=cfg.wide_dtype, tall=cfg.tall_obs,
-                                      tall_dtype=cfg.tall_dtype)
+                                      tall_dtype=cfg.tall_dtype, dist=bool(cfg.dist_atoms))
         self.shard.set_policy(self.actor_model)
         self.publish_params()
         self.learn_steps = 0
@@ -657,9 +722,10 @@ class VectorApexEngine(GreedyRollouts):
                   "done": torch.zeros(n, dtype=torch.float32, device=dev),
                   "eps": torch.zeros(n, dtype=torch.float32, device=dev),
                   "counter": torch.zeros(1, dtype=torch.int64, device=dev)}
-            ev["act"] = h.make_vec_act(net, ring.data_ptr(), ev["hist"].data_ptr(), n,
-                                       ev["eps"].data_ptr(), 0, ev["counter"].data_ptr(), ev["q"].data_ptr(),
-                                       ev["actions"].data_ptr())
+            # (a categorical engine acts through vecd_act at epsilon 0: the expected Q)
+            ev["act"] = (h.make_vecw_act if self.cfg.dist_atoms else h.make_vec_act)(
+                net, ring.data_ptr(), ev["hist"].data_ptr(), n, ev["eps"].data_ptr(), 0, ev["counter"].data_ptr(),
+                ev["q"].data_ptr(), ev["actions"].data_ptr())
             self._eval = ev
         ev = self._eval
         env = h.make_vec_env(self.kind, n, self.obs_dim, ev["ring"].shape[0], self.limit, ev["state"].data_ptr(),
@@ -670,8 +736,9 @@ class VectorApexEngine(GreedyRollouts):
                             ev["ep_log"].data_ptr(), s)
         first = torch.zeros(n, dtype=torch.float32, device=dev)
         got = torch.zeros(n, dtype=torch.bool, device=dev)
+        act = h.vecd_act if self.cfg.dist_atoms else h.vec_act
         for t in range(self.limit):
-            h.vec_act(ev["act"], s)
+            act(ev["act"], s)
             h.vec_classic_step(env, ev["actions"].data_ptr(), ev["counter"].data_ptr(), ev["reward"].data_ptr(),
                                ev["done"].data_ptr(), ev["new_frame"].data_ptr(), ev["ep_log"].data_ptr(), s)
             h.frame_hist_step(ev["hist"].data_ptr(), ev["new_frame"].data_ptr(), ev["done"].data_ptr(), n,
@@ -688,6 +755,9 @@ class VectorApexEngine(GreedyRollouts):
     _eval_limit = property(lambda self: self.limit)
 
     def _make_rollout(self, n: int) -> VecRolloutBuffers:
+        if self.cfg.dist_atoms:
+            raise ValueError("rollout_evaluate plays the narrow vec_rollout: a one-launch categorical rollout is a "
+                             "follow-up; a dist_atoms engine evaluates with evaluate()")
         # (noisy_heads: the rollout reads the evaluation set; every launch first composes mu as it is now into it)
         return VecRolloutBuffers(self.hip, self.learner.greedy_net(), self.kind, self.obs_dim, n, self.device,
                                  prepare=self.learner.greedy_net if self.learner.noisy else None)
@@ -726,6 +796,9 @@ class VectorEvaluator(RolloutEvaluation):
         if not isinstance(engine, VectorApexEngine):
             raise TypeError("VectorEvaluator plays vec_rollout's device envs: it needs a VectorApexEngine; a "
                             "host-env engine evaluates on the host (VectorHostEngine.evaluate)")
+        if engine.cfg.dist_atoms:
+            raise ValueError("VectorEvaluator plays the narrow vec_rollout: a one-launch categorical rollout is a "
+                             "follow-up; a dist_atoms engine evaluates with evaluate()")
         self.hip, self.n = engine.hip, int(episodes)
         self.model = copy.deepcopy(engine.learner.net_model)   # the snapshot (a plain set; noisy_heads: of mu)
         self.model._flat = None

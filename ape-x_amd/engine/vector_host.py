@@ -79,7 +79,8 @@ from .graphs import capture_graph
 from .hbm_replay import HBMReplay
 from .host_env import PinnedMirror
 from .shard import NStepShard
-from .vector import MLPDQNLearner, VectorEngineConfig, ring_bytes, save_state_dict, vec_net, wide_kernel
+from .vector import (DIST_MAX_ACTIONS, MLPDQNLearner, VectorEngineConfig, ring_bytes, save_state_dict, vec_net,
+                     wide_kernel)
 
 MAX_OBS = 8       # kVecMaxObs: the MLP kernels' widest observation
 MAX_ACTIONS = 7   # kVecMaxA: their widest action set
@@ -120,8 +121,10 @@ class VectorHostShard(NStepShard):
     def __init__(self, replay: HBMReplay, vec, n_step: int = 3, gamma: float = 0.99, eps_base: float = 0.4,
                  eps_alpha: float = 7.0, actor_offset: int = 0, total_actors: int | None = None, seed: int = 0,
                  mode: str = "reference", wide: bool = False, wide_dtype: str = "fp32", tall: bool = False,
-                 tall_dtype: str = "fp32", ring_dtype: str = "fp32"):
+                 tall_dtype: str = "fp32", ring_dtype: str = "fp32", dist: bool = False):
         self.vec = vec
+        if dist and not wide:
+            raise ValueError("the categorical act (vecd_act) is a mode of the wide kernels: pass wide=True")
         self.wide = bool(wide)   # act with vecw_act; the tail takes the wide observation limit
         self.tall = bool(tall)   # (wide) act with vect_act; the tail takes the tall observation limit
         self.obs_dim, n_actions, self.max_episode_steps = host_env_spec(vec, self.wide, self.tall)
@@ -137,9 +140,9 @@ class VectorHostShard(NStepShard):
             raise ValueError(f"replay frame_bytes must be {width} * obs_dim = {width * self.obs_dim}")
         super().__init__(replay, E, n_actions, n_step, gamma, eps_base, eps_alpha, actor_offset, total_actors, seed,
                          mode)
-        # (vecwb_act for bf16, vect_act for tall)
-        self._wide_act = (wide_kernel(self.hip, "act", wide_dtype, self.tall, tall_dtype, ring_dtype) if self.wide
-                          else None)
+        # (vecwb_act for bf16, vect_act for tall, vecd_act for categorical heads)
+        self._wide_act = (wide_kernel(self.hip, "act", wide_dtype, self.tall, tall_dtype, ring_dtype, dist=dist)
+                          if self.wide else None)
         h, dev = self.hip, self.device
         self.ring = replay.frames.view(torch.bfloat16 if self.ring_bf16 else torch.float32)  # [F, obs_dim]
         self.ep_ret = torch.zeros(E, dtype=torch.float32, device=dev)
@@ -262,16 +265,20 @@ class VectorHostEngine:
         self.device = dev = torch.device(device)
         self.hip = ops.hip()
         torch.manual_seed(cfg.seed)
-        model = DuelingDQN.from_shapes((self.obs_dim,), self.A, noisy=cfg.noisy_heads)
+        # (dist_atoms: categorical heads on the learner's model, the acting copy and evaluate()'s CPU copy)
+        self._dist = dict(atoms=cfg.dist_atoms, v_min=cfg.v_min, v_max=cfg.v_max) if cfg.dist_atoms else {}
+        if self._dist and self.A > DIST_MAX_ACTIONS:
+            raise ValueError(f"dist_atoms takes up to {DIST_MAX_ACTIONS} actions, the env has {self.A}")
+        model = DuelingDQN.from_shapes((self.obs_dim,), self.A, noisy=cfg.noisy_heads, **self._dist)
         self.replay = HBMReplay(cfg.replay_capacity, cfg.n_envs, cfg.n_step, cfg.alpha, dev,
                                 frame_bytes=ring_bytes(cfg.ring_dtype) * self.obs_dim, seed=cfg.seed + 17)
         self.learner = MLPDQNLearner(model, self.replay, cfg)
-        self.actor_model = DuelingDQN.from_shapes((self.obs_dim,), self.A).to(dev)
+        self.actor_model = DuelingDQN.from_shapes((self.obs_dim,), self.A, **self._dist).to(dev)
         self.actor_flat = self.actor_model.flatten_parameters()
         self.shard = VectorHostShard(self.replay, vec, cfg.n_step, cfg.gamma, cfg.eps_base, cfg.eps_alpha,
                                      seed=cfg.seed * 0x2545F491 + 0xAC7, mode=cfg.nstep_mode, wide=cfg.wide_net,
                                      wide_dtype=cfg.wide_dtype, tall=cfg.tall_obs, tall_dtype=cfg.tall_dtype,
-                                     ring_dtype=cfg.ring_dtype)
+                                     ring_dtype=cfg.ring_dtype, dist=bool(cfg.dist_atoms))
         self.shard._enqueued = lambda: self._enqueued()
         self.shard.set_policy(self.actor_model)
         self.publish_params()
@@ -355,7 +362,7 @@ class VectorHostEngine:
         env = self.eval_env() if self.eval_env is not None else envs.make(self.cfg.env_id)
         env.seed(int(seed))
         torch.cuda.synchronize(self.device)
-        m = DuelingDQN.from_shapes((self.obs_dim,), self.A, noisy=self.cfg.noisy_heads)   # (eval mode: mu)
+        m = DuelingDQN.from_shapes((self.obs_dim,), self.A, noisy=self.cfg.noisy_heads, **self._dist)   # (eval: mu)
         m.load_state_dict({k: v.detach().cpu() for k, v in self.learner.model.state_dict().items()})
         m.eval()
         limit = int(getattr(env, "_max_episode_steps", None) or self.limit

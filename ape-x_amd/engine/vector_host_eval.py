@@ -113,6 +113,9 @@ class VectorHostEvaluator:
         self.wide_dtype = getattr(getattr(engine, "cfg", None), "wide_dtype", "fp32")     # "bf16": the vecwb_* ones
         self.tall = bool(getattr(getattr(engine, "cfg", None), "tall_obs", False))        # the vect_* ones
         self.tall_dtype = getattr(getattr(engine, "cfg", None), "tall_dtype", "fp32")     # "bf16": the vectb_* ones
+        cfg = getattr(engine, "cfg", None)   # categorical heads: the vecd_* ones
+        self.dist = (dict(atoms=cfg.dist_atoms, v_min=cfg.v_min, v_max=cfg.v_max)
+                     if getattr(cfg, "dist_atoms", 0) else {})
         self.seed = int(seed)
         self.sd = eval_seed(self.seed) & 0xFFFFFFFFFFFF
         self.act_seed = self.sd ^ ACT_XOR
@@ -136,7 +139,7 @@ class VectorHostEvaluator:
         L = engine.learner
         self.models, self.flats, self.nets = [], [], []
         for _ in range(2):
-            m = DuelingDQN.from_shapes((self.obs,), self.A).to(dev)
+            m = DuelingDQN.from_shapes((self.obs,), self.A, **self.dist).to(dev)
             for p in m.parameters():
                 p.requires_grad_(False)
             flat = m.flatten_parameters()
@@ -187,8 +190,8 @@ class VectorHostEvaluator:
                      actions=self.actions.data_ptr())
             make = h.make_vecw_host_eval_act if w else h.make_vec_host_eval_act
             self._acts = [make(net, d) for net in self.nets]
-            self._fused_act = (wide_kernel(h, "host_eval_act", self.wide_dtype, self.tall, self.tall_dtype) if w
-                               else h.vec_host_eval_act)
+            self._fused_act = (wide_kernel(h, "host_eval_act", self.wide_dtype, self.tall, self.tall_dtype,
+                                           dist=bool(self.dist)) if w else h.vec_host_eval_act)
             return
         self._tail = h.make_vec_host_tail(dict(
             E=N, obs=self.obs, F=self.F, stage=self.stage_dev.data_ptr(), ring=self.ring.data_ptr(),
@@ -199,7 +202,8 @@ class VectorHostEvaluator:
         self._step_acts = [make(net, self.ring.data_ptr(), self.hist.data_ptr(), N, self.eps.data_ptr(),
                                 self.act_seed, self.counter.data_ptr(), self.q.data_ptr(),
                                 self.actions.data_ptr()) for net in self.nets]
-        self._step_act = wide_kernel(h, "act", self.wide_dtype, self.tall, self.tall_dtype) if w else h.vec_act
+        self._step_act = (wide_kernel(h, "act", self.wide_dtype, self.tall, self.tall_dtype, dist=bool(self.dist))
+                          if w else h.vec_act)
 
     # ------------------------------------------------------------------ weights
     def refresh(self) -> bool:

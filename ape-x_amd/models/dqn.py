@@ -56,13 +56,22 @@ class DuelingDQN(nn.Module):
 
     NOISY_LAYERS = ("advantage.0", "advantage.2", "value.0", "value.2")
 
-    def __init__(self, env, noisy: bool = False):
+    def __init__(self, env, noisy: bool = False, atoms: int = 0, v_min: float = -10.0, v_max: float = 10.0):
         super().__init__()
         self.input_shape = tuple(env.observation_space.shape)
         self.cnn = len(self.input_shape) == 3
         self.noisy = bool(noisy)
         if self.noisy and self.cnn:
             raise ValueError("noisy heads are offered for the MLP form of DuelingDQN")
+        # categorical (C51) heads: atoms = N > 0 atoms on the support v_min .. v_max; 0: the scalar heads
+        self.atoms, self.v_min, self.v_max = int(atoms), float(v_min), float(v_max)
+        if self.atoms:
+            if self.cnn:
+                raise ValueError("categorical heads (atoms) are offered for the MLP form of DuelingDQN")
+            if self.noisy:
+                raise ValueError("categorical heads with noisy heads on top are a follow-up: pass one of them")
+            if self.atoms < 2 or not self.v_min < self.v_max:
+                raise ValueError("categorical heads need atoms >= 2 and v_min < v_max")
         self.num_actions = int(env.action_space.n)
         self.flatten = Flatten()
         if self.cnn:
@@ -83,16 +92,42 @@ class DuelingDQN(nn.Module):
         else:
             def head(i, o):
                 return init(nn.Linear(i, o))
-        self.advantage = nn.Sequential(head(f, self.HIDDEN), nn.ReLU(), head(self.HIDDEN, self.num_actions))
-        self.value = nn.Sequential(head(f, self.HIDDEN), nn.ReLU(), head(self.HIDDEN, 1))
+        n_out = max(self.atoms, 1)   # outputs per action: advantage.2 unit a * N + z, value.2 unit z
+        self.advantage = nn.Sequential(head(f, self.HIDDEN), nn.ReLU(), head(self.HIDDEN, self.num_actions * n_out))
+        self.value = nn.Sequential(head(f, self.HIDDEN), nn.ReLU(), head(self.HIDDEN, n_out))
         self._flat = None
 
     @classmethod
-    def from_shapes(cls, obs_shape, n_actions: int, noisy: bool = False) -> "DuelingDQN":
+    def from_shapes(cls, obs_shape, n_actions: int, noisy: bool = False, atoms: int = 0, v_min: float = -10.0,
+                    v_max: float = 10.0) -> "DuelingDQN":
         """``noisy``: advantage.{0,2} and value.{0,2} are :class:`~apex_amd.models.noisy.NoisyLinear`
         (state_dict keys ``weight_mu``, ``weight_sigma``, ``bias_mu``, ``bias_sigma`` + the buffers
-        ``weight_epsilon``, ``bias_epsilon`` under those names); ``features.0`` stays ``nn.Linear``."""
-        return cls(env_spec(obs_shape, n_actions), noisy=noisy)
+        ``weight_epsilon``, ``bias_epsilon`` under those names); ``features.0`` stays ``nn.Linear``.
+        ``atoms=N`` (MLP form, not with ``noisy``): categorical (C51) heads -- ``advantage.2`` is
+        ``Linear(128, A * N)`` (unit ``a * N + z``), ``value.2`` ``Linear(128, N)``, the same ten state_dict
+        keys; :meth:`dist` is the return distribution over :meth:`support` and ``forward`` its mean."""
+        return cls(env_spec(obs_shape, n_actions), noisy=noisy, atoms=atoms, v_min=v_min, v_max=v_max)
+
+    def support(self, like: torch.Tensor) -> torch.Tensor:
+        """``z_i = v_min + i * (v_max - v_min) / (N - 1)`` in the dtype and on the device of ``like`` (built on
+        demand: not a buffer, so the state_dict keeps its ten keys)."""
+        if not self.atoms:
+            raise ValueError("not a categorical model")
+        dz = (self.v_max - self.v_min) / (self.atoms - 1)
+        return self.v_min + dz * torch.arange(self.atoms, dtype=like.dtype, device=like.device)
+
+    def dist_logits(self, x):
+        """Logits ``[B, A, N]``: ``l[a][z] = V[z] + Adv[a][z] - mean_a' Adv[a'][z]``."""
+        if not self.atoms:
+            raise ValueError("not a categorical model")
+        h = self.flatten(self.features(x))
+        adv = self.advantage(h).view(-1, self.num_actions, self.atoms)
+        val = self.value(h).view(-1, 1, self.atoms)
+        return val + adv - adv.mean(1, keepdim=True)
+
+    def dist(self, x):
+        """Return distribution ``[B, A, N]``: the softmax of :meth:`dist_logits` over the atoms."""
+        return torch.softmax(self.dist_logits(x), dim=-1)
 
     def noisy_layers(self) -> list:
         """The four NoisyLinear modules in ``NOISY_LAYERS`` order."""
@@ -105,6 +140,9 @@ class DuelingDQN(nn.Module):
             m.reset_noise()
 
     def forward(self, x):
+        if self.atoms:   # the expected Q [B, A]
+            p = self.dist(x)
+            return (p * self.support(p)).sum(-1)
         h = self.flatten(self.features(x))
         adv = self.advantage(h)
         val = self.value(h)

@@ -57,6 +57,7 @@ HIP_SOURCES = [
     "vector_kernels.hip",
     "vector_wide_kernels.hip",
     "vector_wide_bf16_kernels.hip",
+    "vector_dist_kernels.hip",
     "vector_tall_kernels.hip",
     "vector_tall_bf16_kernels.hip",
     "vector_noisy_kernels.hip",
@@ -188,6 +189,7 @@ HIP_FLAGS = [
 EXTRA_HIP_FLAGS = {
     "vector_wide_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "vector_wide_bf16_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "vector_dist_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "vector_tall_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "vector_tall_bf16_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }

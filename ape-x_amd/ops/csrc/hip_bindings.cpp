@@ -1106,6 +1106,10 @@ PYBIND11_MODULE(_apex_hip, m) {
     n.wv1 = g("value.0.weight"); n.bv1 = g("value.0.bias");
     n.wv2 = g("value.2.weight"); n.bv2 = g("value.2.bias");
     n.obs = d["obs"].cast<int>(); n.A = d["A"].cast<int>();
+    // categorical heads (vecd_* alone): atoms + the support's ends; absent: the scalar heads (atoms = 0)
+    n.atoms = d.contains("atoms") ? d["atoms"].cast<int>() : 0;
+    n.v_min = d.contains("v_min") ? d["v_min"].cast<float>() : 0.f;
+    n.v_max = d.contains("v_max") ? d["v_max"].cast<float>() : 0.f;
     return n;
   });
   py::class_<VecEnv>(m, "VecEnv");
@@ -1274,6 +1278,28 @@ PYBIND11_MODULE(_apex_hip, m) {
   });
   m.def("vecw_grad_blocks", &vecw_grad_blocks);
   m.def("vecw_grad", [](const VecGrad& g, uint64_t s) { vecw_grad(g, S(s)); });
+  // categorical (C51) heads on the wide path (vector_dist_kernels.hip): the make_vecw_act / make_vecw_learn /
+  // make_vecw_host_eval_act handles over a VecNet with atoms; the gradient handle adds the atom count
+  m.def("vecd_act", [](const VecAct& a, uint64_t s) { vecd_act(a, S(s)); });
+  m.def("vecd_host_eval_act", [](VecHostEvalAct a, int64_t k, uint64_t s) {
+    a.k = k;
+    vecd_host_eval_act(a, S(s));
+  }, py::arg("a"), py::arg("k"), py::arg("s"));
+  m.def("vecd_learn", [](const VecLearn& p, uint64_t s) { vecd_learn(p, S(s)); });
+  m.def("vecd_layout", []() {
+    py::dict d;
+    d["X"] = vecd::X; d["F"] = vecd::F; d["DF"] = vecd::DF; d["H"] = vecd::H; d["DH"] = vecd::DH;
+    d["G"] = vecd::G; d["ACT"] = vecd::ACT; d["STRIDE"] = vecd::STRIDE;
+    return d;
+  });
+  py::class_<VecDistGrad>(m, "VecDistGrad");
+  m.def("make_vecd_grad", [](uint64_t vec, int B, int obs, int A, int atoms, int64_t n, uint64_t grad, uint64_t part) {
+    return VecDistGrad{VecGrad{P<const float>(vec), B, obs, A, n, P<float>(grad), P<double>(part)}, atoms};
+  }, py::arg("vec"), py::arg("B"), py::arg("obs"), py::arg("A"), py::arg("atoms"), py::arg("n"), py::arg("grad"),
+     py::arg("part"));
+  m.def("vecd_param_count", &vecd_param_count);
+  m.def("vecd_grad_blocks", &vecd_grad_blocks);
+  m.def("vecd_grad", [](const VecDistGrad& g, uint64_t s) { vecd_grad(g, S(s)); });
   // the same four launches with bf16 matrix-core operands (vector_wide_bf16_kernels.hip) over the make_vecw_*
   // handles
   m.def("vecwb_act", [](const VecAct& a, uint64_t s) { vecwb_act(a, S(s)); });

@@ -893,6 +893,11 @@ struct VecNet {
   const float *wv1, *bv1;    // value.0      [128][128], [128]
   const float *wv2, *bv2;    // value.2      [1][128], [1]
   int obs, A;
+  // categorical (C51) heads, vector_dist_kernels.hip alone: atoms = N > 0 makes advantage.2 [A N][128]
+  // (unit a N + z) and value.2 [N][128] over the support z_i = v_min + i (v_max - v_min) / (N - 1).
+  // atoms = 0: the scalar heads above; every launcher but vecd_* refuses atoms != 0.
+  int atoms;
+  float v_min, v_max;
 };
 // per-env state row (floats): the physical state, the episode's running return / length and
 // the last step's own next observation (what the ring row holds unless the episode ended)
@@ -1039,6 +1044,27 @@ void vecw_host_eval_act(const VecHostEvalAct& a, hipStream_t s);
 void vecw_learn(const VecLearn& p, hipStream_t s);
 int vecw_grad_blocks(int obs, int A);
 void vecw_grad(const VecGrad& g, hipStream_t s);
+// ---- vector_dist_kernels.hip: the wide fp32-MFMA path with categorical (C51) heads (VecNet::atoms in
+// [2, kVecDistMaxAtoms], obs <= kVecWideMaxObs, A <= kVecDistMaxA).  vecd_act / vecd_host_eval_act /
+// vecd_learn take vecw_*'s descriptors; q, q_s, q_s2 and qt_s2 hold the EXPECTED Q, lw = w * cross-entropy
+// against the projected target distribution, delta = |E[projected target] - Q(s, a)|.  vecd_learn writes
+// its per-sample rows in the vecd layout: vecw's X / F / DF / H / DH, then G = dL/d logits of the taken
+// action at 64 slots (zero past atoms), then the action index (as a float).  vecd_grad contracts them, one
+// workgroup per 32x32 output tile (VecGrad::part holds vecd_grad_blocks(obs, A, atoms) partials).
+constexpr int kVecDistMaxA = 8, kVecDistMaxAtoms = 64;
+namespace vecd {
+constexpr int X = 0, F = 128, DF = 256, H = 384, DH = 640, G = 896, ACT = 960, STRIDE = 964;
+}
+struct VecDistGrad {
+  VecGrad g;     // n = vecd_param_count(obs, A, atoms)
+  int atoms;
+};
+void vecd_act(const VecAct& a, hipStream_t s);
+void vecd_host_eval_act(const VecHostEvalAct& a, hipStream_t s);
+void vecd_learn(const VecLearn& p, hipStream_t s);
+int64_t vecd_param_count(int obs, int A, int atoms);
+int vecd_grad_blocks(int obs, int A, int atoms);
+void vecd_grad(const VecDistGrad& g, hipStream_t s);
 // ---- vector_wide_bf16_kernels.hip: the four wide kernels with bf16 matrix-core operands
 // (v_mfma_f32_32x32x16_bf16, fp32 accumulation; every operand rounded to nearest even where it becomes
 // one, everything else fp32).  Same descriptors, limits, vecw row layout and vecw_grad_blocks tiles.

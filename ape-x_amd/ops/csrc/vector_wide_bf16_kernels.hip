@@ -192,6 +192,7 @@ __global__ __launch_bounds__(kT) void vecwb_grad_k(VecGrad g) {
 void check_wide_net(const VecNet& n, const char* who) {
   if (n.obs < 1 || n.obs > kVecWideMaxObs || n.A < 1 || n.A > kVecWideMaxA)
     throw std::invalid_argument(std::string(who) + ": obs in [1, 128] and actions in [1, 32]");
+  if (n.atoms != 0) throw std::invalid_argument(std::string(who) + ": categorical heads (atoms != 0) are vecd_*'s");
   if (!n.w0 || !n.b0 || !n.wa1 || !n.ba1 || !n.wa2 || !n.ba2 || !n.wv1 || !n.bv1 || !n.wv2 || !n.bv2)
     throw std::invalid_argument(std::string(who) + ": missing parameter tensor");
 }

@@ -37,6 +37,10 @@ replay's observation bytes, the same numbers bit for bit).
 (``VectorEngineConfig.noisy_heads``): NoisyLinear advantage and value heads, fresh factorised noise per SGD step
 and per publish (``vecn_compose`` / ``vecn_grad``), greedy evaluation on ``mu``; ``model{t}.pth`` then carries the
 reference's NoisyLinear keys.
+``--wide --atoms N --v-min X --v-max Y`` (either kind of env, fp32, not with ``--tall`` or ``--noisy``) trains
+categorical (C51) heads of N <= 64 atoms over the support X .. Y (``VectorEngineConfig.dist_atoms``, ``vecd_*``):
+cross-entropy against the projected target distribution, expected-value priorities, at most 8 actions; evaluation
+is ``--eval-mode step`` (greedy on the expected Q).
 ``--wide`` is still refused with ``--eval-envs``: the evaluator itself takes a wide engine
 (``vecw_host_eval_act``, :mod:`apex_amd.engine.vector_host_eval`), this command line's switch-over is
 a follow-up; the blocking evaluator and the reference-format checkpoints work as they are.
@@ -74,6 +78,12 @@ class _Parser(argparse.ArgumentParser):
         if a.ring_dtype != "fp32" and not (a.tall and a.dtype == "bf16"):
             self.error("--ring-dtype bf16 is a layout of the tall bf16 kernels: pass --host-envs --wide --tall "
                        "--dtype bf16")
+        if a.atoms:
+            if not a.wide or a.dtype != "fp32" or a.tall or a.noisy:
+                self.error("--atoms is a mode of the fp32 wide kernels: pass --wide; bf16 operands (--dtype bf16), "
+                           "--tall and --noisy with it are follow-ups")
+            if a.eval_mode != "step":
+                self.error("--atoms evaluates with --eval-mode step: a one-launch categorical rollout is a follow-up")
         if a.host_envs:
             if a.eval_mode != "step":
                 self.error("--host-envs evaluates on the host: --eval-mode must be 'step'")
@@ -127,6 +137,11 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--noisy", action="store_true",
                    help="NoisyLinear advantage / value heads (noisy_heads): noise redrawn on the device every SGD step "
                         "and publish; evaluation is greedy on mu")
+    p.add_argument("--atoms", type=int, default=d.dist_atoms,
+                   help="(--wide, fp32) categorical (C51) heads of this many atoms, 2..64 (dist_atoms, vecd_*): "
+                        "<= 8 actions; 0 = the scalar heads")
+    p.add_argument("--v-min", type=float, default=d.v_min, help="(--atoms) the support's lower end")
+    p.add_argument("--v-max", type=float, default=d.v_max, help="(--atoms) the support's upper end")
     p.add_argument("--learner-steps", type=int, default=1, help="(--host-envs) SGD steps per env step")
     p.add_argument("--host-serial", action="store_true",
                    help="(--host-envs) learner steps, then the acting step: no overlap with the host's env step")
@@ -178,7 +193,8 @@ def config_from_args(a) -> VectorEngineConfig:
                               publish_param_interval=a.publish_interval, seed=a.seed,
                               wide_net=a.wide, wide_dtype="fp32" if a.tall else a.dtype, tall_obs=a.tall,
                               tall_dtype=a.dtype if a.tall else "fp32",
-                              ring_dtype=a.ring_dtype, noisy_heads=a.noisy).validate(not a.host_envs)
+                              ring_dtype=a.ring_dtype, noisy_heads=a.noisy, dist_atoms=a.atoms, v_min=a.v_min,
+                              v_max=a.v_max).validate(not a.host_envs)
 
 
 def _crossed(t: int, prev: int, interval: int) -> bool:
